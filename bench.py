@@ -19,9 +19,16 @@ views, rank r renders view r, azimuth 45 r degrees) -- views are sharded, weak s
 fused all_gather of a 3-float metrics vector per step (RCCL over xGMI).
 
 Timing: W warm-up steps, then the K-step timed region (barrier + synchronize on both sides, max over ranks) is repeated
-`--repeats` times; `ms_per_step` / `value` are the MEDIAN region, min / max are reported beside it.
+`--repeats` times (default: once; with `--full` as many times as keep the GPU busy for ~3 s); `ms_per_step` / `value` are the
+MEDIAN region, min / max are reported beside it.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run does only what the headline needs: set up, warm up, time the K steps, print ONE JSON line (rank 0) with the driver's
+contract fields.  `--dump-outputs DIR` then also writes what the last timed step returned to its caller (images, gradients, ...) as
+DIR/<name>.npy (float32; integer / boolean outputs as float64), at most 64 MB in all: an array beyond its share of that budget is
+replaced by a fixed, seeded sample of its flattened elements (the same sample for the same shape).  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+`--full` adds everything else the line used to carry:
   "roofline":     dominant kernel (backward composite): algorithmic bytes (SURVEY 8d formula with the measured R)
                   / average kernel time from HIP events recorded on the launch stream DURING the timed steps,
                   against the 8 TB/s HBM peak; `traffic` = PMC bytes per launch from profiles/traffic_<workload>.json,
@@ -29,7 +36,9 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
   "shaded":       (N = 1, default workload only) the same measurement on cfg3_train -- shading + rasterizer forward +
                   backward, the "shaded + blended" number of north_star -- with its own roofline;
   "cpu_baseline": the CPU oracle (port of the reference kernels; the reference has no CPU path) timed on the host
-                  cores on a bounded number of the same steps (rank 0, N = 1 only).
+                  cores on a bounded number of the same steps (rank 0, N = 1 only);
+  and the per-stage table (`stage_ms`), the compact records of the other configurations, the rotating-camera and
+  several-views-in-flight records, and at N > 1 the single-GPU reference (`n1_same_workload`, `scaling_efficiency`).
 """
 import argparse
 import hashlib
@@ -121,13 +130,62 @@ def library_is_current():
         return False
 
 
+# what the binding layer returns (gaussian_renderer/{svgss,rgss}_rasterization.py _C), by name; the forward's trailing state buffers
+# (geometry, binning, image) are left out
+SVGSS_FWD = ("num_rendered", "color", "normal", "depth", "opacity", "feature", "vfeature", "weights", "radii")
+SVGSS_BWD = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dfeatures", "dL_dvfeatures", "dL_dcov3D", "dL_dsh",
+             "dL_dscales", "dL_drotations", "dL_dviewmat", "dL_dprojmat", "dL_dcampos")
+RGSS_FWD = ("num_rendered", "n_contrib", "color", "normal", "opacity", "depth", "feature", "pseudo_normal", "surface_xyz", "weights",
+            "radii")
+RGSS_BWD = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dfeatures", "dL_dcov3D", "dL_dsh", "dL_dscales",
+            "dL_drotations")
+DUMP_BYTES = 63_000_000   # (64 MB with room for the .npy headers)
+
+
+def host_outputs(arrays):
+    """{name: tensor / number} -> {name: numpy array}: float32, integer and boolean values as float64; None and empty arrays dropped."""
+    import numpy as np
+    import torch
+    out = {}
+    for k, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        if v is None:
+            continue
+        v = np.asarray(v)
+        if v.size == 0:
+            continue
+        out[k] = np.ascontiguousarray(v, dtype=np.float32 if v.dtype.kind == "f" else np.float64)
+    return out
+
+
+def dump_outputs(arrays, path):
+    """Writes `arrays` ({name: numpy array}) as path/<name>.npy, at most DUMP_BYTES in all.  Smallest first, every array gets an equal
+    share of what is left; one larger than its share is replaced by a sorted sample of its flattened elements drawn with a fixed seed
+    (the same elements for the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, names = DUMP_BYTES, sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    for i, k in enumerate(names):
+        a = arrays[k]
+        cap = left // (len(names) - i) // a.itemsize
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+        left -= a.nbytes
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=0, help="repetitions of the K-step timed region (median reported); 0 = as many as "
-                    "keep the GPU busy for ~3 s (at least 25, at most 500)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps per region (default 50; 3 for --workload tracers)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 5; 1 for --workload tracers)")
+    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the K-step timed region (median reported); default 1, "
+                    "with --full 0; 0 = as many as keep the GPU busy for ~3 s (at least 25, at most 500)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline / stage table, CPU "
+                    "baseline, shaded and compact records of the other configurations, rotating views, views in flight, N > 1 "
+                    "single-GPU reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--workload", default=None, help="default: cfg2 (N = 1), cfg4 (N > 1); also cfg3_train, cfg3_eval, cfg5, cfg5_dense, "
                     "train_step (whole stage-2 iteration), tracers (visibility / radiance cache producers)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -147,7 +205,15 @@ def parse():
     ap.add_argument("--samples", type=int, default=0, help="incident samples per surfel (default 64 train / 384 eval)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: exercise launch / collective / reporting logic with "
                     "gloo on the CPU (the rendering step is replaced by a token computation)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    tracers = args.workload == "tracers"   # (a tracers step is ~1.5 s)
+    if args.steps is None:
+        args.steps = 3 if tracers else 50
+    if args.warmup is None:
+        args.warmup = 1 if tracers else 5
+    if args.repeats is None:
+        args.repeats = (3 if tracers else 0) if args.full else 1
+    return args
 
 
 def visible_gpu_count():
@@ -251,6 +317,8 @@ class Workload:
             from gaussian_renderer.rgss_rasterization import _C
         self._C = _C
         self.empty = torch.empty(0, dtype=torch.float32, device=dev)
+        self.keep = False   # (--dump-outputs) step() keeps what it returned to the caller in self.last
+        self.last = None
         self.st = runner.settings(sct, variant)
         # svgss workloads: the per-surfel SV-BRDF shading (rendering_equation4 + feature packing) produces the rasterizer's
         # features / vfeatures every step, and its backward consumes the rasterizer's dL_dfeatures / dL_dvfeatures.
@@ -341,6 +409,8 @@ class Workload:
                                          st.sh_degree, st.campos, False, False, st.config, shade=fs)
             (R, color, normal, depth, opac, feat, vfeat, weights, radii, gb, bb, ib) = out
             if not self.train:
+                if self.keep:
+                    self._remember(out, SVGSS_FWD)
                 return R, color, weights
             kw = dict(out_weights=weights)
             if self.training:
@@ -354,6 +424,12 @@ class Workload:
                                                 st.patch_bbox, st.tanfovx, st.tanfovy, gt["color"], gt["normal"], gt["depth"],
                                                 gt["opacity"], gt["feature"], gt["vfeature"], sct["shs"], st.sh_degree, st.campos,
                                                 gb, R, bb, ib, False, st.config, **kw)
+            if self.keep:
+                if self.training:   # (dL_dfeatures / dL_dvfeatures are then intermediates with undefined rows; the shading's gradients are the result)
+                    self._remember(out, SVGSS_FWD, g, SVGSS_BWD, skip=("dL_dfeatures", "dL_dvfeatures"),
+                                   **{k: v for k, v in self.sgrads.items() if k.startswith("dL_d")})
+                else:
+                    self._remember(out, SVGSS_FWD, g, SVGSS_BWD)
         elif self.variant == "svgss":
             feats_in, vfeats_in = sct["features"], sct["vfeatures"]
             if self.shade:
@@ -378,6 +454,8 @@ class Workload:
                                          st.campos, False, False, st.config, features_ready=ready)
             (R, color, normal, depth, opac, feat, vfeat, weights, radii, gb, bb, ib) = out
             if not self.train:
+                if self.keep:
+                    self._remember(out, SVGSS_FWD)
                 return R, color, weights
             g = _C.rasterize_gaussians_backward(st.bg, sct["means3D"], feats_in.detach(), vfeats_in.detach(), radii, empty,
                                                 sct["scales"], sct["rotations"], st.scale_modifier, empty,
@@ -387,6 +465,9 @@ class Workload:
                                                 gb, R, bb, ib, False, st.config, out_weights=weights)
             if self.shade and self.training:
                 torch.autograd.backward([feats_in, vfeats_in], [g[4], g[5]])
+            if self.keep:
+                self._remember(out, SVGSS_FWD, g, SVGSS_BWD,
+                               **({"dL_d" + k: v.grad for k, v in self.leaves.items()} if self.shade and self.training else {}))
         else:
             out = _C.rasterize_gaussians(st.bg, sct["means3D"], sct["features"], empty, sct["opacities"],
                                          sct["scales"], sct["rotations"], st.scale_modifier, empty, st.viewmatrix,
@@ -398,7 +479,17 @@ class Workload:
                                                 st.projmatrix, st.tanfovx, st.tanfovy, gt["color"], gt["normal"],
                                                 gt["opacity"], gt["depth"], gt["feature"], sct["shs"], st.sh_degree,
                                                 st.campos, gb, R, bb, ib, True, False, out_weights=weights)
+            if self.keep:
+                self._remember(out, RGSS_FWD, g, RGSS_BWD)
         return R, color, g[3]
+
+    def _remember(self, out, names, g=None, gnames=(), skip=(), **extra):
+        """(--dump-outputs) what this step returned to its caller, by name: the forward's outputs (without its state buffers), the
+        backward's gradients and `extra`."""
+        self.last = dict(zip(names, out))
+        if g is not None:
+            self.last.update((n, t) for n, t in zip(gnames, g) if n not in skip)
+        self.last.update(extra)
 
 
 def timed(wl, args, world, dev, dry=None, solo=False, step_fn=None, stages=True):
@@ -465,6 +556,8 @@ def timed(wl, args, world, dev, dry=None, solo=False, step_fn=None, stages=True)
             nrep = int(t.item())
     for rep in range(nrep):
         regions.append(region())
+    if wl is not None and wl.keep:   # (--dump-outputs) what the last timed step returned, before anything else runs
+        wl.captured = host_outputs(wl.last)
     # Per-stage / per-kernel durations: ONE more region of the same K steps with the library's HIP-event stage marks on
     # (an event record per stage boundary costs ~4 us on the stream -- ~50 us per cfg2 step -- so the regions that
     # produce `value` run without them; this region is not part of `value`).
@@ -612,6 +705,13 @@ def shading_counts(wl):
     return nf, int((w > 0).sum())
 
 
+def shading_config(wl):
+    streamed = not isinstance(wl.dirs, wl.shading.FibonacciLattice)
+    return (f"rendering_equation4 + packing, Ns={wl.Ns} incident samples/surfel, env 32x64, incident directions "
+            f"{'streamed from HBM' if streamed else 'generated in the kernels (Fibonacci lattice)'}, "
+            f"{'forward+backward' if wl.training else 'forward only (eval)'}")
+
+
 def shading_record(wl, stage, counts=None):
     sf_per_sample = 32 if not isinstance(wl.dirs, wl.shading.FibonacciLattice) else 16
     # surfels the kernels actually shade: all P (--unfused), or the view's working set (fused); the byte model charges those
@@ -622,9 +722,7 @@ def shading_record(wl, stage, counts=None):
            "mode": "fused into svgir_forward / svgir_backward: the view's working set" if getattr(wl, "fused", False) else "all surfels (svgir_shade_forward / _backward around the rasterizer)",
            "radiance": ("the [P,Ns,3] cache is differentiated (--radiance-grad)" if getattr(wl, "rad_grad", False) else
                         "get_radiances = nan_to_num(_radiances.detach() * _radiance_ratio) formed in the kernels; the backward returns dL/d_radiance_ratio"),
-           "config": f"rendering_equation4 + packing, Ns={wl.Ns} incident samples/surfel, env 32x64, incident directions "
-                     f"{'streamed from HBM' if sf_per_sample == 32 else 'generated in the kernels (Fibonacci lattice)'}, "
-                     f"{'forward+backward' if wl.training else 'forward only (eval)'}",
+           "config": shading_config(wl),
            "fwd": {"avg_launch_ms": stage["shade_fwd"][0], "algorithmic_bytes_per_launch": sf, "bytes_per_sample": sf_per_sample,
                    "achieved": sf / (stage["shade_fwd"][0] * 1e-3) / 1e9, "unit": "GB/s",
                    "frac": sf / (stage["shade_fwd"][0] * 1e-3) / 1e9 / HBM_PEAK_GBS}}
@@ -852,20 +950,21 @@ def cpu_baseline(wl, args):
 
 
 def _time_regions(fn, args, dev):
-    """W warm-up calls, then `repeats` regions of K calls (synchronize on both sides); returns seconds per region."""
+    """W warm-up calls, then `repeats` regions of K calls (synchronize on both sides); returns (seconds per region, what the last call
+    returned)."""
     import torch
     for _ in range(args.warmup):
         fn()
     torch.cuda.synchronize()
-    out = []
+    out, last = [], None
     for _ in range(max(1, args.repeats or 25)):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            fn()
+            last = fn()
         torch.cuda.synchronize()
         out.append(time.perf_counter() - t0)
-    return out
+    return out, last
 
 
 def bench_train_step(args, dev):
@@ -875,8 +974,27 @@ def bench_train_step(args, dev):
     from gaussian_renderer import _native
     from svgir_harness import workloads
     ts = workloads.TrainStep(dev, radiance_grad=bool(getattr(args, "radiance_grad", False)))
-    regions = _time_regions(ts.step, args, dev)
+    regions, (R, pbr, loss) = _time_regions(ts.step, args, dev)
     med = float(np.median(regions))
+    outs = host_outputs(dict(num_rendered=R, pbr=pbr, loss=loss, **ts.last, **{"param_" + k: p for k, p in ts.params.items()})) \
+        if args.dump_outputs else {}   # (the last timed step: its image, loss, densification inputs and the parameters it updated)
+    res = {
+        "metric": "Gaussian-surfels/sec, whole stage-2 training iteration @800x800 (shade + rasterize + unpack + L1/SSIM + backward + Adam)",
+        "value": ts.P * args.steps / med, "unit": "surfels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": med / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic", "repeats": len(regions), "ms_per_step_min": min(regions) / args.steps * 1e3,
+        "ms_per_step_max": max(regions) / args.steps * 1e3,
+        "config": {"workload": f"train_step: cfg3_train scene (svgss, P={ts.P}, {ts.W}x{ts.H}, S=4, VS=52, Ns={ts.Ns}), one optimisation step per "
+                               f"step: FibonacciLattice (random azimuths) -> shade_and_pack -> GaussianRasterizer -> unpack -> l1_ssim -> "
+                               f"loss.backward() -> add_densification_stats -> FusedAdam.step(nan scrub, zero_grad) over {ts.n_param_elems} "
+                               f"parameter elements (geometry, SH, SV-BRDF, env map and " +
+                               ("the radiance cache as a differentiated leaf: --radiance-grad)" if ts.radiance_grad else
+                                "the scalar _radiance_ratio: the radiance cache enters detached as get_radiances = nan_to_num(_radiances.detach() * "
+                                "_radiance_ratio), scene/gaussian_model.py:323-324, 526-528 -- it sits in the optimizer but never has a gradient)"),
+                   "num_rendered": int(R), "reference": "train.py:133-134, gaussian_renderer/svgss.py:15-262, scene/gaussian_model.py:775-813, 1270-1276"},
+    }
+    if not args.full:
+        return res, outs
     # kernel-level stage marks of the library (rasterizer + shading stages) over one more region, and the phase table
     _native.set_profiling(True)
     for _ in range(args.steps):
@@ -898,30 +1016,17 @@ def bench_train_step(args, dev):
         counts = shading_counts(w3)
         del w3
     n_adam = ts.n_param_elems
-    res = {
-        "metric": "Gaussian-surfels/sec, whole stage-2 training iteration @800x800 (shade + rasterize + unpack + L1/SSIM + backward + Adam)",
-        "value": ts.P * args.steps / med, "unit": "surfels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": med / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic", "repeats": len(regions), "ms_per_step_min": min(regions) / args.steps * 1e3,
-        "ms_per_step_max": max(regions) / args.steps * 1e3,
-        "config": {"workload": f"train_step: cfg3_train scene (svgss, P={ts.P}, {ts.W}x{ts.H}, S=4, VS=52, Ns={ts.Ns}), one optimisation step per "
-                               f"step: FibonacciLattice (random azimuths) -> shade_and_pack -> GaussianRasterizer -> unpack -> l1_ssim -> "
-                               f"loss.backward() -> add_densification_stats -> FusedAdam.step(nan scrub, zero_grad) over {n_adam} parameter "
-                               f"elements (geometry, SH, SV-BRDF, env map and " +
-                               ("the radiance cache as a differentiated leaf: --radiance-grad)" if ts.radiance_grad else
-                                "the scalar _radiance_ratio: the radiance cache enters detached as get_radiances = nan_to_num(_radiances.detach() * "
-                                "_radiance_ratio), scene/gaussian_model.py:323-324, 526-528 -- it sits in the optimizer but never has a gradient)"),
-                   "num_rendered": int(R), "reference": "train.py:133-134, gaussian_renderer/svgss.py:15-262, scene/gaussian_model.py:775-813, 1270-1276"},
+    res.update({
         "phase_ms": {k: round(v, 4) for k, v in phases.items()},
         "stage_ms": {k: round(v[0], 4) for k, v in stage.items()},
         "roofline": roofline_of(w, R, stage, "cfg3_train"),
         "shading": {k: v for k, v in shading_record(w, stage, counts).items() if k != "config"},
         "optimizer": {"kernel": "adam_kernel (multi-tensor, NaN scrub)", "algorithmic_bytes_per_launch": 28 * n_adam,
                       "note": "28 B per parameter element (param, grad, two moments read; param, two moments written)"},
-    }
+    })
     if not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_train_step(ts, args)
-    return res
+    return res, outs
 
 
 def cpu_baseline_train_step(ts, args):
@@ -984,11 +1089,10 @@ def bench_tracers(args, dev):
     from svgir_harness import workloads
     tc = workloads.TracerCache(dev)
     args = argparse.Namespace(**vars(args))
-    args.steps = min(args.steps, 3); args.warmup = min(args.warmup, 1); args.repeats = min(args.repeats or 3, 3)   # a step is ~1.5 s
-    regions = _time_regions(tc.step, args, dev)
+    args.repeats = min(args.repeats or 3, 3)   # a step is ~1.5 s (parse(): 3 steps, 1 warm-up by default)
+    regions, (vis, rad, idx) = _time_regions(tc.step, args, dev)
     med = float(np.median(regions))
-    ms_vis, vis = tc.timed(tc.update_visibility, n=2)
-    ms_rad, (rad, vis2, idx) = tc.timed(tc.update_radiance, n=1)
+    outs = host_outputs(dict(visibility=vis, radiance=rad, hit_index=idx)) if args.dump_outputs else {}
     rays = 2 * tc.rays
     res = {
         "metric": "rays/sec, visibility + radiance cache update (BVH builds + trace_visibility + render_radiance_with_sampling_SH)",
@@ -999,6 +1103,12 @@ def bench_tracers(args, dev):
                                f"(sample_incident_rays), the reference's chunk loop (P // 3 surfels per call); one step = update_visibility "
                                f"+ update_radiace = {rays} rays",
                    "reference": "scene/gaussian_model.py:435-522, submodules/bvh/src/{construct,trace}.cu, pbgi/bvhworkers/intersect_test.slang:1879-1990"},
+    }
+    if not args.full:
+        return res, outs
+    ms_vis, vis = tc.timed(tc.update_visibility, n=2)
+    ms_rad, (rad, vis2, idx) = tc.timed(tc.update_radiance, n=1)
+    res.update({
         "producers": {"update_visibility": {"ms": ms_vis, "rays_per_s": tc.rays / (ms_vis * 1e-3), "mean_visibility": float(vis.mean())},
                       "update_radiance": {"ms": ms_rad, "rays_per_s": tc.rays / (ms_rad * 1e-3), "hit_fraction": float((idx >= 0).float().mean()),
                                           "mean_radiance": float(rad.mean())}},
@@ -1010,10 +1120,10 @@ def bench_tracers(args, dev):
                      "achieved": tc.rays * 40 / (ms_rad * 1e-3) / 1e9, "frac": tc.rays * 40 / (ms_rad * 1e-3) / 1e9 / HBM_PEAK_GBS,
                      "traffic": None,
                      "note": "divergent tree traversal: instruction-issue / latency bound (profiles/r04_tracer_pmc.txt), not an HBM stream"},
-    }
+    })
     if not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_tracers(tc, args)
-    return res
+    return res, outs
 
 
 def cpu_baseline_tracers(tc, args):
@@ -1068,7 +1178,7 @@ def main():
             return 100 + rank, tok * 2.0, tok + 1.0
 
         n1 = None
-        if world > 1:   # the same-workload single-rank reference of the N > 1 line (see below): rank 0 alone, the others wait
+        if world > 1 and args.full:   # the same-workload single-rank reference of the N > 1 line (see below): rank 0 alone, the others wait
             vp.barrier()
             if rank == 0:
                 sreg, _, _, _ = timed(None, args, world, dev, dry=dry_step, solo=True)
@@ -1095,18 +1205,23 @@ def main():
         sys.exit(2)
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
+    torch.manual_seed(0)   # (the device-side random draws of the svgss workloads: the same inputs in every run)
     if name in ("train_step", "tracers"):
         if world != 1:
             print(f"bench.py: --workload {name} is a single-GPU measurement", file=sys.stderr)
             sys.exit(2)
-        print(json.dumps(bench_train_step(args, dev) if name == "train_step" else bench_tracers(args, dev)))
+        res, outs = bench_train_step(args, dev) if name == "train_step" else bench_tracers(args, dev)
+        if args.dump_outputs:
+            dump_outputs(outs, args.dump_outputs)
+        print(json.dumps(res))
         return
     wl = Workload(name, dev, rank, world, args)
-    # N > 1: the line must carry its own single-GPU reference -- the SAME workload (rank 0's view of it) on ONE GPU of the same node,
+    wl.keep = bool(args.dump_outputs) and rank == 0
+    # N > 1 (--full): the line carries its own single-GPU reference -- the SAME workload (rank 0's view of it) on ONE GPU of the same node,
     # measured by the same process right before the concurrent regions while the other ranks wait at a barrier.  value / (N x that) is the
     # view-parallel scaling efficiency; the N = 1 default line times another workload (cfg2, BASELINE's headline) and is not comparable.
     n1 = None
-    if world > 1:
+    if world > 1 and args.full:
         vp.barrier()
         if rank == 0:
             sa = argparse.Namespace(**vars(args))
@@ -1114,7 +1229,9 @@ def main():
             sreg, sR, _, _ = timed(wl, sa, world, dev, solo=True, stages=False)
             n1 = (float(np.median(sreg)), int(sR))
         vp.barrier()
-    regions, R, stage, table = timed(wl, args, world, dev)
+    regions, R, stage, table = timed(wl, args, world, dev, stages=args.full)
+    if wl.keep:
+        dump_outputs(wl.captured, args.dump_outputs)
     # which physical GPU every rank ran on (a rank that silently fell back to another device would show up here)
     pr = torch.cuda.get_device_properties(dev)
     ids = vp.gather_rows(torch.tensor([float(torch.cuda.current_device()), float(getattr(pr, "pci_domain_id", -1)),
@@ -1138,13 +1255,14 @@ def main():
                        "per_rank_cpus": "pinned: cores split evenly over the ranks (bench.py pin_rank_to_cores)" if cores else "not pinned",
                        "per_rank_device": [{"rank": i, "ordinal": int(r[0]), "pci": "%04x:%02x:%02x" % (int(r[1]) & 0xffff, int(r[2]) & 0xff, int(r[3]) & 0xff)}
                                            for i, r in enumerate(ids)]},
-            "roofline": roofline_of(wl, R, stage, name),
-            "stage_ms": {k: round(v[0], 4) for k, v in stage.items()},
         }
         if wl.shade:
-            srec = shading_record(wl, stage)
-            res["config"]["shading"] = srec["config"]
-            res["shading"] = {k: v for k, v in srec.items() if k != "config"}
+            res["config"]["shading"] = shading_config(wl)
+        if args.full:
+            res["roofline"] = roofline_of(wl, R, stage, name)
+            res["stage_ms"] = {k: round(v[0], 4) for k, v in stage.items()}
+            if wl.shade:
+                res["shading"] = {k: v for k, v in shading_record(wl, stage).items() if k != "config"}
         if n1:
             v1 = wl.P * args.steps / n1[0]
             res["n1_same_workload"] = {"value": v1, "unit": "surfels/s", "ms_per_step": n1[0] / args.steps * 1e3, "num_rendered": n1[1],
@@ -1155,7 +1273,7 @@ def main():
                                    "N = 1 default line (cfg2) is BASELINE's headline and a different workload -- its cfg4 record "
                                    "(`configs.cfg4`) is the N = 1 point on another box")
     # the "shaded + blended" number of north_star: cfg3_train with the shading stage, same measurement, extra keys
-    if world == 1 and args.workload is None and not args.no_shaded:
+    if args.full and world == 1 and args.workload is None and not args.no_shaded:
         wl.sct = wl.gt = None
         torch.cuda.empty_cache()
         sa = argparse.Namespace(**vars(args))
@@ -1185,7 +1303,7 @@ def main():
                 res["rotating_views"][cname] = rotating_views(cname, dev, args, fixed)
             except Exception as e:   # noqa: BLE001
                 res["rotating_views"][cname] = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_concurrent:   # (last: it creates streams of its own)
+    if args.full and rank == 0 and world == 1 and not args.no_concurrent:   # (last: it creates streams of its own)
         torch.cuda.empty_cache()
         # (HIP streams share a few hardware queues, dealt in creation order: each record creates its streams right before it runs)
         ob = one_thread_batch(name, dev, args)
@@ -1194,7 +1312,7 @@ def main():
         torch.cuda.empty_cache()
         res["two_streams"] = two_streams(name, dev, args)
     # (last: the OpenMP oracle leaves its worker threads spinning for a while, which would slow the host-side launch loops above)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(wl, args)
     if rank == 0:
         print(json.dumps(res))

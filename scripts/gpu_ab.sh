@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for W in ${WORKLOADS:-cfg5}; do
   for spec in "$@"; do
     L=${spec%%:*}; E=${spec#*:}
-    env $E timeout 300 python bench.py --workload $W --steps 30 --warmup 5 --repeats ${REPEATS:-5} --no-cpu-baseline --no-shaded --no-concurrent ${BENCH_FLAGS:---no-shade} \
+    env $E timeout 300 python bench.py --full --workload $W --steps 30 --warmup 5 --repeats ${REPEATS:-5} --no-cpu-baseline --no-shaded --no-concurrent ${BENCH_FLAGS:---no-shade} \
         > gpurun_out/ab_${L}_$W.json 2> gpurun_out/ab_${L}_$W.err
     python - <<PY
 import json

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 TAG=${TAG:-it}
 if [ "${TESTS:-1}" = 1 ]; then timeout 1200 python -m pytest tests -q -m gpu -x 2>&1 | tail -15; fi
 for W in ${WORKLOADS:-cfg2 cfg3_train cfg3_eval}; do
-  timeout 300 python bench.py --workload $W --steps 30 --warmup 5 --repeats ${REPEATS:-9} --no-cpu-baseline --no-shaded ${BENCH_FLAGS:---no-shade} \
+  timeout 300 python bench.py --full --workload $W --steps 30 --warmup 5 --repeats ${REPEATS:-9} --no-cpu-baseline --no-shaded ${BENCH_FLAGS:---no-shade} \
       > gpurun_out/${TAG}_bench_$W.json 2> gpurun_out/${TAG}_bench_$W.err
   python - <<PY
 import json

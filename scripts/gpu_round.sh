@@ -5,6 +5,7 @@ export TMPDIR=/tmp
 R=$PWD
 TAG=${1:-x}
 mkdir -p gpurun_out
+B=${BENCH_OUT:-bench_out}; mkdir -p $B   # the bench.py --full lines
 if [ "${2:-}" != "quick" ]; then
   python -m pytest tests -q -m gpu -x 2>&1 | tail -5 > gpurun_out/${TAG}_tests.log
   cat gpurun_out/${TAG}_tests.log
@@ -13,15 +14,15 @@ for W in ${PMC_WORKLOADS:-cfg2 cfg3_train cfg3_eval cfg4 cfg5}; do   # PMC passe
   scripts/pmc_traffic.sh $W ${TAG}_$W > /dev/null 2>&1 && cp gpurun_out/${TAG}_${W}_traffic.json profiles/traffic_$W.json && cp gpurun_out/${TAG}_${W}_traffic.json gpurun_out/traffic_$W.json
   scripts/pmc_issue.sh $W ${TAG}_$W > /dev/null 2>&1 && cp gpurun_out/${TAG}_${W}_issue.json profiles/issue_$W.json && cp gpurun_out/${TAG}_${W}_issue.json gpurun_out/issue_$W.json
 done
-python bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
-tail -c 6000 gpurun_out/${TAG}_bench_default.json; tail -3 gpurun_out/${TAG}_bench_default.err
+python bench.py --full > $B/${TAG}_bench_default.json 2> $B/${TAG}_bench_default.err
+tail -c 6000 $B/${TAG}_bench_default.json; tail -3 $B/${TAG}_bench_default.err
 for W in cfg3_train cfg3_eval cfg4 cfg5 cfg5_dense; do
-  python bench.py --workload $W --no-cpu-baseline --repeats 5 > gpurun_out/${TAG}_bench_$W.json 2> gpurun_out/${TAG}_bench_$W.err
-  tail -c 3000 gpurun_out/${TAG}_bench_$W.json; tail -3 gpurun_out/${TAG}_bench_$W.err
+  python bench.py --full --workload $W --no-cpu-baseline --repeats 5 > $B/${TAG}_bench_$W.json 2> $B/${TAG}_bench_$W.err
+  tail -c 3000 $B/${TAG}_bench_$W.json; tail -3 $B/${TAG}_bench_$W.err
 done
 for W in train_step tracers; do   # the "next" rows of SURVEY 8: whole training iteration (f2 + f4), cache producers (f3)
-  python bench.py --workload $W > gpurun_out/${TAG}_bench_$W.json 2> gpurun_out/${TAG}_bench_$W.err
-  tail -c 3000 gpurun_out/${TAG}_bench_$W.json; tail -3 gpurun_out/${TAG}_bench_$W.err
+  python bench.py --full --workload $W > $B/${TAG}_bench_$W.json 2> $B/${TAG}_bench_$W.err
+  tail -c 3000 $B/${TAG}_bench_$W.json; tail -3 $B/${TAG}_bench_$W.err
 done
 for W in cfg2 cfg3_train cfg5 train_step tracers; do
   (cd /tmp && rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${TAG}_prof_$W -o p -- python3 $R/bench.py --steps 20 --warmup 3 --repeats 1 --no-cpu-baseline --no-shaded --no-concurrent --workload $W > $R/gpurun_out/${TAG}_prof_$W.log 2>&1)

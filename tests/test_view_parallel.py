@@ -92,12 +92,12 @@ def test_view_parallel_world2_gloo():
 def test_bench_self_launches_ranks_dry_run():
     """`python bench.py --gpus 2` without torchrun starts the two ranks itself (fresh processes, before anything touches
     the GPU), runs the timed regions with the per-step metrics all_gather (gloo here, RCCL on the GPUs) and prints ONE
-    JSON line with n_gpus = 2."""
+    JSON line with n_gpus = 2 (with --full: and its single-rank reference)."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1",
-                          "--repeats", "3"], env=env, capture_output=True, text=True, timeout=300)
+                          "--repeats", "3", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
