@@ -11,7 +11,6 @@
 #include <cstdio>
 #include <atomic>
 #include <cstdlib>
-#include <cstring>
 #include <ctime>
 #include <memory>
 #include <mutex>
@@ -19,6 +18,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "workload_history.hpp"
 
 using namespace svgir;
 
@@ -29,102 +29,13 @@ thread_local std::string g_err;
 // HIP events recorded on the launch stream; they are resolved lazily (svgir_last_timings), so enabling profiling
 // adds no synchronisation to forward/backward.
 std::atomic<bool> g_prof{false};
-// Speculative-capacity history: the instance counts of the last eight forwards PER WORKLOAD KEY (device, image size,
-// Gaussian count, channel widths, variant), so that scenes / resolutions that alternate in one process (a 256x256
-// preview next to a 1600x1600 render, several scenes, several devices) neither re-run each other's dependent stages nor
-// over-allocate each other's blobs.  A small fixed table, least-recently-used replacement.
-struct CapKey { int dev, W, H, P, S, VS, variant, scope; };
-// (P is NOT part of a workload's identity as long as it moves slowly: densification / pruning changes it every few hundred iterations,
-// scene/gaussian_model.py:1229-1253, and the history must survive that -- every sample remembers the Gaussian count it was taken at and
-// is scaled to the caller's: instances and state slots grow with the surfel count on a fixed view.  A caller whose P is more than a
-// factor of two away from the entry's latest sample is another model: it gets its own entry, and a scaled sample never exceeds four
-// times the largest unscaled one.  `scope` = svgir_params.workload_scope: models that share (device, image size, widths, variant) keep
-// separate histories by giving each its own id.)
-struct CapEntry { CapKey key; int hist[8]; int hist_P[8]; long long hist_slots[8]; int hist_slots_P[8]; unsigned next, next_slots; unsigned long long stamp; bool used;
-                  long long fill; int fill_P;   // non-empty 8x8 sub-tiles of the workload's latest view (-1 / 0: none seen), and its Gaussian count
-                  int top_byte, top_streak;   // common top byte of the visible depth keys of the last `top_streak` views (0: none / not common)
-                  const void* last_view; int last_view_P; };   // image blob of the workload's latest forward: its slot total is read when the next one starts
-std::mutex g_cap_mu;
-CapEntry g_cap[16];
-unsigned long long g_cap_clock = 0;
-bool same_key(const CapKey& a, const CapKey& b) {   // a: the entry's key (P = the Gaussian count of its latest sample), b: the caller's
-    if (!(a.dev == b.dev && a.W == b.W && a.H == b.H && a.S == b.S && a.VS == b.VS && a.variant == b.variant && a.scope == b.scope)) return false;
-    return a.P <= 0 || b.P <= 0 || ((long long)a.P <= 2ll * b.P && (long long)b.P <= 2ll * a.P);
-}
-CapEntry* cap_entry(const CapKey& k, bool create) {
-    CapEntry* lru = &g_cap[0];
-    for (auto& e : g_cap) {
-        if (e.used && same_key(e.key, k)) { e.stamp = ++g_cap_clock; return &e; }
-        if (!e.used) { if (lru->used) lru = &e; }
-        else if (lru->used && e.stamp < lru->stamp) lru = &e;
-    }
-    if (!create) return nullptr;
-    *lru = CapEntry{};
-    lru->key = k; lru->used = true; lru->stamp = ++g_cap_clock;
-    return lru;
-}
-inline long long scale_to(long long v, int from_P, int to_P) {   // a count measured at from_P Gaussians, expected at to_P
-    if (from_P <= 0 || from_P == to_P) return v;
-    return (long long)((double)v * (double)to_P / (double)from_P) + 1;
-}
-int guess_R(const CapKey& k) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    const CapEntry* e = cap_entry(k, false);
-    long long m = 0, raw = 0;
-    if (e) for (unsigned i = 0; i < std::min(e->next, 8u); i++) { m = std::max(m, scale_to(e->hist[i], e->hist_P[i], k.P)); raw = std::max<long long>(raw, e->hist[i]); }
-    return (int)std::min<long long>(std::min(m, 4 * raw), 0x7ffff000LL);
-}
-void record_R(const CapKey& k, int R) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    CapEntry* e = cap_entry(k, true);
-    e->hist[e->next % 8] = R; e->hist_P[e->next % 8] = k.P;
-    e->next++;
-    e->key.P = k.P;   // (the entry follows its model's Gaussian count)
-}
-// state slots (common.hpp seg_slots summed over the sub-tiles) of recent views of the workload: -1 = none seen yet
-long long guess_slots(const CapKey& k) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    const CapEntry* e = cap_entry(k, false);
-    long long m = -1, raw = 0;
-    if (e && e->next_slots) for (unsigned i = 0; i < std::min(e->next_slots, 8u); i++) { m = std::max(m, scale_to(e->hist_slots[i], e->hist_slots_P[i], k.P)); raw = std::max(raw, e->hist_slots[i]); }
-    return m < 0 ? m : std::min(m, 4 * raw + 64);
-}
-void record_slots(const CapKey& k, long long slots, long long nonempty) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    CapEntry* e = cap_entry(k, true);
-    e->hist_slots[e->next_slots % 8] = slots; e->hist_slots_P[e->next_slots % 8] = k.P;
-    e->next_slots++;
-    if (nonempty >= 0) { e->fill = nonempty + 1; e->fill_P = k.P; }   // (stored + 1: a zero-initialised entry has seen none)
-}
-// The FILL of the composite launch: non-empty sub-tiles (= waves with work) of the workload's latest view.  The forward composite exists in
-// two occupancy variants (render_fwd.hip): below ~4 rounds of waves the machine is under-filled and the variant with more registers per
-// wave wins; above, the one with more resident waves.  -1: no view seen yet.
-long long guess_fill(const CapKey& k) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    const CapEntry* e = cap_entry(k, false);
-    return (e && e->fill > 0) ? e->fill - 1 : -1;
-}
-// Depth-key speculation.  The depth keys are positive floats; in a bounded scene they share their top byte (sign + 7 exponent bits: all
-// depths in [2, 8), or [8, 32) ...), and then the fourth 8-bit pass of the depth sort orders nothing.  The preprocess reports AND / OR of
-// the visible keys' top bytes (read back with the instance count); once kTopStreak consecutive views of a workload had one common byte, the
-// next view is launched with three passes, its culled keys carrying that byte -- and re-run from scratch, with four, if a visible key
-// turns out to differ (the streak then starts over, so at most one view in kTopStreak + 1 can ever be re-run).
-constexpr int kTopStreak = 3;
-// {forwards, re-runs for the instance capacity, for the state-slot capacity, for the depth-key byte, views sorted in three passes}
-std::atomic<long long> g_spec_stats[5];
-int guess_top(const CapKey& k) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    const CapEntry* e = cap_entry(k, false);
-    return (e && e->top_streak >= kTopStreak) ? e->top_byte : -1;
-}
-void record_top(const CapKey& k, uint32_t summary) {   // {AND << 8 | OR}; AND = 0xff, OR = 0: nothing visible (no information)
-    const int av = (int)((summary >> 8) & 0xffu), ov = (int)(summary & 0xffu);
-    if (av == 0xff && ov == 0) return;
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    CapEntry* e = cap_entry(k, true);
-    if (av != ov) { e->top_streak = 0; return; }
-    if (e->top_streak > 0 && e->top_byte == av) e->top_streak = std::min(e->top_streak + 1, 1 << 20);
-    else { e->top_byte = av; e->top_streak = 1; }
+WorkloadHistory g_history;   // (workload_history.hpp)
+// zeroed pinned words, explicitly host-coherent: the device's system-scope stores must become visible to the polling host thread
+unsigned long long* pinned_words(size_t n) {
+    void* ptr = nullptr;
+    if (hipHostMalloc(&ptr, n * sizeof(unsigned long long), hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    std::fill_n((unsigned long long*)ptr, n, 0ull);
+    return (unsigned long long*)ptr;
 }
 // Pinned landing slots for the instance count (+ prefilter violation + depth-key summary): the scan's last block stores them there,
 // tagged, with system-scope stores -- no copy operation and no event on the stream -- and the host spins on the tag.  A slot belongs to
@@ -140,19 +51,9 @@ uint64_t g_pinned_busy[kPinnedSlots / 64];   // bit set: the slot is owned by a 
 struct PinnedSlot {
     unsigned long long* at = nullptr; uint32_t tag = 0; int index = -1;
     PinnedSlot() {
-        std::call_once(g_pinned_once, [] {
-            void* ptr = nullptr;
-            // (explicitly host-coherent: the device's system-scope stores must become visible to the polling host thread)
-            if (hipHostMalloc(&ptr, kPinnedSlots * 2 * sizeof(unsigned long long), hipHostMallocCoherent) == hipSuccess) {
-                g_pinned = (unsigned long long*)ptr;
-                for (unsigned i = 0; i < 2 * kPinnedSlots; i++) g_pinned[i] = 0ull;
-            } else {
-                (void)hipGetLastError();
-            }
-        });
-        uint32_t t = ++g_pinned_tag;
-        if (t == 0) t = ++g_pinned_tag;   // (never 0: the slots start as 0)
-        tag = t;
+        std::call_once(g_pinned_once, [] { g_pinned = pinned_words(2 * kPinnedSlots); });
+        tag = ++g_pinned_tag;
+        if (tag == 0) tag = ++g_pinned_tag;   // (never 0: the slots start as 0)
         if (!g_pinned) return;
         // (SVGIR_PINNED_SLOTS: fewer slots, for tests of the no-free-slot path)
         static const unsigned usable = [] { const char* e = getenv("SVGIR_PINNED_SLOTS"); return e ? (unsigned)std::min<long>(std::max<long>(atol(e), 0), kPinnedSlots) : kPinnedSlots; }();
@@ -212,7 +113,7 @@ bool pinned_spin(volatile unsigned long long* at, uint32_t tag, uint32_t* w0, ui
 // nothing: the composite is still queued (measured with a full event synchronisation there: 0.4353 vs 0.4361 ms per cfg2 step).
 struct ViewEntry { const void* key = nullptr; uint32_t tag = 0; int cap_R = 0; long long cap_slots = -1; unsigned long long stamp = 0;
                    bool recorded = false;   // its slot total has entered the workload's history
-                   hipStream_t stream = nullptr; bool has_stream = false; };   // the stream the forward ran on: what a waiter without a stream of its own blocks on   // its slot total has entered the workload's history
+                   hipStream_t stream = nullptr; };   // the stream the forward ran on: what a waiter without a stream of its own blocks on
 constexpr int kViewEntries = 1024;   // forwards whose backward may still come (least recently used entry replaced)
 std::mutex g_view_mu;
 ViewEntry g_view[kViewEntries];
@@ -223,12 +124,7 @@ uint32_t g_view_tag = 0;
 // registers the launch sequence of the forward that owns `image_blob`: returns where order_desc_kernel writes its totals and the tag
 unsigned long long* view_note(const void* image_blob, int cap_R, long long cap_slots, uint32_t* tag, hipStream_t stream) {
     std::lock_guard<std::mutex> lk(g_view_mu);
-    if (!g_view_pinned) {
-        void* ptr = nullptr;
-        if (hipHostMalloc(&ptr, kViewEntries * kViewWords * sizeof(unsigned long long), hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        g_view_pinned = (unsigned long long*)ptr;
-        for (int i = 0; i < kViewWords * kViewEntries; i++) g_view_pinned[i] = 0ull;
-    }
+    if (!g_view_pinned && !(g_view_pinned = pinned_words(kViewEntries * kViewWords))) return nullptr;
     int slot = 0;
     for (int i = 0; i < kViewEntries; i++) {
         if (g_view[i].key == image_blob) { slot = i; break; }
@@ -236,7 +132,7 @@ unsigned long long* view_note(const void* image_blob, int cap_R, long long cap_s
     }
     ViewEntry& e = g_view[slot];
     e.key = image_blob; e.stamp = ++g_view_clock; e.cap_R = cap_R; e.cap_slots = cap_slots; e.recorded = false;
-    e.stream = stream; e.has_stream = true;
+    e.stream = stream;
     e.tag = ++g_view_tag ? g_view_tag : ++g_view_tag;   // (never 0: the slots start as 0)
     *tag = e.tag;
     return g_view_pinned + kViewWords * slot;
@@ -245,82 +141,73 @@ unsigned long long* view_note(const void* image_blob, int cap_R, long long cap_s
 // longer knows -- more than kViewEntries forwards ago, or a binder that moved / cloned the saved buffer -- is still self-describing, like
 // the reference's blobs; the table is the fast path (no device read, no synchronisation).
 constexpr uint32_t kBlobMagic = 0x53564931u;   // "SVI1" in counters[3]: order_desc_kernel of this library version wrote the words behind it
-struct ViewCounts { int cap_R = 0; long long cap_slots = -1, pairs = -1, slots = -1; };
-// blocking read of the blob's own copy; the forward that wrote it must be complete on the device (the callers synchronise first)
-bool view_from_blob(const uint32_t* counters_dev, ViewCounts* out) {
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (!counters_dev || hipMemcpy(w, counters_dev, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (w[3] != kBlobMagic) return false;
-    out->pairs = (long long)w[1]; out->slots = (long long)w[2]; out->cap_R = (int)w[4];
-    out->cap_slots = (long long)((unsigned long long)w[5] | ((unsigned long long)w[6] << 32));
-    return true;
-}
-// the entry of the forward that owns `image_blob` (capacities; counts when `wait`): false = unknown blob.  The counts are in host memory
-// as soon as the forward's order kernel has run.  wait = 1: poll for spin_budget_s(), then BLOCK -- on `*sync_stream` when the caller has
-// the stream the forward ran on (or one ordered behind it), else on the stream the forward itself was launched on (remembered in the
-// entry; the whole device only if that stream no longer exists) -- and look again: a backlog in front of the forward is not an error,
-// and backlogs on OTHER streams (tracer updates of another view, a second model) are not waited for.  pairs / slots stay -1 only if the forward never wrote them (it failed on the device) or the entry was recycled.
-// wait = 2: one look.
-bool view_lookup(const void* image_blob, int wait, int* cap_R, long long* cap_slots, long long* pairs, long long* slots,
-                 const hipStream_t* sync_stream = nullptr, long long* nonempty = nullptr) {
-    volatile unsigned long long* at = nullptr;
+struct ViewCounts { bool known = false; int cap_R = 0; long long cap_slots = -1, pairs = -1, slots = -1, nonempty = -1; hipError_t err = hipSuccess; };
+enum class Wait { kCaps, kLook, kBlock };
+// The capacities and counts of the forward that owns `image_blob` (known = false: an unknown view), found in this order:
+//   1. the host table: the capacities (no device read, no synchronisation; kCaps: nothing else);
+//   2. the tagged pinned words: the counts, in host memory as soon as the forward's order kernel has run.  kLook looks once; kBlock polls
+//      for spin_budget_s(), then BLOCKS -- on `*stream` when the caller has the stream the forward ran on (or one ordered behind it),
+//      else on the stream the forward itself was launched on (remembered in the entry; the whole device only if that stream no longer
+//      exists) -- and looks again: a backlog in front of the forward is not an error, and backlogs on OTHER streams (tracer updates of
+//      another view, a second model) are not waited for;
+//   3. given `blob_counters` (the image blob's ImageLayout::counters), when the table does not know the view, its counts never arrived
+//      (the forward failed on the device, or the entry was recycled) or -- `caps`: a compact binning blob -- its entry has no slot
+//      capacity (an address reused by another view): the blob's own copy, read behind a synchronisation of `*stream`, or of the whole
+//      device when the caller has no stream (err: that synchronisation's error).
+// `record`: a view's slot total enters the history of workload *record once, through whoever sees it first: the workload's next forward
+// (kLook: the forward itself never waits for the cull) or the view's own backward (kBlock: the value is there by then).
+ViewCounts resolve_view(const void* image_blob, const uint32_t* blob_counters, Wait how, const hipStream_t* stream, bool caps = false,
+                        const CapKey* record = nullptr) {
+    ViewCounts out;
+    if (!image_blob) return out;
+    int i = 0;
     uint32_t tag = 0;
-    hipStream_t fwd_stream = nullptr; bool have_fwd_stream = false;
+    hipStream_t fwd_stream = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_view_mu);
-        for (int i = 0; i < kViewEntries; i++)
-            if (g_view[i].key == image_blob && g_view_pinned) {
-                at = g_view_pinned + kViewWords * i; tag = g_view[i].tag;
-                fwd_stream = g_view[i].stream; have_fwd_stream = g_view[i].has_stream;
-                if (cap_R) *cap_R = g_view[i].cap_R;
-                if (cap_slots) *cap_slots = g_view[i].cap_slots;
-                break;
-            }
+        while (g_view_pinned && i < kViewEntries && g_view[i].key != image_blob) i++;
+        if (!g_view_pinned || i == kViewEntries) i = -1;
+        else { tag = g_view[i].tag; fwd_stream = g_view[i].stream; out.cap_R = g_view[i].cap_R; out.cap_slots = g_view[i].cap_slots; }
     }
-    if (pairs) *pairs = -1;
-    if (slots) *slots = -1;
-    if (nonempty) *nonempty = -1;
-    if (!at) return false;
-    if (!wait) return true;
-    uint32_t w0 = 0, w1 = 0;
-    bool got = wait == 2 ? tagged_pair(at, tag, &w0, &w1) : pinned_spin(at, tag, &w0, &w1);
-    if (!got && wait == 1) {
-        hipError_t e = hipErrorInvalidHandle;
-        if (sync_stream) e = hipStreamSynchronize(*sync_stream);
-        else if (have_fwd_stream) {   // (the handle may be stale: a query tells; the null stream is always valid)
-            const hipError_t q = fwd_stream ? hipStreamQuery(fwd_stream) : hipSuccess;
-            if (q == hipSuccess || q == hipErrorNotReady) e = hipStreamSynchronize(fwd_stream);
-            else (void)hipGetLastError();
+    out.known = i >= 0;
+    if (out.known && how != Wait::kCaps) {
+        volatile unsigned long long* at = g_view_pinned + kViewWords * i;
+        uint32_t w0 = 0, w1 = 0;
+        bool got = how == Wait::kLook ? tagged_pair(at, tag, &w0, &w1) : pinned_spin(at, tag, &w0, &w1);
+        if (!got && how == Wait::kBlock) {
+            hipError_t e = hipErrorInvalidHandle;
+            if (stream) e = hipStreamSynchronize(*stream);
+            else {   // (the handle may be stale: a query tells; the null stream is always valid)
+                const hipError_t q = fwd_stream ? hipStreamQuery(fwd_stream) : hipSuccess;
+                if (q == hipSuccess || q == hipErrorNotReady) e = hipStreamSynchronize(fwd_stream);
+                else (void)hipGetLastError();
+            }
+            if (e != hipSuccess) { (void)hipGetLastError(); e = hipDeviceSynchronize(); }
+            if (e != hipSuccess) (void)hipGetLastError();
+            got = tagged_pair(at, tag, &w0, &w1);
         }
-        if (e != hipSuccess) { (void)hipGetLastError(); e = hipDeviceSynchronize(); }
-        if (e != hipSuccess) (void)hipGetLastError();
-        got = tagged_pair(at, tag, &w0, &w1);
-    }
-    if (got) {
-        if (pairs) *pairs = (long long)w0;
-        if (slots) *slots = (long long)w1;
-        const unsigned long long v2 = at[2];
-        if (nonempty && (uint32_t)(v2 >> 32) == tag) *nonempty = (long long)(uint32_t)v2;
-    }
-    return true;
-}
-// A view's state-slot total enters its workload's history once, through whoever sees it first: the workload's next forward (mode 2:
-// a look, no wait -- the forward itself never waits for the cull) or the view's own backward (mode 1: the value is there by then).
-void note_view_slots(const CapKey& k, const void* image_blob, int mode, const hipStream_t* sync_stream = nullptr) {
-    long long slots = -1, nonempty = -1;
-    if (!image_blob || !view_lookup(image_blob, mode, nullptr, nullptr, nullptr, &slots, sync_stream, &nonempty) || slots < 0) return;
-    {
-        std::lock_guard<std::mutex> lk(g_view_mu);
-        bool found = false;
-        for (int i = 0; i < kViewEntries; i++)
-            if (g_view[i].key == image_blob) {
-                if (g_view[i].recorded) return;
-                g_view[i].recorded = true; found = true;
-                break;
+        if (got) {
+            out.pairs = (long long)w0; out.slots = (long long)w1;
+            const unsigned long long v2 = at[2];
+            if ((uint32_t)(v2 >> 32) == tag) out.nonempty = (long long)(uint32_t)v2;
+            bool first = false;
+            if (record) {
+                std::lock_guard<std::mutex> lk(g_view_mu);
+                if (g_view[i].key == image_blob && !g_view[i].recorded) g_view[i].recorded = first = true;
             }
-        if (!found) return;
+            if (first) g_history.record_slots(*record, out.slots, out.nonempty);
+        }
     }
-    record_slots(k, slots, nonempty);
+    if (blob_counters && (!out.known || (caps && out.cap_slots < 0) || (how != Wait::kCaps && out.pairs < 0))) {
+        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        out.err = stream ? hipStreamSynchronize(*stream) : hipDeviceSynchronize();
+        const bool read = out.err == hipSuccess && hipMemcpy(w, blob_counters, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess;
+        if (out.err == hipSuccess && !read) (void)hipGetLastError();
+        if (!read || w[3] != kBlobMagic) return out;
+        out.known = true; out.pairs = (long long)w[1]; out.slots = (long long)w[2]; out.cap_R = (int)w[4];
+        out.cap_slots = (long long)((unsigned long long)w[5] | ((unsigned long long)w[6] << 32));
+    }
+    return out;
 }
 // Side stream of the backward: the gradient tensors are cleared there while the composite backward (which only writes the
 // scratch) runs on the caller's stream.  One per device, created on first use; fork / join through events.
@@ -421,14 +308,12 @@ void stage_mark(StageMarks& t, const char* name) {
 
 namespace {
 
-// Stage timer (stage_begin / stage_mark above): one event per stage boundary; consecutive pairs are queued for
-// lazy resolution.
-struct StageTimer {
-    StageMarks t;
-    explicit StageTimer(hipStream_t s) : t(stage_begin(s)) {}
-    void mark(const char* name) { stage_mark(t, name); }
-};
-
+// The tile grid of a W x H image
+struct ViewGrid { int W, H, gx, gy, T; };
+ViewGrid view_grid(int W, int H) {
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    return {W, H, gx, gy, (int)((long long)gx * gy)};
+}
 
 CfgRef cfg_ref(const svgir_params* p) {
     CfgRef c;
@@ -461,13 +346,12 @@ int validate(const svgir_params* p, bool fwd) {
     if (p->variant != SVGIR_RGSS && p->variant != SVGIR_SVGSS) return fail(SVGIR_ERR_INVALID, "unknown variant %d", p->variant);
     if (p->P < 0 || p->W <= 0 || p->H <= 0) return fail(SVGIR_ERR_INVALID, "bad sizes P=%d W=%d H=%d", p->P, p->W, p->H);
     if (p->P > 40000000) return fail(SVGIR_ERR_INVALID, "P=%d exceeds the supported 40 000 000 Gaussians (32-bit byte offsets into the splat records)", p->P);
-    {   // packing limits of the state blobs: tile rectangle x0 | y0 << 10 | width << 20 (common.hpp R_RECT) and
-        // (sub-tile id << SEG_K_BITS) | segment (seg_list)
-        const long long gx = (p->W + TILE - 1) / TILE, gy = (p->H + TILE - 1) / TILE;
-        if (gx > 1023 || gy > 1023 || 4 * gx * gy >= (1ll << (32 - SEG_K_BITS)))
-            return fail(SVGIR_ERR_INVALID, "image %dx%d exceeds the supported size (at most 1023 tiles per side, %lld tiles in total)",
-                        p->W, p->H, (1ll << (32 - SEG_K_BITS)) / 4 - 1);
-    }
+    // packing limits of the state blobs: tile rectangle x0 | y0 << 10 | width << 20 (common.hpp R_RECT) and
+    // (sub-tile id << SEG_K_BITS) | segment (seg_list)
+    const ViewGrid v = view_grid(p->W, p->H);
+    if (v.gx > 1023 || v.gy > 1023 || 4ll * v.gx * v.gy >= (1ll << (32 - SEG_K_BITS)))
+        return fail(SVGIR_ERR_INVALID, "image %dx%d exceeds the supported size (at most 1023 tiles per side, %lld tiles in total)",
+                    p->W, p->H, (1ll << (32 - SEG_K_BITS)) / 4 - 1);
     if (p->P == 0) return 0;
     if (!p->means3D || !p->viewmatrix || !p->projmatrix || !p->background)
         return fail(SVGIR_ERR_INVALID, "means3D/viewmatrix/projmatrix/background must be provided");
@@ -501,6 +385,51 @@ int validate(const svgir_params* p, bool fwd) {
     return 0;
 }
 
+CapKey workload_key(const svgir_params* p) {
+    int dev_id = 0;
+    (void)hipGetDevice(&dev_id);
+    return CapKey{dev_id, p->W, p->H, p->P, p->S, p->variant == SVGIR_SVGSS ? p->VS : 0, p->variant, p->workload_scope};
+}
+
+// The capacities a binning blob of `bytes` was laid out for, in vc->cap_R / cap_slots.  A blob with worst-case state slots (-1) tells
+// its instance capacity by its size; a compact one (an odd multiple of 128 bytes: a state-slot capacity of the forward's choosing) only
+// through its view, resolved for it (resolve_view) -- and for any blob when `how` asks for the counts.  false: a compact blob whose
+// view is unknown or carries no slot capacity.
+bool bin_capacity(size_t bytes, const char* image_blob, int W, int H, int nstate, Wait how, const hipStream_t* stream, ViewCounts* vc) {
+    const bool compact = bin_bytes_compact(bytes);
+    if (compact || how != Wait::kCaps)
+        *vc = resolve_view(image_blob, image_layout(const_cast<char*>(image_blob), W, H).counters, how, stream, compact);
+    if (compact) return vc->known && vc->cap_slots >= 0;
+    vc->cap_R = binning_capacity_from_bytes(bytes, view_grid(W, H).T, nstate);
+    vc->cap_slots = -1;
+    return true;
+}
+
+// The Gaussians and the camera, as the preprocess and geom_bwd read them
+template <class A> void camera_args(A& a, const svgir_params* p) {
+    a.P = p->P; a.D = p->D; a.M = p->M; a.means3D = p->means3D; a.shs = p->colors_precomp ? nullptr : p->shs;
+    a.scales = p->scales; a.rotations = p->rotations; a.view = p->viewmatrix; a.proj = p->projmatrix; a.campos = p->cam_pos;
+    a.scale_modifier = p->scale_modifier; a.tanx = p->tan_fovx; a.tany = p->tan_fovy; a.cfg = cfg_ref(p);
+    a.focal_x = p->W / (2.0f * p->tan_fovx); a.focal_y = p->H / (2.0f * p->tan_fovy);
+}
+
+// What the composite forward, the state re-dump and seg_build read of one view, from its blobs' layouts.  The callers set what differs:
+// the outputs, `needed`, `hi_fill`, `dump_only` and (the re-dump) the state slots.
+RenderArgs render_args(const svgir_params* p, const ViewGrid& v, const GeomLayout& G, const ImageLayout& I, const BinLayout& B, int fin) {
+    const bool svgss = p->variant == SVGIR_SVGSS;
+    RenderArgs ra{};
+    ra.W = v.W; ra.H = v.H; ra.gx = v.gx; ra.gy = v.gy; ra.S = p->S; ra.VS = svgss ? p->VS : 0;
+    ra.ranges = I.ranges; ra.point_list = B.val[fin]; ra.rec = G.rec; ra.features = p->features; ra.vfeatures = p->vfeatures;
+    ra.bg = p->background; ra.cfg = cfg_ref(p);
+    ra.sub_list = B.sub_list; ra.sub_total = I.sub_total; ra.sub_order = I.sub_order; ra.sub_count = I.sub_count; ra.sub_ndump = I.sub_ndump;
+    ra.sub_pair_base = I.sub_pair_base; ra.sub_slot_base = I.sub_slot_base;
+    ra.seg_list = B.seg_list; ra.seg_desc = B.seg_desc; ra.seg_count = I.counters; ra.seg_block = I.seg_block; ra.seg_state = B.seg_state;
+    ra.slot_cap = (uint32_t)std::min<size_t>(B.slot_cap, 0xffffffffu);
+    ra.order_n = (int)order_entries(v.gx, v.gy);
+    ra.bg_in_render = render_specialised(p->S, ra.VS, svgss) ? 1 : 0;
+    ra.final_T = I.final_T; ra.final_D = I.final_D; ra.n_contrib = I.n_contrib;
+    return ra;
+}
 }  // namespace
 
 extern "C" {
@@ -509,8 +438,7 @@ int svgir_abi_version(void) { return SVGIR_ABI_VERSION; }
 size_t svgir_geom_bytes(int32_t P) { return geom_layout(nullptr, P).bytes; }
 size_t svgir_image_bytes(int32_t W, int32_t H) { return image_layout(nullptr, W, H).bytes; }
 size_t svgir_binning_bytes(int32_t R, int32_t W, int32_t H, int32_t S, int32_t VS) {
-    const int T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-    return bin_layout(nullptr, binning_capacity(R), T, seg_nstate(S, VS)).bytes;
+    return bin_layout(nullptr, binning_capacity(R), view_grid(W, H).T, seg_nstate(S, VS)).bytes;
 }
 size_t svgir_image_ncontrib_offset(int32_t W, int32_t H) { return image_layout(nullptr, W, H).ncontrib_off; }
 size_t svgir_image_ranges_offset(int32_t W, int32_t H) {
@@ -518,20 +446,10 @@ size_t svgir_image_ranges_offset(int32_t W, int32_t H) {
     return (size_t)((char*)I.ranges - (char*)256);
 }
 size_t svgir_binning_point_list_offset(size_t binning_bytes, const char* image_blob, int32_t W, int32_t H, int32_t S, int32_t VS) {
-    const int T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-    const int nstate = seg_nstate(S, VS);
-    int cap = 0;
-    if (bin_bytes_compact(binning_bytes)) {   // laid out for a state-slot capacity of the forward's choosing: the view's entry knows
-        if (!image_blob) return (size_t)-1;
-        if (!view_lookup(image_blob, false, &cap, nullptr, nullptr, nullptr)) {   // not in the host table: the blob's own copy
-            ViewCounts vc;
-            if (hipDeviceSynchronize() != hipSuccess || !view_from_blob(image_layout(const_cast<char*>(image_blob), W, H).counters, &vc)) return (size_t)-1;
-            cap = vc.cap_R;
-        }
-    } else {
-        cap = binning_capacity_from_bytes(binning_bytes, T, nstate);
-    }
-    const BinLayout B = bin_layout((char*)256, cap, T, nstate);   // (the instance arrays come first: independent of the slot capacity)
+    const int T = view_grid(W, H).T, nstate = seg_nstate(S, VS);
+    ViewCounts vc;
+    if (!bin_capacity(binning_bytes, image_blob, W, H, nstate, Wait::kCaps, nullptr, &vc)) return (size_t)-1;
+    const BinLayout B = bin_layout((char*)256, vc.cap_R, T, nstate);   // (the instance arrays come first: independent of the slot capacity)
     return (size_t)((char*)B.val[tile_sort_plan(T).passes & 1] - (char*)256);
 }
 const char* svgir_last_error(void) { return g_err.c_str(); }
@@ -562,81 +480,57 @@ int svgir_last_timings(const char** names, float* avg_ms, int* counts, int cap) 
 // confirms the guess, or re-runs the dependent stages) and returns it.  svgir_forward is begin() + finish(); svgir_forward_batch begins all
 // its views before it finishes the first, so that ONE host thread keeps several views in flight (on as many streams).
 struct ForwardCall {
-    const svgir_params* p; const svgir_outputs* o;
-    svgir_alloc_fn geom, binning, image; void *geom_ctx, *binning_ctx, *image_ctx;
-    hipStream_t s; bool key_spec;
+    const svgir_view_call c; const svgir_params* p = c.params; const svgir_outputs* o = c.outputs; hipStream_t s = (hipStream_t)c.stream;
+    bool key_spec;
     // set by begin()
-    int P = 0, W = 0, H = 0, gx = 0, gy = 0, T = 0, nstate = 0, fin = 0, spec_top = -1, cap = 0;
-    size_t N = 0;
+    int P = 0, nstate = 0, fin = 0, spec_top = -1, cap = 0;
+    ViewGrid v{};
     bool svgss = false, shade_subset = false, prepass = false, done = false;
-    CfgRef cfg{}; float focal_x = 0.f, focal_y = 0.f;
     char *gblob = nullptr, *iblob = nullptr, *bblob = nullptr;
     GeomLayout G{}; ImageLayout I{}; TileSortPlan plan{};
     CapKey ckey{}; const uint32_t* depth_order = nullptr; long long cap_slots = -1;
     hipEvent_t features_ready = nullptr;
-    PinnedSlot R_pin; unsigned long long* R_slot = nullptr; uint32_t R_tag = 0;
-    const uint32_t* prefilter_violation = nullptr;
-    StageTimer tm;
+    PinnedSlot R_pin;   // (the landing slot of the instance count, released when this call object dies)
+    StageMarks tm;   // (stage_begin / stage_mark: one event per stage boundary, resolved lazily)
 
-    ForwardCall(const svgir_params* p_, const svgir_outputs* o_, svgir_alloc_fn geom_, void* geom_ctx_, svgir_alloc_fn binning_,
-                void* binning_ctx_, svgir_alloc_fn image_, void* image_ctx_, void* stream, bool key_spec_)
-        : p(p_), o(o_), geom(geom_), binning(binning_), image(image_), geom_ctx(geom_ctx_), binning_ctx(binning_ctx_), image_ctx(image_ctx_),
-          s((hipStream_t)stream), key_spec(key_spec_), tm((hipStream_t)stream) {}
+    ForwardCall(const svgir_view_call& c_, bool key_spec_) : c(c_), key_spec(key_spec_), tm(stage_begin(s)) {}
 
     int check(const char* what) {
-        if (!p->debug) {
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SVGIR_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-            return 0;
-        }
-        hipError_t e = hipStreamSynchronize(s);  // reference CHECK_CUDA(debug), auxiliary.h:425-432
+        hipError_t e = p->debug ? hipStreamSynchronize(s) : hipSuccess;  // reference CHECK_CUDA(debug), auxiliary.h:425-432
         if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) return fail(SVGIR_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-        return 0;
+        return e != hipSuccess ? fail(SVGIR_ERR_HIP, p->debug ? "%s failed: %s" : "%s launch failed: %s", what, hipGetErrorString(e)) : 0;
     }
 
     // Everything behind the offsets scan depends on the instance count R that the GPU is still computing.  The stages are launched for an
     // instance CAPACITY `cap` and read R on the device (min(cap, R)); the binning blob is laid out for `cap`.  `timed`: stage marks are
     // only recorded for the launch sequence that counts.
     int run_binning_and_render(char* bblob, int cap, long long cap_slots, bool timed, bool cull_only = false) {
-        const BinLayout B = bin_layout(bblob, cap, T, nstate, cap_slots);
-        launch_emit(P, depth_order, G.tiles, G.offsets, G.rec, o->radii, gx, gy, B.key[0], B.val[0], cap, I.ranges,
+        const BinLayout B = bin_layout(bblob, cap, v.T, nstate, cap_slots);
+        launch_emit(P, depth_order, G.tiles, G.offsets, G.rec, o->radii, v.gx, v.gy, B.key[0], B.val[0], cap, I.ranges,
                     I.counters, B.radix_tbl, G.counters + 3, s);
         if (int rc = check("emit")) return rc;
-        if (timed) tm.mark("emit");
+        if (timed) stage_mark(tm, "emit");
         if (plan.single) {   // up to 4096 tiles: one counting pass over the whole tile id, which also yields the tile ranges
-            launch_tile_sort12(B.key, B.val, cap, G.counters, B.radix_tbl, I.ranges, T, s);
+            launch_tile_sort12(B.key, B.val, cap, G.counters, B.radix_tbl, I.ranges, v.T, s);
             if (int rc = check("tile sort")) return rc;
-            if (timed) tm.mark("sort_tile");
+            if (timed) stage_mark(tm, "sort_tile");
         } else {
             launch_radix_sort(B.key, B.val, cap, G.counters, plan.bits, plan.bits_per_pass, B.radix_tbl, s);
             if (int rc = check("tile sort")) return rc;
-            if (timed) tm.mark("sort_tile");
-            launch_ranges(cap, G.counters, B.key[fin], I.ranges, T, s);
+            if (timed) stage_mark(tm, "sort_tile");
+            launch_ranges(cap, G.counters, B.key[fin], I.ranges, v.T, s);
             if (int rc = check("ranges")) return rc;
-            if (timed) tm.mark("ranges");
+            if (timed) stage_mark(tm, "ranges");
         }
 
-        RenderArgs ra;
-        ra.W = W; ra.H = H; ra.gx = gx; ra.gy = gy; ra.S = p->S; ra.VS = svgss ? p->VS : 0;
-        ra.ranges = I.ranges; ra.point_list = B.val[fin]; ra.rec = G.rec; ra.features = p->features; ra.vfeatures = p->vfeatures;
-        ra.bg = p->background;
-        ra.cfg = cfg; ra.sub_list = B.sub_list; ra.sub_total = I.sub_total; ra.sub_order = I.sub_order;
-        ra.sub_pair_base = I.sub_pair_base; ra.sub_slot_base = I.sub_slot_base; ra.slot_cap = (uint32_t)std::min<size_t>(B.slot_cap, 0xffffffffu);
-        ra.dump_only = 0;
-        ra.hi_fill = high_fill(guess_fill(ckey)) ? 1 : 0;
-        ra.order_n = (int)order_entries(gx, gy);
-        ra.bg_in_render = render_specialised(p->S, svgss ? p->VS : 0, svgss) ? 1 : 0;
-        ra.sub_count = I.sub_count;
-        ra.sub_ndump = I.sub_ndump; ra.seg_list = B.seg_list; ra.seg_desc = B.seg_desc; ra.seg_count = I.counters; ra.seg_block = I.seg_block; ra.seg_state = B.seg_state;
-        ra.final_T = I.final_T; ra.final_D = I.final_D; ra.n_contrib = I.n_contrib;
+        RenderArgs ra = render_args(p, v, G, I, B, fin);
+        ra.hi_fill = high_fill(g_history.guess_fill(ckey)) ? 1 : 0;
         ra.out_color = o->out_color; ra.out_normal = o->out_normal; ra.out_depth = o->out_depth; ra.out_opacity = o->out_opacity;
         ra.out_feature = o->out_feature; ra.out_vfeature = o->out_vfeature; ra.out_weights = o->out_weights;
         // rgss without computer_pseudo_normal: the two stencil outputs are all zero (rasterize_points.cu:85-86)
         const bool clear_stencil = !svgss && !p->computer_pseudo_normal;
         ra.zero_a = clear_stencil ? o->out_pseudo_normal : nullptr;
         ra.zero_b = clear_stencil ? o->out_surface_xyz : nullptr;
-        ra.needed = nullptr;
         launch_cull(ra, s);
         // dispatch order of the sub-tiles, first gradient row / first state slot of each, and the two totals (device + tagged host copy)
         uint32_t vtag = 0;
@@ -645,17 +539,17 @@ struct ForwardCall {
         // (a launch of many rounds of waves gets one longest-first list per XCD instead of one global list: common.hpp ORDER_NONE)
         static const int xcd_forced = [] { const char* e = getenv("SVGIR_FWD_XCD"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
         const bool per_xcd = ra.bg_in_render && (xcd_forced >= 0 ? xcd_forced != 0 : ra.hi_fill != 0);   // (specialised composite kernels only)
-        launch_order_desc(I.sub_total, 4 * T, I.sub_order, row_path ? I.sub_pair_base : nullptr, I.sub_slot_base, I.counters, vslot, vtag,
-                          (uint32_t)cap, cap_slots, kBlobMagic, gx, ra.order_n, per_xcd, s);
+        launch_order_desc(I.sub_total, 4 * v.T, I.sub_order, row_path ? I.sub_pair_base : nullptr, I.sub_slot_base, I.counters, vslot, vtag,
+                          (uint32_t)cap, cap_slots, kBlobMagic, v.gx, ra.order_n, per_xcd, s);
         if (int rc = check("cull")) return rc;
-        if (timed) tm.mark("cull");
+        if (timed) stage_mark(tm, "cull");
         if (cull_only) return 0;   // (the sizing phase of a workload's first view: see finish())
         if (prepass) {
             RenderArgs rp = ra;
             rp.S = 0; rp.VS = 0; rp.features = nullptr; rp.vfeatures = nullptr; rp.needed = G.needed;
             launch_contrib_prepass(rp, s);
             if (int rc = check("prepass")) return rc;
-            if (timed) tm.mark("prepass");
+            if (timed) stage_mark(tm, "prepass");
         }
         if (p->shade) {
             // The per-splat shading of this view, for the surfels its composite is about to read (the reference shades all P before
@@ -672,12 +566,12 @@ struct ForwardCall {
             if (shade_forward_impl(&sp, p->shade->reduced, const_cast<float*>(p->features), const_cast<float*>(p->vfeatures), true, s) != 0)
                 return fail(SVGIR_ERR_INVALID, "fused shading: svgir_shade_forward rejected its parameters");
             if (int rc = check("shade")) return rc;
-            if (timed) tm.mark("shade");
+            if (timed) stage_mark(tm, "shade");
         }
         if (features_ready && hipStreamWaitEvent(s, features_ready, 0) != hipSuccess) return fail(SVGIR_ERR_HIP, "waiting for the features event");
         if (launch_render_fwd(ra, svgss, s) < 0) launch_render_fwd_generic(ra, svgss, s);   // run-time-width kernels
         if (int rc = check("render")) return rc;
-        if (timed) tm.mark("render");
+        if (timed) stage_mark(tm, "render");
         // (the list of live backward segments is built by svgir_backward, next to its clears: a forward-only call never pays for it)
         return 0;
     }
@@ -688,13 +582,11 @@ struct ForwardCall {
         // features / vfeatures may still be in production on another stream (the shading kernels do not depend on the binning and
         // the binning does not read them): only the composite kernel waits for the caller's event
         features_ready = (hipEvent_t)p->features_ready;
-        if (!o || !geom || !binning || !image) return fail(SVGIR_ERR_INVALID, "outputs / allocators must be provided");
-        P = p->P; W = p->W; H = p->H;
-        N = (size_t)W * H;
-        gx = (W + TILE - 1) / TILE; gy = (H + TILE - 1) / TILE; T = gx * gy;
+        if (!o || !c.geom || !c.binning || !c.image) return fail(SVGIR_ERR_INVALID, "outputs / allocators must be provided");
+        P = p->P; v = view_grid(p->W, p->H);
         svgss = p->variant == SVGIR_SVGSS;
-        cfg = cfg_ref(p);
         if (P == 0) {  // rasterize_points.cu:100: nothing runs, outputs stay zero
+            const size_t N = (size_t)v.W * v.H;
             HIP_OK(hipMemsetAsync(o->out_color, 0, 3 * N * 4, s));
             HIP_OK(hipMemsetAsync(o->out_normal, 0, 3 * N * 4, s));
             HIP_OK(hipMemsetAsync(o->out_depth, 0, N * 4, s));
@@ -706,20 +598,16 @@ struct ForwardCall {
             done = true;
             return 1;
         }
-        focal_y = H / (2.0f * p->tan_fovy); focal_x = W / (2.0f * p->tan_fovx);
-        gblob = geom(geom_layout(nullptr, P).bytes, geom_ctx);
-        iblob = image(image_layout(nullptr, W, H).bytes, image_ctx);
+        gblob = c.geom(geom_layout(nullptr, P).bytes, c.geom_ctx);
+        iblob = c.image(image_layout(nullptr, v.W, v.H).bytes, c.image_ctx);
         if (!gblob || !iblob) return fail(SVGIR_ERR_ALLOC, "geometry/image blob allocation failed");
         G = geom_layout(gblob, P);
-        I = image_layout(iblob, W, H);
+        I = image_layout(iblob, v.W, v.H);
 
         PreArgs pa;
-        pa.P = P; pa.D = p->D; pa.M = p->M; pa.W = W; pa.H = H; pa.gx = gx; pa.gy = gy;
-        pa.means3D = p->means3D; pa.shs = p->colors_precomp ? nullptr : p->shs; pa.colors_precomp = p->colors_precomp;
-        pa.opacities = p->opacities; pa.scales = p->scales; pa.rotations = p->rotations; pa.cov3D_precomp = p->cov3D_precomp;
-        pa.view = p->viewmatrix; pa.proj = p->projmatrix; pa.campos = p->cam_pos; pa.patchbbox = p->patchbbox;
-        pa.scale_modifier = p->scale_modifier; pa.tanx = p->tan_fovx; pa.tany = p->tan_fovy;
-        pa.focal_x = focal_x; pa.focal_y = focal_y; pa.cfg = cfg;
+        camera_args(pa, p);
+        pa.W = v.W; pa.H = v.H; pa.gx = v.gx; pa.gy = v.gy; pa.colors_precomp = p->colors_precomp; pa.opacities = p->opacities;
+        pa.cov3D_precomp = p->cov3D_precomp; pa.patchbbox = p->patchbbox;
         pa.rec = G.rec; pa.cov3D = G.cov3D; pa.clamped = G.clamped; pa.tiles = G.tiles; pa.key = G.key[0]; pa.idx = G.idx[0];
         pa.radii = o->radii;
         pa.out_weights = o->out_weights;
@@ -739,11 +627,9 @@ struct ForwardCall {
         pa.span = G.counters + 3;
         if (p->shade) pa.tabs = shade_tables(&p->shade->sp, nullptr, 0);   // (the preprocess launch carries the shading kernels' tables)
         pa.zero_words = radix_gtot(G.radix_tbl, P); pa.n_zero_words = (int)radix_gtot_words(P);
-        int dev_id = 0;
-        (void)hipGetDevice(&dev_id);
-        ckey = CapKey{dev_id, W, H, P, p->S, svgss ? p->VS : 0, p->variant, p->workload_scope};
+        ckey = workload_key(p);
         static const bool key_spec_env = getenv("SVGIR_NO_KEY_SPEC") == nullptr;
-        spec_top = (key_spec && key_spec_env) ? guess_top(ckey) : -1;
+        spec_top = (key_spec && key_spec_env) ? g_history.guess_top(ckey) : -1;
         pa.spec_top = spec_top; pa.key_top = G.key_top;
         pa.prefilter_violation = nullptr;
         if (p->prefiltered) {   // the violation flag sits next to the instance counter and is read back with it
@@ -752,41 +638,35 @@ struct ForwardCall {
         }
         launch_preprocess(pa, svgss, s);
         if (int rc = check("preprocess")) return rc;
-        tm.mark("preprocess");
+        stage_mark(tm, "preprocess");
 
         // depth sort of the P Gaussians: 4 x 8-bit stable passes (ends in slot 0), or 3 when the top byte is speculated to be common (slot 1)
         const int depth_bits = spec_top >= 0 ? 24 : 32;
         depth_order = G.idx[(depth_bits / 8) & 1];
         launch_radix_sort(G.key, G.idx, P, nullptr, depth_bits, 8, G.radix_tbl, s);
         if (int rc = check("depth sort")) return rc;
-        tm.mark("sort_depth");
+        stage_mark(tm, "sort_depth");
 
-        R_slot = R_pin.at; R_tag = R_pin.tag;   // (the slot is released when this call object dies)
         launch_offsets_scan(G.tiles, depth_order, G.offsets, G.scan_tmp, P, G.counters, G.key_top, (P + 63) / 64, pa.prefilter_violation,
-                            R_slot, R_tag, s);
+                            R_pin.at, R_pin.tag, s);
         if (int rc = check("offsets scan")) return rc;
-        tm.mark("scan");
+        stage_mark(tm, "scan");
 
-        prefilter_violation = pa.prefilter_violation;
         nstate = seg_nstate(p->S, svgss ? p->VS : 0);
-        plan = tile_sort_plan(T);
+        plan = tile_sort_plan(v.T);
         fin = plan.passes & 1;
 
         // Speculative launch: capacities from this workload's recent views (+12.5 %) -- instances (binning arrays) and state slots
         // (seg_state) -- no host round trip in between.  The first view of a workload gets the exact instance capacity and the worst-case
         // slot count (4 full lists per tile); later ones typically a third of that.
         cap = 0; cap_slots = -1; bblob = nullptr;
-        {   // the previous view of this workload: its slot total, if the backward has not recorded it already (forward-only loops)
-            const void* prev = nullptr;
-            CapKey pkey = ckey;
-            { std::lock_guard<std::mutex> lk(g_cap_mu); if (const CapEntry* e = cap_entry(ckey, false)) { prev = e->last_view; pkey.P = e->last_view_P; } }
-            note_view_slots(pkey, prev, 2);
-        }
-        if (const int guess = guess_R(ckey)) {
+        CapKey pkey = ckey;   // the previous view of this workload: its slot total, if the backward has not recorded it already (forward-only loops)
+        (void)resolve_view(g_history.last_view(ckey, &pkey.P), nullptr, Wait::kLook, nullptr, false, &pkey);
+        long long gs = -1;
+        if (const int guess = g_history.guess(ckey, &gs)) {
             cap = binning_capacity((long long)guess + guess / 8 + 1024);
-            const long long gs = guess_slots(ckey);
-            cap_slots = p->forward_only ? 0 : (gs < 0 ? -1 : std::min<long long>(gs + gs / 8 + 64, (long long)seg_capacity(cap, T)));
-            bblob = binning(bin_layout(nullptr, cap, T, nstate, cap_slots).bytes, binning_ctx);
+            cap_slots = p->forward_only ? 0 : (gs < 0 ? -1 : std::min<long long>(gs + gs / 8 + 64, (long long)seg_capacity(cap, v.T)));
+            bblob = c.binning(bin_layout(nullptr, cap, v.T, nstate, cap_slots).bytes, c.binning_ctx);
             // (a failed speculative allocation is not an error: the guess may be far larger than this view needs; fall
             // through to the exact-size path below)
             if (bblob) {
@@ -798,13 +678,19 @@ struct ForwardCall {
         return 0;
     }
 
+    static int run(const svgir_view_call& c, bool key_spec) {
+        ForwardCall f(c, key_spec);
+        const int rc = f.begin();
+        return rc != 0 ? (rc < 0 ? rc : 0) : f.finish();
+    }
+
     // waits for the instance count, confirms (or repairs) the speculation; returns R or a negative status
     int finish() {
         if (done) return 0;
         done = true;
         // the instance count (only: the speculative stages keep running)
         uint32_t R_host = 0, R_aux = 0;
-        bool have_R = R_slot && pinned_spin(R_slot, R_tag, &R_host, &R_aux);
+        bool have_R = R_pin.at && pinned_spin(R_pin.at, R_pin.tag, &R_host, &R_aux);
         if (!have_R) {
             // The count is further away than the spin budget -- a backlog in front of this forward on the stream (the reference's call order
             // puts update_visibility / update_radiace, seconds of work, right before a render), a shared GPU, a serialising profiler -- or no
@@ -812,7 +698,7 @@ struct ForwardCall {
             // a slow stream is not an error.
             const hipError_t e = hipStreamSynchronize(s);
             if (e != hipSuccess) return fail(SVGIR_ERR_HIP, "the forward failed on the device: %s", hipGetErrorString(e));
-            have_R = R_slot && tagged_pair(R_slot, R_tag, &R_host, &R_aux);
+            have_R = R_pin.at && tagged_pair(R_pin.at, R_pin.tag, &R_host, &R_aux);
             if (!have_R) {   // the counters' device copy (same three words)
                 uint32_t w[3] = {0, 0, 0};
                 HIP_OK(hipMemcpy(w, G.counters, 12, hipMemcpyDeviceToHost));
@@ -827,26 +713,24 @@ struct ForwardCall {
         const int R = (int)R_host;
         {   // the visible depth keys' top bytes: history for the next view; and did this view's speculation hold?
             const uint32_t summary = R_aux & 0xffffu;
-            if (key_spec) { record_top(ckey, summary); g_spec_stats[0]++; }
-            if (spec_top >= 0) g_spec_stats[4]++;
+            if (key_spec) { g_history.record_top(ckey, summary); g_history.count(WorkloadHistory::kForwards); }
+            if (spec_top >= 0) g_history.count(WorkloadHistory::kThreePass);
             const int av = (int)((summary >> 8) & 0xffu), ov = (int)(summary & 0xffu);
             if (spec_top >= 0 && !(av == 0xff && ov == 0) && (av != spec_top || ov != spec_top)) {
                 // a visible key outside the speculated byte: the three-pass order is wrong -- run the whole view again, four passes
                 HIP_OK(hipStreamSynchronize(s));
-                g_spec_stats[3]++;
-                ForwardCall again(p, o, geom, geom_ctx, binning, binning_ctx, image, image_ctx, (void*)s, false);
-                if (int rc = again.begin()) return rc < 0 ? rc : 0;
-                return again.finish();
+                g_history.count(WorkloadHistory::kRerunTop);
+                return run(c, false);
             }
         }
-        record_R(ckey, R);
+        g_history.record_R(ckey, R);
         // (whether the state-slot guess held is the backward's business -- svgir_backward re-dumps the states of a view that exceeded it; the
         // forward does not wait for the cull.  Measured on the host-bound training step, bench.py --workload train_step: 2.11 ms with
         // the wait and a re-run here, see HISTORY.md 4)
         if (!bblob || R > cap) {
             // first view, or the scene grew past a guess: (re)do the dependent stages -- exact instance capacity, worst-case state slots
             const bool redo = bblob != nullptr;
-            if (redo) { HIP_OK(hipStreamSynchronize(s)); g_spec_stats[1]++; }
+            if (redo) { HIP_OK(hipStreamSynchronize(s)); g_history.count(WorkloadHistory::kRerunR); }
             cap = binning_capacity(R);
             cap_slots = p->forward_only ? 0 : -1;
             if (cap_slots < 0 && R > 0) {
@@ -855,48 +739,308 @@ struct ForwardCall {
                 // cull run once into a stream-ordered temporary WITHOUT state slots, the view's own slot total comes back (the same tagged
                 // store the backward reads), and the blob the caller keeps is laid out for exactly that.  ~0.2 ms, once per workload.
                 void* tmp = nullptr;
-                if (hipMallocAsync(&tmp, bin_layout(nullptr, cap, T, nstate, 0).bytes, s) == hipSuccess) {
+                if (hipMallocAsync(&tmp, bin_layout(nullptr, cap, v.T, nstate, 0).bytes, s) == hipSuccess) {
                     const int rc = run_binning_and_render((char*)tmp, cap, 0, false, true);
-                    long long slots = -1;
-                    if (rc == 0) (void)view_lookup(iblob, 1, nullptr, nullptr, nullptr, &slots, &s);
+                    const ViewCounts vc = rc == 0 ? resolve_view(iblob, nullptr, Wait::kBlock, &s) : ViewCounts{};
                     (void)hipFreeAsync(tmp, s);
                     if (rc) return rc;
-                    if (slots >= 0) cap_slots = std::min<long long>(slots, (long long)seg_capacity(cap, T));
+                    if (vc.slots >= 0) cap_slots = std::min<long long>(vc.slots, (long long)seg_capacity(cap, v.T));
                 } else {
                     (void)hipGetLastError();   // (no temporary: the worst-case layout, as before)
                 }
             }
-            bblob = binning(bin_layout(nullptr, cap, T, nstate, cap_slots).bytes, binning_ctx);
+            bblob = c.binning(bin_layout(nullptr, cap, v.T, nstate, cap_slots).bytes, c.binning_ctx);
             if (!bblob) return fail(SVGIR_ERR_ALLOC, "binning blob allocation failed");
             if (redo && o->out_weights) HIP_OK(hipMemsetAsync(o->out_weights, 0, (size_t)P * 4, s));   // accumulated by atomics
             if (int rc = run_binning_and_render(bblob, cap, cap_slots, !redo)) return rc;
         }
-        {
-            std::lock_guard<std::mutex> lk(g_cap_mu);
-            CapEntry* e = cap_entry(ckey, true);
-            e->last_view = iblob; e->last_view_P = P;
-        }
+        g_history.set_last_view(ckey, iblob, P);
 
         if (!svgss && p->computer_pseudo_normal) {
-            launch_image_ops(W, H, p->viewmatrix, focal_x, focal_y, p->cx, p->cy, o->out_opacity, o->out_depth,
-                             o->out_pseudo_normal, o->out_surface_xyz, s);
+            launch_image_ops(v.W, v.H, p->viewmatrix, v.W / (2.0f * p->tan_fovx), v.H / (2.0f * p->tan_fovy), p->cx, p->cy, o->out_opacity,
+                             o->out_depth, o->out_pseudo_normal, o->out_surface_xyz, s);
             if (int rc = check("image ops")) return rc;
-            tm.mark("image");
+            stage_mark(tm, "image");
         }
         return R;
     }
 };
 
-}  // extern "C"  (the call object is C++)
+// One svgir_backward, as the named steps of run(), in the order of their launches.
+struct BackwardCall {
+    const svgir_params* p; const svgir_grads* g; int R; const int32_t* radii; char *geom_blob, *binning_blob; size_t binning_bytes;
+    char *image_blob, *scratch; size_t scratch_bytes; hipStream_t s;
+    ViewCounts caps;   // the binning blob's capacities (cap_R, cap_slots)
+    ViewGrid v{};
+    bool svgss = false;
+    GeomLayout G{}; ImageLayout I{}; BinLayout B{};
+    RenderArgs ra{};
+    StageMarks tm{};
+    RenderBwdArgs ba{};
+    bool generic = false, rows = false, clear_in_kernel = false;
+    ShadeTables shade_tabs;   // (env == nullptr: the shading backward launches its own prologue)
+    const uint32_t* blended = nullptr; const uint32_t* blended_n = nullptr;
+    // scope guards: every exit -- the error returns included -- joins the side stream of the clears with the caller's stream (and
+    // releases the event), then frees the re-dumped states
+    struct FreeAsync { void* p; hipStream_t s; ~FreeAsync() { if (p) (void)hipFreeAsync(p, s); } } redump{nullptr, s};
+    struct ClearJoin {
+        hipStream_t s; hipEvent_t ev = nullptr;
+        void join() {
+            if (ev) { (void)hipStreamWaitEvent(s, ev, 0); (void)hipEventDestroy(ev); ev = nullptr; }
+        }
+        ~ClearJoin() { join(); }
+    } cleared{s};
 
-extern "C" {
+    int run() {
+        if (int rc = locate()) return rc < 0 ? rc : 0;
+        tm = stage_begin(s);
+        if (int rc = redump_states()) return rc;
+        if (int rc = clears()) return rc;
+        if (int rc = seg_build()) return rc;
+        composite();
+        grad_reduce();
+        if (int rc = shade_backward()) return rc;
+        return geom_backward();
+    }
+
+    // validates the call, lays the blobs out and fills the composite's arguments: a negative status, 0, or 1 (nothing to do: P == 0)
+    int locate() {
+        if (int rc = validate(p, false)) return rc;
+        if (p->P == 0) return 1;
+        if (!g || !radii || !geom_blob || !binning_blob || !image_blob)
+            return fail(SVGIR_ERR_INVALID, "grads / radii / blobs must be provided");
+        if (p->shade) {   // fused shading: everything its backward needs, checked BEFORE anything is launched (no half-written gradients on a bad call)
+            if (!g->dL_dbase_color || !g->dL_droughness || !g->dL_dshade_normals || (!g->dL_dradiance && !p->shade->sp.radiance_ratio) || !g->dL_denv ||
+                !g->env_grad_work)
+                return fail(SVGIR_ERR_INVALID, "fused shading: the gradient outputs of the shading inputs must be provided");
+            if (!render_specialised(p->S, p->VS, true)) return fail(SVGIR_ERR_INVALID, "fused shading without a specialised composite");
+            if (g->dL_dreduced && !p->shade->all_surfels) return fail(SVGIR_ERR_INVALID, "fused shading: dL_dreduced needs all_surfels");
+            if (!p->shade->all_surfels && !g->out_weights) return fail(SVGIR_ERR_INVALID, "fused shading: out_weights (the forward's) must be provided");
+        }
+        v = view_grid(p->W, p->H);
+        svgss = p->variant == SVGIR_SVGSS;
+        G = geom_layout(geom_blob, p->P);
+        I = image_layout(image_blob, v.W, v.H);
+        const int nstate = seg_nstate(p->S, svgss ? p->VS : 0);
+        // (a compact blob is described by its view: the host table, else -- an old forward, or a binder that moved the saved buffer --
+        // the image blob's own copy)
+        if (!bin_capacity(binning_bytes, image_blob, v.W, v.H, nstate, Wait::kCaps, &s, &caps)) {
+            if (caps.err != hipSuccess) return fail(SVGIR_ERR_HIP, "hipStreamSynchronize(s) failed: %s", hipGetErrorString(caps.err));
+            return fail(SVGIR_ERR_INVALID, "the binning blob (%zu bytes) has a compact layout, but the image blob does not describe it "
+                                           "(not the image blob of the same svgir_forward?)", binning_bytes);
+        }
+        if (caps.cap_R < R || bin_layout(nullptr, caps.cap_R, v.T, nstate, caps.cap_slots).bytes != binning_bytes)
+            return fail(SVGIR_ERR_INVALID, "binning blob of %zu bytes does not match any layout for R=%d", binning_bytes, R);
+        B = bin_layout(binning_blob, caps.cap_R, v.T, nstate, caps.cap_slots);
+        ra = render_args(p, v, G, I, B, tile_sort_plan(v.T).passes & 1);
+        // the composite backward: what it shares with the forward's composite, then its gradients and its scratch.  Composite gradients go
+        // through the scratch: svgss (VS > 0) -> one row per (instance, sub-tile) pair, summed per Gaussian by grad_reduce (no atomics,
+        // deterministic); otherwise one packed row per Gaussian accumulated with float atomics and unpacked by geom_bwd.
+        ba.W = ra.W; ba.H = ra.H; ba.gx = ra.gx; ba.gy = ra.gy; ba.S = ra.S; ba.VS = ra.VS;
+        ba.ranges = ra.ranges; ba.point_list = ra.point_list; ba.rec = ra.rec; ba.features = ra.features; ba.vfeatures = ra.vfeatures;
+        ba.bg = ra.bg; ba.cfg = ra.cfg; ba.sub_list = ra.sub_list; ba.sub_count = ra.sub_count; ba.sub_ndump = ra.sub_ndump;
+        ba.seg_list = ra.seg_list; ba.seg_desc = ra.seg_desc; ba.seg_count = ra.seg_count; ba.seg_state = ra.seg_state;
+        ba.final_T = ra.final_T; ba.final_D = ra.final_D; ba.n_contrib = ra.n_contrib;
+        ba.seg_cap = (int)B.seg_cap;
+        ba.backward_geometry = p->backward_geometry;
+        ba.g_color = g->dL_dout_color; ba.g_normal = g->dL_dout_normal; ba.g_depth = g->dL_dout_depth;
+        ba.g_opacity = g->dL_dout_opacity; ba.g_feature = g->dL_dout_feature; ba.g_vfeature = g->dL_dout_vfeature;
+        ba.dL_dmean2D = g->dL_dmeans2D; ba.dL_dconic = g->dL_dconic; ba.dL_dopacity = g->dL_dopacity; ba.dL_dcolor = g->dL_dcolors;
+        ba.dL_dfeature = g->dL_dfeatures; ba.dL_dvfeature = g->dL_dvfeatures; ba.dL_dnormal = g->dL_dnormal; ba.dL_ddepth = g->dL_ddepth;
+        generic = !render_specialised(p->S, ba.VS, svgss);   // run-time-width kernels: atomics on the dL_d* tensors
+        rows = ba.VS > 0 && !generic;
+        ba.grad_rows = generic ? nullptr : (float*)scratch;
+        if (rows && scratch) {   // reverse map (cleared) | compact rows (no scratch: refused by clears())
+            ba.row_of = (uint32_t*)scratch;
+            ba.grad_rows = (float*)(scratch + grad_rowof_bytes(caps.cap_R));
+            ba.rows_cap = (uint32_t)std::min<size_t>((scratch_bytes - grad_rowof_bytes(caps.cap_R)) / ((size_t)grad_row_geom(p->S, ba.VS).RS * 4),
+                                                     0xfffffff0u);
+        }
+        return 0;
+    }
+
+    // The forward dumped its blend states into slots sized from the workload's previous views and never waited to learn whether this
+    // view fits (that wait stalls a host-bound training loop).  By now the view's slot total is in host memory: it enters the
+    // workload's history, and if it exceeds the capacity the states are dumped AGAIN, all of them, into a stream-ordered temporary -- a
+    // replay of the composite forward that writes nothing else (one extra forward composite on the rare view that outgrows its guess).
+    int redump_states() {
+        // (state slots in use: the backward never runs on slots it has not verified -- when the slot total is not in host memory even
+        // after blocking on the stream, the table entry was recycled or the blob came from elsewhere, and the blob's own copy tells)
+        const bool verify = caps.cap_slots >= 0 && R > 0;
+        const CapKey ckey = workload_key(p);
+        const ViewCounts vc = resolve_view(image_blob, verify ? I.counters : nullptr, Wait::kBlock, &s, false, &ckey);
+        if (verify && vc.slots < 0) {
+            if (vc.err != hipSuccess) return fail(SVGIR_ERR_HIP, "hipStreamSynchronize(s) failed: %s", hipGetErrorString(vc.err));
+            return fail(SVGIR_ERR_INVALID, "the image blob does not carry this view's state-slot total (forward failed, or a foreign blob)");
+        }
+        const long long slots = verify ? vc.slots : -1;
+        static const bool trace = getenv("SVGIR_TRACE_SPEC") != nullptr;
+        if (trace) fprintf(stderr, "[svgir] backward: R=%d capacity=%d state slots: capacity %lld, view %lld%s\n", R, caps.cap_R, caps.cap_slots, slots, (verify && slots > caps.cap_slots) ? " -> re-dump" : "");
+        if (!verify || slots <= caps.cap_slots) return 0;
+        if (!render_specialised(p->S, svgss ? p->VS : 0, svgss)) return fail(SVGIR_ERR_INVALID, "state slots without a specialised composite");
+        HIP_OK(hipMallocAsync(&redump.p, align_up((size_t)slots * seg_nstate(p->S, ra.VS) * 64 * 4), s));
+        ba.seg_state = ra.seg_state = (float*)redump.p;
+        g_history.count(WorkloadHistory::kRerunSlots);
+        RenderArgs rd = ra;
+        rd.slot_cap = (uint32_t)std::min<long long>(slots, 0xffffffffll);
+        rd.dump_only = 1;
+        if (launch_render_fwd(rd, svgss, s) < 0) return fail(SVGIR_ERR_INVALID, "state re-dump: no specialised composite");
+        stage_mark(tm, "state_redump");
+        return 0;
+    }
+
+    // Clears (behind the check of the caller's scratch):
+    //   1. the backward scratch (gradient-row validity bytes / packed rows), needed by the composite backward: it rides on the launch
+    //      that builds the list of live segments (one kernel in front of the composite instead of a memset + that kernel);
+    //   2. the dL_d* outputs, which start from zero (the kernels write the visible Gaussians only): the specialised composite
+    //      backward does not touch them (it accumulates in the scratch), so this clear runs on a side stream next to it and is joined
+    //      before the per-Gaussian kernels; the run-time-width composite adds into them, so there the clear comes first, on the
+    //      caller's stream.
+    int clears() {
+        // (svgss rows: sized for the pair count of this view when the forward's read-back of it is at hand, else for the worst case)
+        const size_t need = svgir_backward_scratch_bytes_for(p->variant, p->P, binning_bytes, image_blob, v.W, v.H, p->S, ba.VS);
+        if (!generic && (!scratch || scratch_bytes < need))
+            return fail(SVGIR_ERR_INVALID, "backward scratch of %zu bytes is smaller than svgir_backward_scratch_bytes_for() = %zu",
+                        scratch ? scratch_bytes : (size_t)0, need);
+        // (one allocation behind all gradient tensors, 16-byte granular, and a specialised composite about to run: its waves clear it)
+        clear_in_kernel = !generic && R > 0 && g->clear_base && g->clear_bytes && (((uintptr_t)g->clear_base | g->clear_bytes) & 15) == 0;
+        ba.clear = clear_in_kernel ? (uint4*)g->clear_base : nullptr;
+        ba.clear_n16 = clear_in_kernel ? g->clear_bytes / 16 : 0;
+        if (!clear_in_kernel) {
+            hipStream_t cs = generic ? s : side_stream(s);
+            if (!cs) cs = s;
+            hipEvent_t ev_fork = nullptr;
+            if (cs != s) {   // the tensors may have been used on `s` before (stream-ordered allocators): order the clear after that
+                HIP_OK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+                HIP_OK(hipEventRecord(ev_fork, s));
+                HIP_OK(hipStreamWaitEvent(cs, ev_fork, 0));
+                (void)hipEventDestroy(ev_fork);
+            }
+            const size_t Pz = (size_t)p->P * 4;
+            if (g->clear_base && g->clear_bytes) {
+                HIP_OK(hipMemsetAsync(g->clear_base, 0, g->clear_bytes, cs));
+            } else {
+                struct { float* p; size_t n; } t[] = {
+                    {g->dL_dmeans2D, 3 * Pz}, {g->dL_dconic, 4 * Pz}, {g->dL_dopacity, Pz}, {g->dL_dcolors, 3 * Pz},
+                    {g->dL_dfeatures, (size_t)p->S * Pz}, {g->dL_dvfeatures, (size_t)ba.VS * Pz}, {g->dL_dnormal, 3 * Pz},
+                    {g->dL_ddepth, Pz}, {g->dL_dmeans3D, 3 * Pz}, {g->dL_dcov3D, 6 * Pz}, {g->dL_dsh, (size_t)p->M * 3 * Pz},
+                    {g->dL_dscales, 3 * Pz}, {g->dL_drotations, 4 * Pz}, {svgss ? g->dL_dviewmat : nullptr, 64},
+                    {svgss ? g->dL_dprojmat : nullptr, 64}, {svgss ? g->dL_dcampos : nullptr, 12}};
+                for (auto& e : t)
+                    if (e.p && e.n) HIP_OK(hipMemsetAsync(e.p, 0, e.n, cs));
+            }
+            if (cs != s) {
+                HIP_OK(hipEventCreateWithFlags(&cleared.ev, hipEventDisableTiming));
+                HIP_OK(hipEventRecord(cleared.ev, cs));
+            }
+        }
+        return 0;
+    }
+
+    // live backward segments, longest first (common.hpp SEG), from the forward's per-sub-tile counts: built here -- a forward-only call
+    // never pays for it -- together with the scratch clear; then the partition of the blended surfels
+    int seg_build() {
+        void* sc_clear = rows ? (void*)ba.row_of : (void*)ba.grad_rows;   // (null: run-time-width kernels, no scratch)
+        const size_t sc_bytes = rows ? grad_rowof_bytes(caps.cap_R) : align_up((size_t)p->P * grad_row_geom(p->S, ba.VS).RS * 4);
+        bool use_list = false;
+        if (R > 0) {
+            // (fused shading: the same launch builds the tables and zeroes the env-gradient accumulator of the shading backward below)
+            if (p->shade && g->env_grad_work) shade_tabs = shade_tables(&p->shade->sp, g->env_grad_work, p->shade->sp.env_h * p->shade->sp.env_w * 3);
+            // (and counts, per chunk, the surfels that received a blend weight: the first half of the partition the per-Gaussian kernels walk)
+            use_list = g->out_weights && !generic && (p->shade || p->P >= (rows ? kListMinPRows : kListMinP));
+            launch_seg_build(ra, sc_clear, sc_bytes, shade_tabs, use_list ? g->out_weights : nullptr, p->P, G.shade_work, s);
+        } else if (sc_clear && !rows) {
+            HIP_OK(hipMemsetAsync(sc_clear, 0, sc_bytes, s));   // (nothing rendered: geom_bwd still unpacks the -- zero -- packed rows)
+        }
+        stage_mark(tm, "seg_build");
+        // The surfels that received a blend weight (the forward's out_weights > 0): only they own gradient rows, only their per-Gaussian
+        // gradients are non-zero, only their shading is differentiated.  With the weights at hand the per-Gaussian kernels behind the
+        // composite walk that list (13-29 % of the model on the BASELINE scenes) instead of all P.
+        if (use_list && R > 0) {
+            uint32_t* cnt = G.shade_work + partition_work_words(p->P) - 1;
+            launch_partition_scatter(p->P, g->out_weights, G.shade_list, G.shade_work, cnt, s);
+            blended = G.shade_list; blended_n = cnt;
+        }
+        return 0;
+    }
+
+    void composite() {
+        if (R > 0) {
+            if (generic) launch_render_bwd_generic(ba, svgss, s);
+            else (void)launch_render_bwd(ba, svgss, s);
+        }
+        stage_mark(tm, "render_bwd");
+        cleared.join();
+    }
+
+    void grad_reduce() {
+        if (!(R > 0 && rows)) return;
+        GradReduceArgs ga;
+        ga.list = blended; ga.list_count = blended_n;
+        ga.P = p->P; ga.S = p->S; ga.VS = ba.VS; ga.radii = radii; ga.tiles = G.tiles; ga.rec = G.rec;
+        ga.grad_rows = ba.grad_rows; ga.row_of = ba.row_of;
+        ga.dL_dmean2D = g->dL_dmeans2D; ga.dL_dconic = g->dL_dconic; ga.dL_dopacity = g->dL_dopacity; ga.dL_dcolor = g->dL_dcolors;
+        ga.dL_dfeature = g->dL_dfeatures; ga.dL_dvfeature = g->dL_dvfeatures; ga.dL_dnormal = g->dL_dnormal; ga.dL_ddepth = g->dL_ddepth;
+        launch_grad_reduce(ga, s);
+        stage_mark(tm, "grad_reduce");
+    }
+
+    // dL_dfeatures / dL_dvfeatures are complete: the shading's backward, for the surfels that received a blend weight (the rows of all
+    // others are exactly zero: no pixel blended them)
+    int shade_backward() {
+        if (!p->shade) return 0;
+        const bool all = p->shade->all_surfels != 0;   // (the arguments were validated before the first launch)
+        svgir_shade_params sp = p->shade->sp;
+        sp.subset = nullptr; sp.subset_count = nullptr;
+        if (!all) {
+            if (!blended) {   // (R == 0: nothing was blended -- the partition of all-zero weights zero-fills every row)
+                uint32_t* cnt = G.shade_work + partition_work_words(p->P) - 1;
+                launch_partition(p->P, nullptr, g->out_weights, G.shade_list, G.shade_work, cnt, s);
+                blended = G.shade_list; blended_n = cnt;
+            }
+            sp.subset = blended; sp.subset_count = blended_n;
+        }
+        // (a binder that lays the four per-surfel gradient tensors out inside clear_base gets their zero rows from the composite
+        // backward's clearing sweep -- stores nobody waits for -- instead of a zero-fill launch in front of the shading backward)
+        auto in_clear = [&](const float* t, size_t floats) {
+            const char* b = (const char*)g->clear_base, *q = (const char*)t;
+            return clear_in_kernel && q >= b && q + floats * 4 <= b + g->clear_bytes;
+        };
+        const size_t Pz = (size_t)p->P;
+        const bool precleared = in_clear(g->dL_dbase_color, 12 * Pz) && in_clear(g->dL_droughness, 4 * Pz) &&
+                                in_clear(g->dL_dshade_normals, 12 * Pz) &&
+                                (!g->dL_dradiance || in_clear(g->dL_dradiance, 3 * Pz * (size_t)sp.Ns));
+        if (shade_backward_impl(&sp, g->dL_dreduced, g->dL_dfeatures, g->dL_dvfeatures, g->dL_dbase_color, g->dL_droughness,
+                                g->dL_dshade_normals, g->dL_dradiance, g->dL_denv, g->env_grad_work, g->dL_dradiance_ratio, precleared,
+                                shade_tabs.env != nullptr, s) != 0)
+            return fail(SVGIR_ERR_INVALID, "fused shading: svgir_shade_backward rejected its parameters");
+        stage_mark(tm, "shade_bwd");
+        return 0;
+    }
+
+    int geom_backward() {
+        GeomBwdArgs ga;
+        ga.list = R > 0 ? blended : nullptr; ga.list_count = blended_n;
+        camera_args(ga, p);
+        ga.cov3D = p->cov3D_precomp ? p->cov3D_precomp : G.cov3D; ga.radii = radii; ga.clamped = G.clamped; ga.svgss = svgss;
+        ga.dL_dmean2D = g->dL_dmeans2D; ga.dL_dconic = g->dL_dconic; ga.dL_dcolor = g->dL_dcolors; ga.dL_dnormal = g->dL_dnormal;
+        ga.dL_ddepth = g->dL_ddepth;
+        ga.packed = (rows || generic) ? nullptr : ba.grad_rows; ga.S = p->S;
+        ga.dL_dopacity = g->dL_dopacity; ga.dL_dfeature = g->dL_dfeatures;
+        ga.dL_dmean3D = g->dL_dmeans3D; ga.dL_dcov3D = g->dL_dcov3D; ga.dL_dsh = g->dL_dsh; ga.dL_dscale = g->dL_dscales;
+        ga.dL_drot = g->dL_drotations; ga.dL_dviewmat = g->dL_dviewmat; ga.dL_dprojmat = g->dL_dprojmat; ga.dL_dcampos = g->dL_dcampos;
+        if (ga.scales && !ga.rotations) return fail(SVGIR_ERR_INVALID, "rotations missing");
+        launch_geom_bwd(ga, s);
+        stage_mark(tm, "geom_bwd");
+        hipError_t e = p->debug ? hipStreamSynchronize(s) : hipSuccess;
+        if (e == hipSuccess) e = hipGetLastError();
+        return e != hipSuccess ? fail(SVGIR_ERR_HIP, "backward failed: %s", hipGetErrorString(e)) : 0;
+    }
+};
 
 int svgir_forward(const svgir_params* p, const svgir_outputs* o, svgir_alloc_fn geom, void* geom_ctx,
                   svgir_alloc_fn binning, void* binning_ctx, svgir_alloc_fn image, void* image_ctx, void* stream) {
-    ForwardCall c(p, o, geom, geom_ctx, binning, binning_ctx, image, image_ctx, stream, true);
-    const int rc = c.begin();
-    if (rc != 0) return rc < 0 ? rc : 0;
-    return c.finish();
+    return ForwardCall::run({p, o, geom, geom_ctx, binning, binning_ctx, image, image_ctx, stream, 0}, true);
 }
 
 // Several views in flight from ONE host thread: every view is begun (validated, allocated, all of its kernels launched on ITS stream)
@@ -908,10 +1052,9 @@ int svgir_forward_batch(svgir_view_call* views, int32_t count) {
     calls.reserve((size_t)count);
     int first_err = 0;
     for (int v = 0; v < count; v++) {
-        svgir_view_call& c = views[v];
-        calls.emplace_back(new ForwardCall(c.params, c.outputs, c.geom, c.geom_ctx, c.binning, c.binning_ctx, c.image, c.image_ctx, c.stream, true));
+        calls.emplace_back(new ForwardCall(views[v], true));
         const int rc = calls.back()->begin();
-        c.num_rendered = rc < 0 ? rc : 0;
+        views[v].num_rendered = rc < 0 ? rc : 0;
         if (rc < 0 && !first_err) first_err = rc;
     }
     const std::string begin_err = first_err ? g_err : std::string();
@@ -924,13 +1067,9 @@ int svgir_forward_batch(svgir_view_call* views, int32_t count) {
     if (!begin_err.empty()) g_err = begin_err;
     return first_err;
 }
-void svgir_reset_workload_history(int32_t scope) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    for (auto& e : g_cap)
-        if (e.used && (scope < 0 || e.key.scope == scope)) e = CapEntry{};
-}
+void svgir_reset_workload_history(int32_t scope) { g_history.reset(scope); }
 void svgir_speculation_stats(int64_t* out5) {
-    if (out5) for (int i = 0; i < 5; i++) out5[i] = (int64_t)g_spec_stats[i].load();
+    if (out5) g_history.stats(out5);
 }
 
 size_t svgir_backward_scratch_bytes(int32_t variant, int32_t P, size_t binning_bytes, int32_t W, int32_t H, int32_t S,
@@ -944,298 +1083,20 @@ size_t svgir_backward_scratch_bytes_for(int32_t variant, int32_t P, size_t binni
         return 256;   // run-time-width kernels accumulate straight into the dL_d* tensors: no scratch (a token size, never touched)
     if (variant != SVGIR_SVGSS || VS == 0)   // one packed gradient row per Gaussian
         return align_up((size_t)(P > 0 ? P : 1) * grad_row_geom(S, 0).RS * 4);
-    const int T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-    // the binning blob's instance capacity: from its size (worst-case state slots) or, for a blob laid out for a slot capacity of the
-    // forward's choosing, from the view's entry; and one gradient row per (sub-tile, instance) pair that survived the cull of THIS
-    // view when its count is known, else four per instance
-    int cap = 0;
-    long long pairs = -1;
-    bool known = image_blob && view_lookup(image_blob, true, &cap, nullptr, &pairs, nullptr);
-    if (image_blob && (!known || pairs < 0)) {   // not in the host table (or its counts never arrived): the blob's own copy, blocking
-        ViewCounts vc;
-        if (hipDeviceSynchronize() == hipSuccess && view_from_blob(image_layout(const_cast<char*>(image_blob), W, H).counters, &vc)) {
-            known = true; cap = vc.cap_R; pairs = vc.pairs;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (!bin_bytes_compact(binning_bytes)) cap = binning_capacity_from_bytes(binning_bytes, T, seg_nstate(S, VS));
-    else if (!known) cap = binning_capacity((long long)(binning_bytes / 48));   // (no view given: an upper bound -- every instance owns 48 B of the blob)
-    const size_t rows = pairs >= 0 ? (size_t)std::min<long long>(pairs, (long long)4 * cap) : (size_t)4 * cap;
-    return grad_scratch_bytes(cap, rows > 0 ? rows : 1, S, VS);
+    // the binning blob's instance capacity (bin_capacity); and one gradient row per (sub-tile, instance) pair that survived the cull of
+    // THIS view when its count is known, else four per instance
+    ViewCounts vc;
+    if (!bin_capacity(binning_bytes, image_blob, W, H, seg_nstate(S, VS), Wait::kBlock, nullptr, &vc))
+        vc.cap_R = binning_capacity((long long)(binning_bytes / 48));   // (no view given: an upper bound -- every instance owns 48 B of the blob)
+    if (image_blob && vc.pairs < 0) (void)hipGetLastError();   // (neither the table nor the blob's own copy had the counts)
+    const size_t rows = vc.pairs >= 0 ? (size_t)std::min<long long>(vc.pairs, (long long)4 * vc.cap_R) : (size_t)4 * vc.cap_R;
+    return grad_scratch_bytes(vc.cap_R, rows > 0 ? rows : 1, S, VS);
 }
 
 int svgir_backward(const svgir_params* p, const svgir_grads* g, int32_t R, const int32_t* radii, char* geom_blob,
                    char* binning_blob, size_t binning_bytes, char* image_blob, char* scratch, size_t scratch_bytes,
                    void* stream) {
-    if (int rc = validate(p, false)) return rc;
-    if (p->P == 0) return 0;
-    if (!g || !radii || !geom_blob || !binning_blob || !image_blob)
-        return fail(SVGIR_ERR_INVALID, "grads / radii / blobs must be provided");
-    if (p->shade) {   // fused shading: everything its backward needs, checked BEFORE anything is launched (no half-written gradients on a bad call)
-        if (!g->dL_dbase_color || !g->dL_droughness || !g->dL_dshade_normals || (!g->dL_dradiance && !p->shade->sp.radiance_ratio) || !g->dL_denv ||
-            !g->env_grad_work)
-            return fail(SVGIR_ERR_INVALID, "fused shading: the gradient outputs of the shading inputs must be provided");
-        if (!render_specialised(p->S, p->VS, true)) return fail(SVGIR_ERR_INVALID, "fused shading without a specialised composite");
-        if (g->dL_dreduced && !p->shade->all_surfels) return fail(SVGIR_ERR_INVALID, "fused shading: dL_dreduced needs all_surfels");
-        if (!p->shade->all_surfels && !g->out_weights) return fail(SVGIR_ERR_INVALID, "fused shading: out_weights (the forward's) must be provided");
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int P = p->P, W = p->W, H = p->H;
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, T = gx * gy;
-    const bool svgss = p->variant == SVGIR_SVGSS;
-    const CfgRef cfg = cfg_ref(p);
-    const float focal_y = H / (2.0f * p->tan_fovy), focal_x = W / (2.0f * p->tan_fovx);
-    const GeomLayout G = geom_layout(geom_blob, P);
-    const ImageLayout I = image_layout(image_blob, W, H);
-    const int nstate = seg_nstate(p->S, svgss ? p->VS : 0);
-    int cap = 0;
-    long long cap_slots = -1;
-    if (bin_bytes_compact(binning_bytes)) {   // laid out by the forward for a state-slot capacity of its choosing: the view's entry knows
-        if (!view_lookup(image_blob, false, &cap, &cap_slots, nullptr, nullptr) || cap_slots < 0) {
-            // not in the host table (an old forward, or a binder that moved the saved buffer): the image blob carries its own copy
-            ViewCounts vc;
-            HIP_OK(hipStreamSynchronize(s));
-            if (!view_from_blob(I.counters, &vc) || vc.cap_slots < 0)
-                return fail(SVGIR_ERR_INVALID, "the binning blob (%zu bytes) has a compact layout, but the image blob does not describe it "
-                                               "(not the image blob of the same svgir_forward?)", binning_bytes);
-            cap = vc.cap_R; cap_slots = vc.cap_slots;
-        }
-    } else {
-        cap = binning_capacity_from_bytes(binning_bytes, T, nstate);
-    }
-    if (cap < R || bin_layout(nullptr, cap, T, nstate, cap_slots).bytes != binning_bytes)
-        return fail(SVGIR_ERR_INVALID, "binning blob of %zu bytes does not match any layout for R=%d", binning_bytes, R);
-    const BinLayout B = bin_layout(binning_blob, cap, T, nstate, cap_slots);
-    const int fin = tile_sort_plan(T).passes & 1;
-    StageTimer tm(s);
-
-    // The forward dumped its blend states into slots sized from the workload's previous views and never waited to learn whether this
-    // view fits (that wait stalls a host-bound training loop).  By now the view's slot total is in host memory: it enters the
-    // workload's history, and if it exceeds the capacity the states are dumped AGAIN, all of them, into a stream-ordered temporary -- a
-    // replay of the composite forward that writes nothing else (one extra forward composite on the rare view that outgrows its guess).
-    float* seg_state = B.seg_state;
-    void* redump = nullptr;
-    {
-        int dev_id = 0;
-        (void)hipGetDevice(&dev_id);
-        const CapKey ckey{dev_id, W, H, P, p->S, svgss ? p->VS : 0, p->variant, p->workload_scope};
-        note_view_slots(ckey, image_blob, 1, &s);
-        long long slots = -1;
-        bool seen = cap_slots >= 0 && R > 0 && view_lookup(image_blob, 1, nullptr, nullptr, nullptr, &slots, &s) && slots >= 0;
-        if (cap_slots >= 0 && R > 0 && !seen) {
-            // The slot total is not in host memory even after blocking on the stream (the table entry was recycled, or the blob came
-            // from elsewhere): read the blob's own copy.  The backward never runs on state slots it has not verified.
-            ViewCounts vc;
-            HIP_OK(hipStreamSynchronize(s));
-            if (!view_from_blob(I.counters, &vc))
-                return fail(SVGIR_ERR_INVALID, "the image blob does not carry this view's state-slot total (forward failed, or a foreign blob)");
-            slots = vc.slots; seen = true;
-        }
-        static const bool trace = getenv("SVGIR_TRACE_SPEC") != nullptr;
-        if (trace) fprintf(stderr, "[svgir] backward: R=%d capacity=%d state slots: capacity %lld, view %lld%s\n", R, cap, cap_slots, slots, (seen && slots > cap_slots) ? " -> re-dump" : "");
-        if (seen && slots > cap_slots) {
-            if (!render_specialised(p->S, svgss ? p->VS : 0, svgss)) return fail(SVGIR_ERR_INVALID, "state slots without a specialised composite");
-            HIP_OK(hipMallocAsync(&redump, align_up((size_t)slots * nstate * 64 * 4), s));
-            seg_state = (float*)redump;
-            g_spec_stats[2]++;
-            RenderArgs ra{};
-            ra.W = W; ra.H = H; ra.gx = gx; ra.gy = gy; ra.S = p->S; ra.VS = svgss ? p->VS : 0;
-            ra.ranges = I.ranges; ra.point_list = B.val[fin]; ra.rec = G.rec; ra.features = p->features; ra.vfeatures = p->vfeatures;
-            ra.bg = p->background; ra.cfg = cfg; ra.sub_list = B.sub_list; ra.sub_total = I.sub_total; ra.sub_order = I.sub_order;
-            ra.sub_pair_base = I.sub_pair_base; ra.sub_slot_base = I.sub_slot_base; ra.slot_cap = (uint32_t)std::min<long long>(slots, 0xffffffffll);
-            ra.sub_count = I.sub_count; ra.sub_ndump = I.sub_ndump; ra.seg_block = I.seg_block; ra.seg_state = seg_state;
-            ra.dump_only = 1;
-            ra.hi_fill = 0;
-            ra.order_n = (int)order_entries(gx, gy);
-            if (launch_render_fwd(ra, svgss, s) < 0) { (void)hipFreeAsync(redump, s); return fail(SVGIR_ERR_INVALID, "state re-dump: no specialised composite"); }
-            tm.mark("state_redump");
-        }
-    }
-    struct FreeAsync { void* p; hipStream_t s; ~FreeAsync() { if (p) (void)hipFreeAsync(p, s); } } free_redump{redump, s};
-
-    RenderBwdArgs ba;
-    ba.W = W; ba.H = H; ba.gx = gx; ba.gy = gy; ba.S = p->S; ba.VS = svgss ? p->VS : 0;
-    ba.ranges = I.ranges; ba.point_list = B.val[fin]; ba.rec = G.rec; ba.features = p->features; ba.vfeatures = p->vfeatures;
-    ba.bg = p->background;
-    ba.cfg = cfg; ba.sub_list = B.sub_list; ba.sub_count = I.sub_count;
-    ba.sub_ndump = I.sub_ndump; ba.seg_list = B.seg_list; ba.seg_desc = B.seg_desc; ba.seg_count = I.counters; ba.seg_state = seg_state;
-    ba.seg_cap = (int)B.seg_cap;
-    ba.backward_geometry = p->backward_geometry;
-    ba.final_T = I.final_T; ba.final_D = I.final_D; ba.n_contrib = I.n_contrib;
-    ba.g_color = g->dL_dout_color; ba.g_normal = g->dL_dout_normal; ba.g_depth = g->dL_dout_depth;
-    ba.g_opacity = g->dL_dout_opacity; ba.g_feature = g->dL_dout_feature; ba.g_vfeature = g->dL_dout_vfeature;
-    ba.dL_dmean2D = g->dL_dmeans2D; ba.dL_dconic = g->dL_dconic; ba.dL_dopacity = g->dL_dopacity; ba.dL_dcolor = g->dL_dcolors;
-    ba.dL_dfeature = g->dL_dfeatures; ba.dL_dvfeature = g->dL_dvfeatures; ba.dL_dnormal = g->dL_dnormal; ba.dL_ddepth = g->dL_ddepth;
-    // Composite gradients go through the scratch: svgss (VS > 0) -> one row per (instance, sub-tile) pair, summed per
-    // Gaussian by grad_reduce (no atomics, deterministic); otherwise one packed row per Gaussian accumulated with float
-    // atomics and unpacked by geom_bwd.
-    const bool generic = !render_specialised(p->S, ba.VS, svgss);   // run-time-width kernels: atomics on the dL_d* tensors
-    // (svgss rows: sized for the pair count of this view when the forward's read-back of it is at hand, else for the worst case)
-    const size_t need = svgir_backward_scratch_bytes_for(p->variant, P, binning_bytes, image_blob, W, H, p->S, ba.VS);
-    if (!generic && (!scratch || scratch_bytes < need))
-        return fail(SVGIR_ERR_INVALID, "backward scratch of %zu bytes is smaller than svgir_backward_scratch_bytes_for() = %zu",
-                    scratch ? scratch_bytes : (size_t)0, need);
-    const bool rows = ba.VS > 0 && !generic;
-    // Clears:
-    //   1. the backward scratch (gradient-row validity bytes / packed rows), needed by the composite backward: it rides on the launch
-    //      that builds the list of live segments (one kernel in front of the composite instead of a memset + that kernel);
-    //   2. the dL_d* outputs, which start from zero (the kernels write the visible Gaussians only): the specialised composite
-    //      backward does not touch them (it accumulates in the scratch), so this clear runs on a side stream next to it and is joined
-    //      before the per-Gaussian kernels; the run-time-width composite adds into them, so there the clear comes first, on the
-    //      caller's stream.
-    // (scope guard: every exit path -- including the error returns below -- joins the side stream with the caller's stream and
-    // releases the event)
-    struct ClearJoin {
-        hipStream_t s; hipEvent_t ev = nullptr;
-        void join() {
-            if (ev) { (void)hipStreamWaitEvent(s, ev, 0); (void)hipEventDestroy(ev); ev = nullptr; }
-        }
-        ~ClearJoin() { join(); }
-    } cleared{s};
-    // (one allocation behind all gradient tensors, 16-byte granular, and a specialised composite about to run: its waves clear it)
-    const bool clear_in_kernel = !generic && R > 0 && g->clear_base && g->clear_bytes && (((uintptr_t)g->clear_base | g->clear_bytes) & 15) == 0;
-    ba.clear = clear_in_kernel ? (uint4*)g->clear_base : nullptr;
-    ba.clear_n16 = clear_in_kernel ? g->clear_bytes / 16 : 0;
-    if (!clear_in_kernel) {
-        hipStream_t cs = generic ? s : side_stream(s);
-        if (!cs) cs = s;
-        hipEvent_t ev_fork = nullptr;
-        if (cs != s) {   // the tensors may have been used on `s` before (stream-ordered allocators): order the clear after that
-            HIP_OK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-            HIP_OK(hipEventRecord(ev_fork, s));
-            HIP_OK(hipStreamWaitEvent(cs, ev_fork, 0));
-            (void)hipEventDestroy(ev_fork);
-        }
-        const size_t Pz = (size_t)P * 4;
-        if (g->clear_base && g->clear_bytes) {
-            HIP_OK(hipMemsetAsync(g->clear_base, 0, g->clear_bytes, cs));
-        } else {
-            struct { float* p; size_t n; } t[] = {
-                {g->dL_dmeans2D, 3 * Pz}, {g->dL_dconic, 4 * Pz}, {g->dL_dopacity, Pz}, {g->dL_dcolors, 3 * Pz},
-                {g->dL_dfeatures, (size_t)p->S * Pz}, {g->dL_dvfeatures, (size_t)ba.VS * Pz}, {g->dL_dnormal, 3 * Pz},
-                {g->dL_ddepth, Pz}, {g->dL_dmeans3D, 3 * Pz}, {g->dL_dcov3D, 6 * Pz}, {g->dL_dsh, (size_t)p->M * 3 * Pz},
-                {g->dL_dscales, 3 * Pz}, {g->dL_drotations, 4 * Pz}, {svgss ? g->dL_dviewmat : nullptr, 64},
-                {svgss ? g->dL_dprojmat : nullptr, 64}, {svgss ? g->dL_dcampos : nullptr, 12}};
-            for (auto& e : t)
-                if (e.p && e.n) HIP_OK(hipMemsetAsync(e.p, 0, e.n, cs));
-        }
-        if (cs != s) {
-            HIP_OK(hipEventCreateWithFlags(&cleared.ev, hipEventDisableTiming));
-            HIP_OK(hipEventRecord(cleared.ev, cs));
-        }
-    }
-    const GradRowGeom rg = grad_row_geom(p->S, ba.VS);
-    ba.grad_rows = generic ? nullptr : (float*)scratch;
-    ba.row_of = nullptr; ba.rows_cap = 0;
-    void* sc_clear = nullptr;
-    size_t sc_bytes = 0;
-    if (!generic) {
-        if (rows) {   // reverse map (cleared) | compact rows
-            ba.row_of = (uint32_t*)scratch;
-            ba.grad_rows = (float*)(scratch + grad_rowof_bytes(cap));
-            ba.rows_cap = (uint32_t)std::min<size_t>((scratch_bytes - grad_rowof_bytes(cap)) / ((size_t)rg.RS * 4), 0xfffffff0u);
-            sc_clear = ba.row_of; sc_bytes = grad_rowof_bytes(cap);
-        } else {
-            sc_clear = ba.grad_rows; sc_bytes = align_up((size_t)P * rg.RS * 4);
-        }
-    }
-    ShadeTables shade_tabs;   // (env == nullptr: the shading backward launches its own prologue)
-    bool use_list = false;
-    if (R > 0) {
-        // live backward segments, longest first (common.hpp SEG), from the forward's per-sub-tile counts: built here -- a forward-only
-        // call never pays for it -- together with the scratch clear
-        RenderArgs sa{};
-        sa.W = W; sa.H = H; sa.gx = gx; sa.gy = gy; sa.S = p->S; sa.VS = ba.VS;
-        sa.ranges = I.ranges; sa.sub_count = I.sub_count; sa.sub_ndump = I.sub_ndump; sa.seg_list = B.seg_list; sa.seg_desc = B.seg_desc;
-        sa.seg_count = I.counters; sa.seg_block = I.seg_block; sa.sub_pair_base = I.sub_pair_base; sa.sub_slot_base = I.sub_slot_base;
-        // (fused shading: the same launch builds the tables and zeroes the env-gradient accumulator of the shading backward below)
-        if (p->shade && g->env_grad_work) shade_tabs = shade_tables(&p->shade->sp, g->env_grad_work, p->shade->sp.env_h * p->shade->sp.env_w * 3);
-        // (and counts, per chunk, the surfels that received a blend weight: the first half of the partition the per-Gaussian kernels walk)
-        use_list = g->out_weights && !generic && (p->shade || P >= (rows ? kListMinPRows : kListMinP));
-        launch_seg_build(sa, sc_clear, sc_bytes, shade_tabs, use_list ? g->out_weights : nullptr, P, G.shade_work, s);
-    } else if (sc_clear && !rows) {
-        HIP_OK(hipMemsetAsync(sc_clear, 0, sc_bytes, s));   // (nothing rendered: geom_bwd still unpacks the -- zero -- packed rows)
-    }
-    tm.mark("seg_build");
-    // The surfels that received a blend weight (the forward's out_weights > 0): only they own gradient rows, only their per-Gaussian
-    // gradients are non-zero, only their shading is differentiated.  With the weights at hand the per-Gaussian kernels behind the
-    // composite walk that list (13-29 % of the model on the BASELINE scenes) instead of all P.
-    const uint32_t* blended = nullptr; const uint32_t* blended_n = nullptr;
-    if (use_list && R > 0) {
-        uint32_t* cnt = G.shade_work + partition_work_words(P) - 1;
-        launch_partition_scatter(P, g->out_weights, G.shade_list, G.shade_work, cnt, s);
-        blended = G.shade_list; blended_n = cnt;
-    }
-    if (R > 0) {
-        if (generic) launch_render_bwd_generic(ba, svgss, s);
-        else (void)launch_render_bwd(ba, svgss, s);
-    }
-    tm.mark("render_bwd");
-    cleared.join();
-    if (R > 0 && rows) {
-        GradReduceArgs ra;
-        ra.list = blended; ra.list_count = blended_n;
-        ra.P = P; ra.S = p->S; ra.VS = ba.VS; ra.radii = radii; ra.tiles = G.tiles; ra.rec = G.rec;
-        ra.grad_rows = ba.grad_rows; ra.row_of = ba.row_of;
-        ra.dL_dmean2D = g->dL_dmeans2D; ra.dL_dconic = g->dL_dconic; ra.dL_dopacity = g->dL_dopacity; ra.dL_dcolor = g->dL_dcolors;
-        ra.dL_dfeature = g->dL_dfeatures; ra.dL_dvfeature = g->dL_dvfeatures; ra.dL_dnormal = g->dL_dnormal; ra.dL_ddepth = g->dL_ddepth;
-        launch_grad_reduce(ra, s);
-        tm.mark("grad_reduce");
-    }
-    if (p->shade) {
-        // dL_dfeatures / dL_dvfeatures are complete: the shading's backward, for the surfels that received a blend weight (the rows of all
-        // others are exactly zero: no pixel blended them)
-        const bool all = p->shade->all_surfels != 0;   // (the arguments were validated before the first launch)
-        svgir_shade_params sp = p->shade->sp;
-        sp.subset = nullptr; sp.subset_count = nullptr;
-        if (!all) {
-            if (!blended) {   // (R == 0: nothing was blended -- the partition of all-zero weights zero-fills every row)
-                uint32_t* cnt = G.shade_work + partition_work_words(P) - 1;
-                launch_partition(P, nullptr, g->out_weights, G.shade_list, G.shade_work, cnt, s);
-                blended = G.shade_list; blended_n = cnt;
-            }
-            sp.subset = blended; sp.subset_count = blended_n;
-        }
-        // (a binder that lays the four per-surfel gradient tensors out inside clear_base gets their zero rows from the composite
-        // backward's clearing sweep -- stores nobody waits for -- instead of a zero-fill launch in front of the shading backward)
-        auto in_clear = [&](const float* t, size_t floats) {
-            const char* b = (const char*)g->clear_base, *q = (const char*)t;
-            return clear_in_kernel && q >= b && q + floats * 4 <= b + g->clear_bytes;
-        };
-        const size_t Pz = (size_t)P;
-        const bool precleared = in_clear(g->dL_dbase_color, 12 * Pz) && in_clear(g->dL_droughness, 4 * Pz) &&
-                                in_clear(g->dL_dshade_normals, 12 * Pz) &&
-                                (!g->dL_dradiance || in_clear(g->dL_dradiance, 3 * Pz * (size_t)sp.Ns));
-        if (shade_backward_impl(&sp, g->dL_dreduced, g->dL_dfeatures, g->dL_dvfeatures, g->dL_dbase_color, g->dL_droughness,
-                                g->dL_dshade_normals, g->dL_dradiance, g->dL_denv, g->env_grad_work, g->dL_dradiance_ratio, precleared,
-                                shade_tabs.env != nullptr, s) != 0)
-            return fail(SVGIR_ERR_INVALID, "fused shading: svgir_shade_backward rejected its parameters");
-        tm.mark("shade_bwd");
-    }
-
-    GeomBwdArgs ga;
-    ga.list = R > 0 ? blended : nullptr; ga.list_count = blended_n;
-    ga.P = P; ga.D = p->D; ga.M = p->M;
-    ga.means3D = p->means3D; ga.shs = p->colors_precomp ? nullptr : p->shs; ga.scales = p->scales; ga.rotations = p->rotations;
-    ga.cov3D = p->cov3D_precomp ? p->cov3D_precomp : G.cov3D; ga.view = p->viewmatrix; ga.proj = p->projmatrix; ga.campos = p->cam_pos;
-    ga.radii = radii; ga.clamped = G.clamped;
-    ga.scale_modifier = p->scale_modifier; ga.tanx = p->tan_fovx; ga.tany = p->tan_fovy; ga.focal_x = focal_x; ga.focal_y = focal_y;
-    ga.cfg = cfg; ga.svgss = svgss;
-    ga.dL_dmean2D = g->dL_dmeans2D; ga.dL_dconic = g->dL_dconic; ga.dL_dcolor = g->dL_dcolors; ga.dL_dnormal = g->dL_dnormal;
-    ga.dL_ddepth = g->dL_ddepth;
-    ga.packed = (rows || generic) ? nullptr : ba.grad_rows; ga.S = p->S;
-    ga.dL_dopacity = g->dL_dopacity; ga.dL_dfeature = g->dL_dfeatures;
-    ga.dL_dmean3D = g->dL_dmeans3D; ga.dL_dcov3D = g->dL_dcov3D; ga.dL_dsh = g->dL_dsh; ga.dL_dscale = g->dL_dscales;
-    ga.dL_drot = g->dL_drotations; ga.dL_dviewmat = g->dL_dviewmat; ga.dL_dprojmat = g->dL_dprojmat; ga.dL_dcampos = g->dL_dcampos;
-    if (ga.scales && !ga.rotations) return fail(SVGIR_ERR_INVALID, "rotations missing");
-
-    launch_geom_bwd(ga, s);
-    tm.mark("geom_bwd");
-    hipError_t e = p->debug ? hipStreamSynchronize(s) : hipSuccess;
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return fail(SVGIR_ERR_HIP, "backward failed: %s", hipGetErrorString(e));
-    return 0;
+    return BackwardCall{p, g, R, radii, geom_blob, binning_blob, binning_bytes, image_blob, scratch, scratch_bytes, (hipStream_t)stream}.run();
 }
 
 int svgir_mark_visible(int32_t variant, int32_t P, const float* means3D, const float* viewmatrix,
