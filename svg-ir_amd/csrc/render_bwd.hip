@@ -396,13 +396,15 @@ render_bwd_kernel(const RenderBwdArgs a) {
                 // w (value 4 + (l & 1)); two row shifts put every 16-lane row's sums into its lanes 12..15; w moves to lanes 8..11; the four
                 // rows meet in rows_total.  Lanes 12..15 then hold the totals of g0..g3, lanes 8, 9 those of g4, g5.
                 {
-                    const float dL_ddist = dLa * (B.y * -0.5f) * Gs;
+                    // Gs is inf / NaN where power > ~88.7 (an indefinite conic): select it before it meets dLa = 0, or 0 * inf poisons the row
+                    const float Gp = pre ? Gs : 0.f;
+                    const float dL_ddist = dLa * (B.y * -0.5f) * Gp;
                     float g0 = dL_ddist * 2.f * (A.z * dx + A.w * dy) * ddelx_dx;
                     float g1 = dL_ddist * 2.f * (B.x * dy + A.w * dx) * ddely_dy;
                     if (sp) { g0 += q5g * B.w; g1 += q5g * E.x; }   // + Q5, d(depth offset)/d(mean2D) = (DA, DB)
                     g0 = pre ? g0 : 0.f; g1 = pre ? g1 : 0.f;
                     const float g2 = dL_ddist * (dx * dx), g3 = dL_ddist * (dx * dy), g4 = dL_ddist * (dy * dy);   // (dL_ddist = 0 where !pre)
-                    const float g5 = Gs * dLa;
+                    const float g5 = Gp * dLa;
                     const bool o1 = (lane & 1) != 0, o2 = (lane & 2) != 0;
                     const float t01 = (o1 ? g1 : g0) + dpp_f32<0xB1>(o1 ? g0 : g1);   // quad_perm [1,0,3,2]
                     const float t23 = (o1 ? g3 : g2) + dpp_f32<0xB1>(o1 ? g2 : g3);

@@ -31,7 +31,7 @@ def settings(sc, variant, debug=False):
         computer_pseudo_normal=bool(sc.get("computer_pseudo_normal", False)), debug=debug)
 
 
-LEAVES = ("means3D", "shs", "opacities", "scales", "rotations", "features", "vfeatures")
+LEAVES = ("means3D", "shs", "opacities", "scales", "rotations", "cov3D_precomp", "features", "vfeatures")
 
 
 def render(sc, variant, requires_grad=False, debug=False):
@@ -50,7 +50,8 @@ def render(sc, variant, requires_grad=False, debug=False):
     leaves["means2D"] = means2D
     rast = GaussianRasterizer(settings(sc, variant, debug))
     kw = dict(means3D=leaves["means3D"], means2D=means2D, opacities=leaves["opacities"], shs=leaves["shs"],
-              scales=leaves["scales"], rotations=leaves["rotations"], features=leaves["features"])
+              scales=leaves.get("scales"), rotations=leaves.get("rotations"), cov3D_precomp=leaves.get("cov3D_precomp"),
+              features=leaves["features"])
     if variant == "svgss":
         kw["vfeatures"] = leaves["vfeatures"]
         (R, color, normal, opacity, depth, feature, vfeature, weights, radii) = rast(**kw)
@@ -89,7 +90,8 @@ def forward_raw(sc, variant):
         from gaussian_renderer.svgss_rasterization import _C
         VS = sc["vfeatures"].shape[1]
         out = _C.rasterize_gaussians(st.bg, sc["means3D"], sc["features"], sc["vfeatures"], empty, sc["opacities"],
-                                     sc["scales"], sc["rotations"], st.scale_modifier, empty, st.viewmatrix,
+                                     sc.get("scales", empty), sc.get("rotations", empty), st.scale_modifier,
+                                     sc.get("cov3D_precomp", empty), st.viewmatrix,
                                      st.projmatrix, st.prcppoint, st.patch_bbox, st.tanfovx, st.tanfovy,
                                      st.image_height, st.image_width, sc["shs"], st.sh_degree, st.campos, False, False,
                                      st.config)
@@ -99,8 +101,9 @@ def forward_raw(sc, variant):
     else:
         from gaussian_renderer.rgss_rasterization import _C
         VS = 0
-        out = _C.rasterize_gaussians(st.bg, sc["means3D"], sc["features"], empty, sc["opacities"], sc["scales"],
-                                     sc["rotations"], st.scale_modifier, empty, st.viewmatrix, st.projmatrix,
+        out = _C.rasterize_gaussians(st.bg, sc["means3D"], sc["features"], empty, sc["opacities"], sc.get("scales", empty),
+                                     sc.get("rotations", empty), st.scale_modifier, sc.get("cov3D_precomp", empty), st.viewmatrix,
+                                     st.projmatrix,
                                      st.tanfovx, st.tanfovy, st.cx, st.cy, st.image_height, st.image_width, sc["shs"],
                                      st.sh_degree, st.campos, False, False, False)
         (R, ncontrib, color, normal, opac, depth, feat, pn, sx, weights, radii, gb, bb, ib) = out
