@@ -119,16 +119,39 @@ def _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs
     return p, keep, dev, P, Ns, env_h, env_w
 
 
-def _radiance_grads(ctx, i_rad, i_ratio, rad, ratio, env_h, env_w, dev):
-    """(dL_dradiance or None, dL_dradiance_ratio or None, env-gradient scratch) of a shading backward.  Without a ratio the library
-    always writes dL_dradiance; with one the cache is usually detached (the reference's get_radiances) and only the scalar's gradient
-    is produced -- no [P, Ns, 3] tensor at all."""
+def _radiance_grads(ctx, i_rad, i_ratio, ratio, env_h, env_w, dev):
+    """(whether dL_dradiance is produced, dL_dradiance_ratio or None, env-gradient scratch) of a shading backward.  Without a ratio the
+    library always writes dL_dradiance; with one the cache is usually detached (the reference's get_radiances) and only the scalar's
+    gradient is produced -- no [P, Ns, 3] tensor at all."""
     want_ratio = ratio is not None and ctx.needs_input_grad[i_ratio]
     want_rad = ratio is None or ctx.needs_input_grad[i_rad]
-    d_rad = torch.empty_like(rad) if want_rad else None
-    d_ratio = torch.empty(1, dtype=torch.float32, device=dev) if want_ratio else None
+    d_ratio = N.out_tensor((1,), torch.float32, dev) if want_ratio else None
     gwork = torch.empty(env_h * env_w * 3 + (RATIO_WORK if want_ratio else 0), dtype=torch.float32, device=dev)
-    return d_rad, d_ratio, gwork
+    return want_rad, d_ratio, gwork
+
+
+def _shade_backward(ctx, i_ratio, inputs, lat, softplus, scale, g_red, g_feat=None, g_vfeat=None, **kw):
+    """The backward of _Shade / _ShadePack: ONE svgir_shade_backward.  `inputs`: the saved (base_color, roughness, normals, viewdirs,
+    radiance, visibility, dirs, areas, env, ratio); returns the gradients of (base_color, roughness, normals, radiance, env, ratio),
+    shaped like them, None where none is produced."""
+    base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, ratio = inputs
+    p, keep, dev, P, Ns, env_h, env_w = _params(base_color, roughness, normals, viewdirs, radiance, visibility,
+                                                lat if lat is not None else dirs, areas, env, softplus, scale, ratio=ratio, **kw)
+    gr, gf, gv = (N.f32c(t, dev) for t in (g_red, g_feat, g_vfeat))
+    d_base, d_rough, d_norm, d_env = (torch.empty_like(keep[i]) for i in (0, 1, 2, 8))  # all overwritten
+    want_rad, d_ratio, gwork = _radiance_grads(ctx, 4, i_ratio, ratio, env_h, env_w, dev)
+    d_rad = torch.empty_like(keep[4]) if want_rad else None
+    if P:
+        N.check(N.lib.svgir_shade_backward(p, N.ptr(gr), N.ptr(gf), N.ptr(gv), d_base.data_ptr(), d_rough.data_ptr(),
+                                           d_norm.data_ptr(), N.ptr(d_rad), d_env.data_ptr(), gwork.data_ptr(), N.ptr(d_ratio),
+                                           N.stream_ptr(dev)), "shade_backward")
+    else:
+        d_env.zero_()
+        if d_ratio is not None:
+            d_ratio.zero_()
+    return (d_base.reshape(base_color.shape), d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape),
+            None if d_rad is None else d_rad.reshape(radiance.shape), d_env.reshape(env.shape),
+            None if d_ratio is None else d_ratio.reshape(ratio.shape))
 
 
 class _Shade(torch.autograd.Function):
@@ -150,25 +173,10 @@ class _Shade(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_reduced):
-        base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, ratio = ctx.saved_tensors
         softplus, scale, env_transform, lat = ctx.cfg
-        p, keep, dev, P, Ns, env_h, env_w = _params(base_color, roughness, normals, viewdirs, radiance, visibility,
-                                                    lat if lat is not None else dirs, areas, env, softplus, scale,
-                                                    env_transform=env_transform, ratio=ratio)
-        g = N.f32c(g_reduced, dev)
-        d_base, d_rough, d_norm, d_env = (torch.empty_like(keep[i]) for i in (0, 1, 2, 8))  # all overwritten
-        d_rad, d_ratio, gwork = _radiance_grads(ctx, 4, 12, keep[4], ratio, env_h, env_w, dev)
-        if P:
-            N.check(N.lib.svgir_shade_backward(p, g.data_ptr(), None, None, d_base.data_ptr(), d_rough.data_ptr(), d_norm.data_ptr(),
-                                               N.ptr(d_rad), d_env.data_ptr(), gwork.data_ptr(), N.ptr(d_ratio), N.stream_ptr(dev)),
-                    "shade_backward")
-        else:
-            d_env.zero_()
-            if d_ratio is not None:
-                d_ratio.zero_()
-        return (d_base.reshape(base_color.shape), d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape), None,
-                None if d_rad is None else d_rad.reshape(radiance.shape), None, None, None, d_env.reshape(env.shape), None, None, None,
-                None if d_ratio is None else d_ratio.reshape(ratio.shape))
+        d_base, d_rough, d_norm, d_rad, d_env, d_ratio = _shade_backward(ctx, 12, ctx.saved_tensors, lat, softplus, scale, g_reduced,
+                                                                         env_transform=env_transform)
+        return (d_base, d_rough, d_norm, None, d_rad, None, None, None, d_env, None, None, None, d_ratio)
 
 
 class _ShadePack(torch.autograd.Function):
@@ -197,27 +205,14 @@ class _ShadePack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_feat, g_vfeat, g_red):
-        base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, viewmatrix, ratio = ctx.saved_tensors
+        *inputs, viewmatrix, ratio = ctx.saved_tensors
         softplus, scale, training, env_transform, lat = ctx.cfg
-        p, keep, dev, P, Ns, env_h, env_w = _params(base_color, roughness, normals, viewdirs, radiance, visibility,
-                                                    lat if lat is not None else dirs, areas, env, softplus, scale,
-                                                    viewmatrix=viewmatrix, training=training, env_transform=env_transform, ratio=ratio)
         if g_feat is None and g_vfeat is None and g_red is None:
             return (None,) * 15
-        gf, gv, gr = (N.f32c(t, dev) for t in (g_feat, g_vfeat, g_red))
-        d_base, d_rough, d_norm, d_env = (torch.empty_like(keep[i]) for i in (0, 1, 2, 8))
-        d_rad, d_ratio, gwork = _radiance_grads(ctx, 4, 14, keep[4], ratio, env_h, env_w, dev)
-        if P:
-            N.check(N.lib.svgir_shade_backward(p, N.ptr(gr), N.ptr(gf), N.ptr(gv), d_base.data_ptr(), d_rough.data_ptr(),
-                                               d_norm.data_ptr(), N.ptr(d_rad), d_env.data_ptr(), gwork.data_ptr(), N.ptr(d_ratio),
-                                               N.stream_ptr(dev)), "shade_backward")
-        else:
-            d_env.zero_()
-            if d_ratio is not None:
-                d_ratio.zero_()
-        return (d_base.reshape(base_color.shape), d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape), None,
-                None if d_rad is None else d_rad.reshape(radiance.shape), None, None, None, d_env.reshape(env.shape), None, None, None,
-                None, None, None if d_ratio is None else d_ratio.reshape(ratio.shape))
+        d_base, d_rough, d_norm, d_rad, d_env, d_ratio = _shade_backward(
+            ctx, 14, (*inputs, ratio), lat, softplus, scale, g_red, g_feat, g_vfeat, viewmatrix=viewmatrix, training=training,
+            env_transform=env_transform)
+        return (d_base, d_rough, d_norm, None, d_rad, None, None, None, d_env, None, None, None, None, None, d_ratio)
 
 
 def _env_of(light):
@@ -294,7 +289,7 @@ class _ShadedRasterize(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, opacities, scales, rotations, base_color, roughness, normals, viewdirs, radiance,
                 visibility, dirs, areas, env, raster_settings, softplus, scale, training, env_transform, all_surfels, want_reduced,
                 ratio=None):
-        from .svgss_rasterization import _C
+        from .svgss_rasterization import _C, forward_args
         st = raster_settings
         sp, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env,
                                              softplus, scale, viewmatrix=st.viewmatrix, training=training,
@@ -306,9 +301,8 @@ class _ShadedRasterize(torch.autograd.Function):
         red = N.out_tensor((P, NRED), torch.float32, dev) if want_reduced else None
         fs = _fused_struct(sp, red, all_surfels)
         empty = torch.empty(0, dtype=torch.float32, device=dev)
-        out = _C.rasterize_gaussians(st.bg, means3D, feats, vfeats, empty, opacities, scales, rotations, st.scale_modifier, empty,
-                                     st.viewmatrix, st.projmatrix, st.prcppoint, st.patch_bbox, st.tanfovx, st.tanfovy,
-                                     st.image_height, st.image_width, sh, st.sh_degree, st.campos, st.prefiltered, st.debug, st.config,
+        out = _C.rasterize_gaussians(*forward_args(st, means3D, feats, vfeats, sh, empty, opacities, scales, rotations, empty,
+                                                   st.viewmatrix, st.projmatrix, st.campos),
                                      shade=fs, forward_only=not any(ctx.needs_input_grad))
         (R, color, normal, depth, opacity, feature, vfeature, weights, radii, gb, bb, ib) = out
         lat = dirs if isinstance(dirs, FibonacciLattice) else None
@@ -323,34 +317,25 @@ class _ShadedRasterize(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _gR, g_color, g_normal, g_opacity, g_depth, g_feature, g_vfeature, _gw, _gr, g_red):
-        from .svgss_rasterization import _C
+        from .svgss_rasterization import _C, backward_args
         (means3D, sh, scales, rotations, base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, feats,
          vfeats, weights, radii, gb, bb, ib, ratio) = ctx.saved_tensors
         st, R, softplus, scale, training, env_transform, lat, all_surfels = ctx.cfg
         dev = means3D.device
-        H, W = st.image_height, st.image_width
         sp, keep, _, P, Ns, env_h, env_w = _params(base_color, roughness, normals, viewdirs, radiance, visibility,
                                                    lat if lat is not None else dirs, areas, env, softplus, scale,
                                                    viewmatrix=st.viewmatrix, training=training, env_transform=env_transform, ratio=ratio)
         if g_red is not None and not all_surfels:
             raise RuntimeError("render_shaded: a loss on `reduced` needs all_surfels=True (rows of unshaded surfels are zero)")
-        def _g(g, ch):  # autograd hands None for outputs that did not take part in the loss: an empty tensor = all zero for the library
-            return g if g is not None else torch.empty(0, dtype=torch.float32, device=dev)
-
         empty = torch.empty(0, dtype=torch.float32, device=dev)
-        args = (st.bg, means3D, feats, vfeats, radii, empty, scales, rotations, st.scale_modifier, empty, st.viewmatrix, st.projmatrix,
-                st.prcppoint, st.patch_bbox, st.tanfovx, st.tanfovy, _g(g_color, 3), _g(g_normal, 3), _g(g_depth, 1), _g(g_opacity, 1),
-                _g(g_feature, feats.shape[1]), _g(g_vfeature, vfeats.shape[1] // 4), sh, st.sh_degree, st.campos, gb, R, bb, ib,
-                st.debug, st.config)
+        args = backward_args(st, means3D, feats, vfeats, radii, empty, scales, rotations, empty, sh, R, gb, bb, ib, g_color, g_normal,
+                             g_opacity, g_depth, g_feature, g_vfeature)
         if not any(ctx.needs_input_grad[i] for i in (6, 7, 8, 10, 14, 22)):   # frozen materials (evaluation): the rasterizer's backward alone
             res = _C.rasterize_gaussians_backward(*args)
             return (res[3], res[0], res[7], res[2], res[8], res[9]) + (None,) * 17
         fs = _fused_struct(sp, None, all_surfels)
         d_env = N.out_tensor(keep[8].shape, torch.float32, dev)
-        want_ratio = ratio is not None and ctx.needs_input_grad[22]
-        want_rad = ratio is None or ctx.needs_input_grad[10]   # (with a ratio the cache is normally detached: no [P, Ns, 3] gradient)
-        d_ratio = N.out_tensor((1,), torch.float32, dev) if want_ratio else None
-        gwork = torch.empty(env_h * env_w * 3 + (RATIO_WORK if want_ratio else 0), dtype=torch.float32, device=dev)
+        want_rad, d_ratio, gwork = _radiance_grads(ctx, 10, 22, ratio, env_h, env_w, dev)
         # (the four per-surfel gradient tensors are carved out of the rasterizer's gradient allocation by the binding: the composite
         # backward clears that region in passing, the shading backward then writes the rows of the surfels that were blended.  Measured
         # at cfg3_train: +28 us in render_bwd / grad_reduce for the 160 MB; a zero-fill launch costs 37 us, zero-fill stores from the
@@ -359,11 +344,11 @@ class _ShadedRasterize(torch.autograd.Function):
                   _shapes=dict(dL_dbase_color=keep[0].shape, dL_droughness=keep[1].shape, dL_dshade_normals=keep[2].shape))
         if want_rad:
             sg["_shapes"]["dL_dradiance"] = keep[4].shape
-        if want_ratio:
+        if d_ratio is not None:
             sg["dL_dradiance_ratio"] = d_ratio
         if P == 0:
             d_env.zero_()
-            if want_ratio:
+            if d_ratio is not None:
                 d_ratio.zero_()
         res = _C.rasterize_gaussians_backward(*args, shade=fs, shade_grads=sg, scratch_feature_grads=not all_surfels)
         d_base, d_rough, d_norm, d_rad = sg["dL_dbase_color"], sg["dL_droughness"], sg["dL_dshade_normals"], sg.get("dL_dradiance")

@@ -8,21 +8,23 @@ Same public names, argument order, return tuples and gradient tuples as
     opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos, None) (:293-308)
   * `_C` with rasterize_gaussians / rasterize_gaussians_backward / mark_visible in the pybind argument order of
     svgss_rasterization/rasterize_points.h:18-82 (24 args -> 12-tuple, 31 args -> 13-tuple).
-The compute runs in libsvgir_raster.so (hand-written HIP for gfx950) through the C ABI of include/svgir_raster.h.
+The compute runs in libsvgir_raster.so (hand-written HIP for gfx950) through the C ABI of include/svgir_raster.h; what this
+module shares with rgss_rasterization.py lives in _binding.py.
 """
 from typing import NamedTuple
 
 import ctypes as C
 
 import torch
-import torch.nn as nn
 
+from . import _binding as B
 from . import _native as N
+from ._binding import cpu_deep_copy_tuple  # noqa: F401  (a public name of the reference's module)
 
 
-def cpu_deep_copy_tuple(input_tuple):
-    copied_tensors = [item.cpu().clone() if isinstance(item, torch.Tensor) else item for item in input_tuple]
-    return tuple(copied_tensors)
+def _svgss_fields(prcppoint, patchbbox, config):
+    """The svgir_params fields only this variant sets, forward and backward (_binding.call_params)."""
+    return dict(prcppoint=prcppoint, patchbbox=patchbbox, config=config, config_len=config.numel() if config is not None else 0)
 
 
 class _CBinding:
@@ -36,10 +38,8 @@ class _CBinding:
 
     @staticmethod
     def rasterize_gaussians_batch(calls, device, streams):
-        """Extension: `calls` = [(args, kwargs)] of rasterize_gaussians, one view each, launched with ONE svgir_forward_batch --
-        view v on streams[v], all views in flight before the first instance count is awaited (one host thread).  Returns the
-        list of 12-tuples.  The caller orders `streams` against the producers / consumers of the tensors."""
-        return N.run_forward_batch([(lambda a=a, k=k: _CBinding._forward_steps(*a, **k)) for a, k in calls], device, streams)
+        """Extension: one svgir_forward_batch for several views (_binding.rasterize_gaussians_batch); returns the list of 12-tuples."""
+        return B.rasterize_gaussians_batch(_CBinding._forward_steps, calls, device, streams)
 
     @staticmethod
     def _forward_steps(background, means3D, features, vfeatures, colors, opacity, scales, rotations,
@@ -52,62 +52,23 @@ class _CBinding:
         `shade` (extension, keyword only): a `_native.FusedShade` -- the library shades the surfels this view's composite reads
         and WRITES `features` / `vfeatures` (pass uninitialised [P,S] / [P,VS] buffers; gaussian_renderer/shading.py).
         `forward_only` (extension, keyword only): no backward will follow -- the composite keeps no blend states."""
-        if means3D.ndimension() != 2 or means3D.size(1) != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:65-67
-        dev = means3D.device
-        if dev.type != "cuda":
-            raise RuntimeError("svgss rasterizer: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
-        P = means3D.size(0)
-        S = features.size(1) if features.dim() == 2 else 0
-        VS = vfeatures.size(1) if vfeatures.dim() == 2 else 0
+        B.check_forward_inputs("svgss", means3D)  # rasterize_points.cu:65-67
+        dev, P, S, VS = means3D.device, means3D.size(0), B.width(features), B.width(vfeatures)
         H, W = int(image_height), int(image_width)
-        f32 = dict(dtype=torch.float32, device=dev)
-        if P == 0:  # nothing is launched: the reference returns its zero-initialised outputs (rasterize_points.cu:100)
-            torch_empty = torch.zeros
-        else:
-            def torch_empty(shape, **kw):  # every element is written by the library
-                return N.out_tensor(shape, kw["dtype"], kw["device"])
-        out_color = torch_empty((3, H, W), **f32)
-        out_normal = torch_empty((3, H, W), **f32)
-        out_depth = torch_empty((1, H, W), **f32)
-        out_opac = torch_empty((1, H, W), **f32)
-        out_feature = torch_empty((S, H, W), **f32)
-        out_vfeature = torch_empty((VS // 4, H, W), **f32)
-        out_weights = torch_empty((P, 1), **f32)
-        radii = torch_empty((P,), dtype=torch.int32, device=dev)
-        blobs = N.BlobAllocator(dev)
-        rendered = 0
-        if P != 0:
-            keep = [N.f32c(t, dev) for t in (background, means3D, sh, colors, features, vfeatures, opacity, scales,
-                                              rotations, cov3D_precomp, viewmatrix, projmatrix, campos, prcppoint,
-                                              patchbbox, config)]
-            (bg, m3, shc, col, fe, vf, op, sc, ro, cv, vm, pm, cp, pr, pb, cfg) = keep
-            p = N.new_params()
-            p.variant, p.P, p.S, p.VS, p.D, p.W, p.H = N.SVGSS, P, S, VS, int(degree), W, H
-            p.M = shc.size(1) if (shc is not None and shc.numel() != 0) else 0
-            p.background, p.means3D, p.shs, p.colors_precomp = N.ptr(bg), N.ptr(m3), N.ptr(shc), N.ptr(col)
-            p.features, p.vfeatures, p.opacities = N.ptr(fe), N.ptr(vf), N.ptr(op)
-            p.scales, p.rotations, p.cov3D_precomp = N.ptr(sc), N.ptr(ro), N.ptr(cv)
-            p.viewmatrix, p.projmatrix, p.cam_pos = N.ptr(vm), N.ptr(pm), N.ptr(cp)
-            p.prcppoint, p.patchbbox = N.ptr(pr), N.ptr(pb)
-            p.config, p.config_len = N.ptr(cfg), (cfg.numel() if cfg is not None else 0)
-            p.scale_modifier, p.tan_fovx, p.tan_fovy = float(scale_modifier), float(tan_fovx), float(tan_fovy)
-            p.cx, p.cy = W / 2.0, H / 2.0
-            p.prefiltered, p.debug = int(bool(prefiltered)), int(bool(debug))
-            o = N.Outputs()
-            o.out_color, o.out_normal, o.out_depth, o.out_opacity = (out_color.data_ptr(), out_normal.data_ptr(),
-                                                                     out_depth.data_ptr(), out_opac.data_ptr())
-            o.out_feature, o.out_vfeature = N.ptr(out_feature), N.ptr(out_vfeature)
-            o.out_weights, o.radii = out_weights.data_ptr(), radii.data_ptr()
-            if features_ready is not None:   # (a struct field of this call: nothing survives if anything below raises)
-                p.features_ready = features_ready.cuda_event
-            if shade is not None:
-                p.shade = C.addressof(shade)
-            p.forward_only = int(bool(forward_only))   # evaluation: no blend states are kept for a backward
-            rendered = yield (dev, p, o, blobs)          # <- svgir_forward / svgir_forward_batch (gaussian_renderer/_native.py)
+        more = dict(_svgss_fields(prcppoint, patchbbox, config), opacities=opacity, cx=W / 2.0, cy=H / 2.0,
+                    prefiltered=int(bool(prefiltered)))
+        if features_ready is not None:   # (a struct field of this call: nothing survives if anything below raises)
+            more["features_ready"] = features_ready.cuda_event
+        if shade is not None:
+            more["shade"] = C.addressof(shade)
+        rendered, o, blobs = yield from B.forward_call(
+            N.SVGSS, dev, P, [("out_color", (3, H, W)), ("out_normal", (3, H, W)), ("out_depth", (1, H, W)), ("out_opacity", (1, H, W)),
+                              ("out_feature", (S, H, W)), ("out_vfeature", (VS // 4, H, W))], forward_only,
+            S, VS, degree, W, H, scale_modifier, tan_fovx, tan_fovy, debug, background, means3D, sh, colors, features, vfeatures,
+            scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, **more)
         # note: C++ order is (..., depth, opac, ...) -- the Python wrapper re-orders (svgss_rasterization.py:175,183)
-        return (rendered, out_color, out_normal, out_depth, out_opac, out_feature, out_vfeature, out_weights, radii,
-                *blobs.take("geom", "binning", "image"))
+        return (rendered, o["out_color"], o["out_normal"], o["out_depth"], o["out_opacity"], o["out_feature"], o["out_vfeature"],
+                o["out_weights"], o["radii"], *blobs.take("geom", "binning", "image"))
 
     @staticmethod
     def rasterize_gaussians_backward(background, means3D, features, vfeatures, radii, colors, scales, rotations,
@@ -117,92 +78,68 @@ class _CBinding:
                                      binningBuffer, imageBuffer, debug, config, *, shade=None, shade_grads=None, out_weights=None,
                                      scratch_feature_grads=False):
         """`shade` / `shade_grads` (extension, keyword only): the `_native.FusedShade` of the forward and a dict of the shading's
-        gradient outputs + `out_weights` (+ optional `dL_dreduced`), written by svgir_backward (gaussian_renderer/shading.py).
-        `out_weights` (extension, keyword only): the forward's weights [P,1] -- the per-Gaussian kernels behind the composite then walk
-        the blended Gaussians only (all others have zero gradients); worth it from a few hundred thousand surfels on.
+        gradient outputs + `out_weights` (+ optional `dL_dreduced`), written by svgir_backward (gaussian_renderer/shading.py;
+        its "_shapes" entry: _binding.carve_gradients).
+        `out_weights` (extension, keyword only): the forward's weights [P,1] (_binding.fill_grads).
         `scratch_feature_grads` (with `shade`): dL_dfeatures / dL_dvfeatures are intermediates of the fused call -- written for the blended
         surfels, read back by the shading's backward for exactly those -- so they need no zero rows: they are taken out of the cleared
         allocation (45 MB less to clear at P = 200 k); the rows of unblended surfels in the two returned tensors are then UNDEFINED."""
-        dev = means3D.device
-        P = means3D.size(0)
-        S = features.size(1) if features.dim() == 2 else 0
-        VS = vfeatures.size(1) if vfeatures.dim() == 2 else 0
-        # (an upstream gradient may be an EMPTY tensor = all zero: an output that took no part in the loss; nothing is read for it)
-        _gs = [t for t in (dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac, dL_dout_feature, dL_dout_vfeature) if t is not None and t.numel()]
-        if not _gs:
-            raise RuntimeError("rasterize_gaussians_backward: every upstream gradient is empty")
-        H, W = _gs[0].size(1), _gs[0].size(2)
-        M = sh.size(1) if sh.numel() != 0 else 0
-        # (fused shading: per-surfel gradient tensors the caller asks for by shape -- shade_grads["_shapes"] -- live in the same
-        # allocation, so the composite backward's clearing sweep zeroes them too; svgir_backward then writes the differentiated rows)
-        extra = list((shade_grads or {}).pop("_shapes", {}).items()) if shade is not None else []
+        dev, P, S, VS, M = means3D.device, means3D.size(0), B.width(features), B.width(vfeatures), B.sh_count(sh)
+        upstream = dict(dL_dout_color=dL_dout_color, dL_dout_normal=dL_dout_normal, dL_dout_depth=dL_dout_depth,
+                        dL_dout_opacity=dL_dout_opac, dL_dout_feature=dL_dout_feature, dL_dout_vfeature=dL_dout_vfeature)
+        H, W = B.upstream_size(upstream.values())
         scratch_fg = bool(scratch_feature_grads) and shade is not None and P != 0
-        views, gblob = N.grad_blob(dev, [(P, 3), (P, 3), (0 if scratch_fg else P, S), (0 if scratch_fg else P, VS), (P, 3), (P, 3), (P, 1),
-                                         (P, 2, 2), (P, 1), (P, 6), (P, M, 3), (P, 3), (P, 4), (4, 4), (4, 4), (3,)] +
-                                   [tuple(sh) for _, sh in extra], zero=(P == 0))
-        (dL_dmeans3D, dL_dmeans2D, dL_dfeatures, dL_dvfeatures, dL_dcolors, dL_dnormal, dL_ddepth, dL_dconic,
-         dL_dopacity, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dviewmat, dL_dprojmat, dL_dcampos) = views[:16]
+        g, gblob = B.carve_gradients(dev, [
+            ("dL_dmeans3D", (P, 3)), ("dL_dmeans2D", (P, 3)), ("dL_dfeatures", (0 if scratch_fg else P, S)),
+            ("dL_dvfeatures", (0 if scratch_fg else P, VS)), ("dL_dcolors", (P, 3)), ("dL_dnormal", (P, 3)), ("dL_ddepth", (P, 1)),
+            ("dL_dconic", (P, 2, 2)), ("dL_dopacity", (P, 1)), ("dL_dcov3D", (P, 6)), ("dL_dsh", (P, M, 3)), ("dL_dscales", (P, 3)),
+            ("dL_drotations", (P, 4)), ("dL_dviewmat", (4, 4)), ("dL_dprojmat", (4, 4)), ("dL_dcampos", (3,))],
+            P, shade_grads if shade is not None else None)
         if scratch_fg:   # (outside the cleared region: only the blended surfels' rows are ever written and read)
-            dL_dfeatures = N.out_tensor((P, S), torch.float32, dev)      # (NaN-filled under SVGIR_POISON: the tests see a row that is
-            dL_dvfeatures = N.out_tensor((P, VS), torch.float32, dev)    # read without having been written)
-        for (name, _), v in zip(extra, views[16:]):
-            shade_grads[name] = v
+            g["dL_dfeatures"] = N.out_tensor((P, S), torch.float32, dev)      # (NaN-filled under SVGIR_POISON: the tests see a row that is
+            g["dL_dvfeatures"] = N.out_tensor((P, VS), torch.float32, dev)    # read without having been written)
         if P != 0:
-            keep = [N.f32c(t, dev) for t in (background, means3D, sh, colors, features, vfeatures, scales, rotations,
-                                              cov3D_precomp, viewmatrix, projmatrix, campos, prcppoint, patchbbox,
-                                              dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac,
-                                              dL_dout_feature, dL_dout_vfeature, config)]
-            (bg, m3, shc, col, fe, vf, sc, ro, cv, vm, pm, cp, pr, pb, gc, gn, gd, go, gf, gvf, cfg) = keep
-            p = N.new_params()
-            p.variant, p.P, p.S, p.VS, p.D, p.M, p.W, p.H = N.SVGSS, P, S, VS, int(degree), M, W, H
-            p.background, p.means3D, p.shs, p.colors_precomp = N.ptr(bg), N.ptr(m3), N.ptr(shc), N.ptr(col)
-            p.features, p.vfeatures = N.ptr(fe), N.ptr(vf)
-            p.scales, p.rotations, p.cov3D_precomp = N.ptr(sc), N.ptr(ro), N.ptr(cv)
-            p.viewmatrix, p.projmatrix, p.cam_pos = N.ptr(vm), N.ptr(pm), N.ptr(cp)
-            p.prcppoint, p.patchbbox = N.ptr(pr), N.ptr(pb)
-            p.config, p.config_len = N.ptr(cfg), (cfg.numel() if cfg is not None else 0)
-            p.scale_modifier, p.tan_fovx, p.tan_fovy = float(scale_modifier), float(tan_fovx), float(tan_fovy)
-            p.debug = int(bool(debug))
-            g = N.Grads()
-            g.dL_dout_color, g.dL_dout_normal, g.dL_dout_depth = N.ptr(gc), N.ptr(gn), N.ptr(gd)
-            g.dL_dout_opacity, g.dL_dout_feature, g.dL_dout_vfeature = N.ptr(go), N.ptr(gf), N.ptr(gvf)
-            g.dL_dmeans2D, g.dL_dconic, g.dL_dopacity = dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr()
-            g.dL_dcolors, g.dL_dfeatures, g.dL_dvfeatures = dL_dcolors.data_ptr(), N.ptr(dL_dfeatures), N.ptr(dL_dvfeatures)
-            g.dL_dnormal, g.dL_ddepth, g.dL_dmeans3D = dL_dnormal.data_ptr(), dL_ddepth.data_ptr(), dL_dmeans3D.data_ptr()
-            g.dL_dcov3D, g.dL_dsh, g.dL_dscales = dL_dcov3D.data_ptr(), N.ptr(dL_dsh), dL_dscales.data_ptr()
-            g.dL_drotations = dL_drotations.data_ptr()
-            if N.CLEAR_HINT:
-                g.clear_base, g.clear_bytes = gblob.data_ptr(), gblob.numel() * 4
-            g.dL_dviewmat, g.dL_dprojmat, g.dL_dcampos = dL_dviewmat.data_ptr(), dL_dprojmat.data_ptr(), dL_dcampos.data_ptr()
-            if out_weights is not None:
-                g.out_weights = N.ptr(N.f32c(out_weights, dev))
+            p, keep = B.call_params(N.SVGSS, dev, S, VS, degree, W, H, scale_modifier, tan_fovx, tan_fovy, debug, background, means3D, sh,
+                                    colors, features, vfeatures, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                    **_svgss_fields(prcppoint, patchbbox, config))
+            gs, gkeep = B.fill_grads(dev, upstream, g, gblob, out_weights)
             if shade is not None:
                 p.shade = C.addressof(shade)
                 for k, t in shade_grads.items():
-                    setattr(g, k, N.ptr(t))
-            rad = radii.contiguous()
+                    setattr(gs, k, N.ptr(t))
             # scratch for the gradient accumulation: one row per (instance, sub-tile) pair that survived this view's cull (the
             # forward read the count back behind its cull), summed per Gaussian
             nscr = N.lib.svgir_backward_scratch_bytes_for(N.SVGSS, P, binningBuffer.numel(), imageBuffer.data_ptr(), W, H, S, VS)
-            scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
-            N.guarded(dev, "backward", N.lib.svgir_backward, p, g, int(R), rad.data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-                                         binningBuffer.numel(), imageBuffer.data_ptr(), scratch.data_ptr(), nscr,
-                                         N.stream_ptr(dev))
-        return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dfeatures, dL_dvfeatures, dL_dcov3D, dL_dsh,
-                dL_dscales, dL_drotations, dL_dviewmat, dL_dprojmat, dL_dcampos)
+            B.run_backward(dev, p, gs, R, radii, geomBuffer, binningBuffer, imageBuffer, nscr)
+        return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dfeatures"], g["dL_dvfeatures"],
+                g["dL_dcov3D"], g["dL_dsh"], g["dL_dscales"], g["dL_drotations"], g["dL_dviewmat"], g["dL_dprojmat"], g["dL_dcampos"])
 
     @staticmethod
     def mark_visible(means3D, viewmatrix, projmatrix):
-        P = means3D.size(0)
-        present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
-        if P != 0:
-            m3, vm, pm = (N.f32c(t, means3D.device) for t in (means3D, viewmatrix, projmatrix))
-            N.guarded(means3D.device, "mark_visible", N.lib.svgir_mark_visible, N.SVGSS, P, m3.data_ptr(), vm.data_ptr(), pm.data_ptr(),
-                                             present.data_ptr(), N.stream_ptr(means3D.device))
-        return present
+        return B.mark_visible(N.SVGSS, means3D, viewmatrix, projmatrix)
 
 
 _C = _CBinding()
+
+
+def forward_args(st, means3D, features, vfeatures, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                 viewmatrix, projmatrix, campos):
+    """The 24 positional arguments of `_C.rasterize_gaussians` from the settings tuple `st` and the per-call tensors."""
+    return (st.bg, means3D, features, vfeatures, colors_precomp, opacities, scales, rotations, st.scale_modifier, cov3Ds_precomp,
+            viewmatrix, projmatrix, st.prcppoint, st.patch_bbox, st.tanfovx, st.tanfovy, st.image_height, st.image_width, sh,
+            st.sh_degree, campos, st.prefiltered, st.debug, st.config)
+
+
+def backward_args(st, means3D, features, vfeatures, radii, colors_precomp, scales, rotations, cov3Ds_precomp, sh, num_rendered,
+                  geomBuffer, binningBuffer, imgBuffer, grad_out_color, grad_out_normal, grad_out_opacity, grad_out_depth,
+                  grad_out_feature, grad_out_vfeature):
+    """The 31 positional arguments of `_C.rasterize_gaussians_backward` (depth's gradient before opacity's: Q13); upstream gradients
+    autograd left out (None) become empty tensors."""
+    up = [B.grad_or_empty(g, means3D.device) for g in (grad_out_color, grad_out_normal, grad_out_depth, grad_out_opacity,
+                                                        grad_out_feature, grad_out_vfeature)]
+    return (st.bg, means3D, features, vfeatures, radii, colors_precomp, scales, rotations, st.scale_modifier, cov3Ds_precomp,
+            st.viewmatrix, st.projmatrix, st.prcppoint, st.patch_bbox, st.tanfovx, st.tanfovy, *up, sh, st.sh_degree, st.campos,
+            geomBuffer, num_rendered, binningBuffer, imgBuffer, st.debug, st.config)
 
 
 def rasterize_gaussians(
@@ -234,23 +171,10 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, features, vfeatures, sh, colors_precomp, opacities, scales, rotations,
                 cov3Ds_precomp, viewmatrix, projmatrix, campos, raster_settings):
-        args = (
-            raster_settings.bg, means3D, features, vfeatures, colors_precomp, opacities, scales, rotations,
-            raster_settings.scale_modifier, cov3Ds_precomp, viewmatrix, projmatrix, raster_settings.prcppoint,
-            raster_settings.patch_bbox, raster_settings.tanfovx, raster_settings.tanfovy,
-            raster_settings.image_height, raster_settings.image_width, sh, raster_settings.sh_degree, campos,
-            raster_settings.prefiltered, raster_settings.debug, raster_settings.config)
+        args = forward_args(raster_settings, means3D, features, vfeatures, sh, colors_precomp, opacities, scales, rotations,
+                            cov3Ds_precomp, viewmatrix, projmatrix, campos)
         fwd_only = not any(ctx.needs_input_grad)   # (evaluation / no_grad: the composite keeps no blend states for a backward)
-        if raster_settings.debug:
-            cpu_args = cpu_deep_copy_tuple(args)  # copy them before they can be corrupted
-            try:
-                out = _C.rasterize_gaussians(*args, forward_only=fwd_only)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                raise ex
-        else:
-            out = _C.rasterize_gaussians(*args, forward_only=fwd_only)
+        out = B.forward_with_snapshot(_C.rasterize_gaussians, args, dict(forward_only=fwd_only), raster_settings.debug)
         (num_rendered, color, normal, depth, opacity, feature, vfeature, weights, radii, geomBuffer, binningBuffer,
          imgBuffer) = out
         ctx.raster_settings = raster_settings
@@ -263,40 +187,16 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_num_rendered, grad_out_color, grad_out_normal, grad_out_opacity, grad_out_depth,
                  grad_out_feature, grad_out_vfeature, grad_out_weights, grad_out_radii):
-        num_rendered = ctx.num_rendered
         raster_settings = ctx.raster_settings
         (colors_precomp, means3D, features, vfeatures, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
          binningBuffer, imgBuffer, weights) = ctx.saved_tensors
-        H, W = raster_settings.image_height, raster_settings.image_width
-
-        def _g(g, ch):  # autograd hands None for outputs that did not take part in the loss: an empty tensor = all zero for the library
-            return g if g is not None else torch.empty(0, dtype=torch.float32, device=means3D.device)
-
-        args = (raster_settings.bg, means3D, features, vfeatures, radii, colors_precomp, scales, rotations,
-                raster_settings.scale_modifier, cov3Ds_precomp, raster_settings.viewmatrix,
-                raster_settings.projmatrix, raster_settings.prcppoint, raster_settings.patch_bbox,
-                raster_settings.tanfovx, raster_settings.tanfovy, _g(grad_out_color, 3), _g(grad_out_normal, 3),
-                _g(grad_out_depth, 1), _g(grad_out_opacity, 1),
-                _g(grad_out_feature, features.size(1) if features.dim() == 2 else 0),
-                _g(grad_out_vfeature, (vfeatures.size(1) if vfeatures.dim() == 2 else 0) // 4),
-                sh, raster_settings.sh_degree, raster_settings.campos, geomBuffer, num_rendered, binningBuffer,
-                imgBuffer, raster_settings.debug, raster_settings.config)
-        if raster_settings.debug:
-            cpu_args = cpu_deep_copy_tuple(args)
-            try:
-                res = _C.rasterize_gaussians_backward(*args, out_weights=weights)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise ex
-        else:
-            res = _C.rasterize_gaussians_backward(*args, out_weights=weights)
+        args = backward_args(raster_settings, means3D, features, vfeatures, radii, colors_precomp, scales, rotations,
+                             cov3Ds_precomp, sh, ctx.num_rendered, geomBuffer, binningBuffer, imgBuffer, grad_out_color,
+                             grad_out_normal, grad_out_opacity, grad_out_depth, grad_out_feature, grad_out_vfeature)
+        res = B.backward_with_snapshot(_C.rasterize_gaussians_backward, args, dict(out_weights=weights), raster_settings.debug)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_features, grad_vfeatures,
          grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations, grad_viewmat, grad_projmat, grad_campos) = res
-
-        def _m(g, like):  # grads of inputs that were passed as empty placeholders
-            return g if (like is not None and like.numel() != 0) else None
-
+        _m = B.grad_if_given
         grads = (
             grad_means3D,
             grad_means2D,
@@ -334,44 +234,14 @@ class GaussianRasterizationSettings(NamedTuple):
     config: torch.Tensor
 
 
-class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
-        super().__init__()
-        self.raster_settings = raster_settings
-
-    def markVisible(self, positions):
-        # Mark visible points (based on frustum culling for camera) with a boolean
-        with torch.no_grad():
-            raster_settings = self.raster_settings
-            visible = _C.mark_visible(positions, raster_settings.viewmatrix, raster_settings.projmatrix)
-        return visible
+class GaussianRasterizer(B.RasterizerBase):
+    variant = N.SVGSS
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, features=None, vfeatures=None):
         raster_settings = self.raster_settings
-
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or (
-                (scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-
-        empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
-        if shs is None:
-            shs = empty
-        if colors_precomp is None:
-            colors_precomp = empty
-        if scales is None:
-            scales = empty
-        if rotations is None:
-            rotations = empty
-        if cov3D_precomp is None:
-            cov3D_precomp = empty
-        if features is None:
-            features = torch.empty_like(means3D[..., :0])
-        if vfeatures is None:
-            vfeatures = torch.empty_like(means3D[..., :0])
+        shs, colors_precomp, scales, rotations, cov3D_precomp, features, vfeatures = B.rasterizer_inputs(
+            means3D, shs, colors_precomp, scales, rotations, cov3D_precomp, features, vfeatures)
 
         # Invoke the HIP rasterization routine
         return rasterize_gaussians(
