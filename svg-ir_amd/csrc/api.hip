@@ -347,7 +347,10 @@ int validate(const svgir_params* p, bool fwd) {
     if (p->P < 0 || p->W <= 0 || p->H <= 0) return fail(SVGIR_ERR_INVALID, "bad sizes P=%d W=%d H=%d", p->P, p->W, p->H);
     if (p->P > 40000000) return fail(SVGIR_ERR_INVALID, "P=%d exceeds the supported 40 000 000 Gaussians (32-bit byte offsets into the splat records)", p->P);
     // packing limits of the state blobs: tile rectangle x0 | y0 << 10 | width << 20 (common.hpp R_RECT) and
-    // (sub-tile id << SEG_K_BITS) | segment (seg_list)
+    // (sub-tile id << SEG_K_BITS) | segment (seg_list).  The grid is bounded here; a LIST is not: segments hold SEG = 64 candidates, so a
+    // sub-tile's list may be consumed up to (1 << SEG_K_BITS) * SEG = 2^20 candidates before the segment index spills into the sub-tile id.
+    // That takes more than 2^20 surfels over one 8x8 pixel block whose pixels never terminate; it is not checked on the device yet
+    // (DESIGN.md sections 2 and 7).
     const ViewGrid v = view_grid(p->W, p->H);
     if (v.gx > 1023 || v.gy > 1023 || 4ll * v.gx * v.gy >= (1ll << (32 - SEG_K_BITS)))
         return fail(SVGIR_ERR_INVALID, "image %dx%d exceeds the supported size (at most 1023 tiles per side, %lld tiles in total)",

@@ -386,6 +386,109 @@ def stack_scene(variant="svgss", counts=STACK_COUNTS, terminate=False, seed=71, 
     return sc
 
 
+# ---- binning scenes: every surfel's tiles, depth key and rank are known before anything runs (tests/test_binning_scenes.py) ----
+
+BINNING_EYE = (0.0, 0.0, 4.0)     # on the world z axis, looking down it: view depth = 4 - z_world, ONE fp32 rounding, whatever x and y are
+
+
+def binning_scene(variant="rgss", P=5000, gx=8, gy=6, layout="uniform", depth="spread", edge_frac=0.0, n_culled=0, n_near=0, seed=0,
+                  sh_degree=0, S=0, VS=0, opacity=(0.3, 0.9), bg=0.5):
+    """P surfels on a gx x gy tile grid (image 16 gx x 16 gy), each with a footprint far below a pixel (world scale 0.05 px: the
+    0.3 px^2 low-pass alone sets the radius), placed within 1.5 px of a tile's centre (u = 16 tx + 7.5): its rectangle is that one
+    tile.  A share `edge_frac` sits on the tile's right edge instead (u = 16 tx + 15.5): two tiles, tx and tx + 1, except in the
+    last column.
+      layout: "uniform" over the grid | "one" tile | "eight" tiles spread over the grid, in equal shares | "skewed" (a twentieth of the tiles, weights
+              falling geometrically: most tiles stay empty);
+      depth:  "spread" over [0.6, 30) (three different top bytes of the fp32 key) | "binade": [2.5, 3.5) (one top byte, 0x40) |
+              "same": one bit-identical depth for all (the whole order is the stable order of the indices);
+      n_culled of the P surfels are culled (alternately behind the camera and facing away), interleaved by index with the visible ones;
+      n_near extra splats (appended: indices P ...) at depth 0.5-0.7 whose 3 sigma is four image widths: their rectangle is the whole grid.
+    The camera looks down the world z axis, so a surfel's view depth is 4 - z_world in one fp32 rounding and "same" really is
+    bit-identical.  Indices are shuffled against every construction order.
+    sc["plan"]: per surfel `tile` (its first tile), `tile2` (the second one, -1: none), `visible`, `depth` (fp32, what the
+    preprocess must compute), the grid, and `R`, the instance count all of this implies."""
+    rng = np.random.default_rng(seed)
+    W, H, T = 16 * gx, 16 * gy, gx * gy
+    sc = {"sh_degree": sh_degree, "bg": np.full(3, bg, dtype=np.float32), "config": np.array([1.0, 1.0, 1.0], dtype=np.float32),
+          "scale_modifier": 1.0, "backward_geometry": True, "computer_pseudo_normal": False}
+    # (the longer image side gets the usual field of view: on a grid one tile wide and hundreds high the other choice is a 170 degree
+    # vertical fov, where the perspective Jacobian at the image's ends stretches the radii from 3 to 7 px)
+    fov = cameras.TENSOIR_FOVX if gx >= gy else 2.0 * math.atan(math.tan(cameras.TENSOIR_FOVX / 2) * gx / gy)
+    sc.update(cameras.make_camera(W, H, np.array(BINNING_EYE), fovx=fov))
+    fx, _ = _focal(sc)
+    visible = np.ones(P, dtype=bool)
+    if n_culled:
+        visible[np.round(np.linspace(0, P - 1, n_culled)).astype(np.int64)] = False
+        assert (~visible).sum() == n_culled
+    if layout == "uniform":
+        tile = rng.integers(0, T, size=P)
+    elif layout == "one":
+        tile = np.full(P, (gy // 2) * gx + gx // 2)
+    elif layout == "eight":
+        tile = np.full(P, T // 16)
+        nv = int(visible.sum())
+        tile[visible] = (((np.arange(8) * T) // 8 + T // 16) % T)[rng.permutation(nv) % 8]     # equal shares: no list beyond ceil(visible / 8)
+    elif layout == "skewed":
+        pool = rng.choice(T, size=max(1, T // 20), replace=False)
+        w = 0.8 ** np.arange(len(pool))
+        tile = pool[rng.choice(len(pool), size=P, p=w / w.sum())]
+    else:
+        raise ValueError(layout)
+    tx, ty = tile % gx, tile // gx
+    edge = rng.random(P) < edge_frac
+    u = 16.0 * tx + np.where(edge, 15.5, 7.5 + rng.uniform(-1.5, 1.5, size=P))
+    v = 16.0 * ty + 7.5 + rng.uniform(-1.5, 1.5, size=P)
+    if depth == "spread":
+        z = np.exp(rng.uniform(math.log(0.6), math.log(30.0), size=P))
+    elif depth == "binade":
+        z = rng.uniform(2.5, 3.5, size=P)
+    elif depth == "same":
+        z = np.full(P, 3.0)
+    else:
+        raise ValueError(depth)
+    cul = np.nonzero(~visible)[0]
+    behind = np.zeros(P, dtype=bool)
+    behind[cul[0::2]] = True
+    pts = _unproject(sc, u, v, np.where(behind, -z, z))
+    nrm = sc["campos"][None].astype(np.float64) - pts
+    nrm[cul[1::2]] *= -1.0                                  # facing away
+    s = 0.05 * z / fx
+    sc["means3D"] = pts.astype(np.float32)
+    sc["scales"] = np.stack([s, s, s], -1).astype(np.float32)
+    sc["rotations"] = _quat_from_frame_fast(nrm, rng)
+    sc.update(_attrs(P, rng, variant, S, VS, sh_degree, rng.uniform(opacity[0], opacity[1], size=P)))
+    tile2 = np.where(edge & (tx < gx - 1), tile + 1, -1)
+    if n_near:
+        zn = rng.uniform(0.5, 0.7, size=n_near)
+        pn = _unproject(sc, rng.uniform(0.4, 0.6, size=n_near) * W, rng.uniform(0.4, 0.6, size=n_near) * H, zn)
+        sn = (4.0 * max(W, H) / 3.0) * zn / fx
+        add = {"means3D": pn.astype(np.float32), "scales": np.stack([sn, sn, sn], -1).astype(np.float32), "rotations": _facing(sc, pn, rng)}
+        add.update(_attrs(n_near, rng, variant, S, VS, sh_degree, rng.uniform(0.05, 0.15, size=n_near)))
+        _append(sc, add)
+    sc["plan"] = {"gx": gx, "gy": gy, "T": T, "n_near": n_near, "tile": tile.astype(np.int64), "tile2": tile2.astype(np.int64),
+                  "visible": visible, "depth": np.float32(BINNING_EYE[2]) - sc["means3D"][:, 2],
+                  "R": int(visible.sum() + (tile2[visible] >= 0).sum() + n_near * T)}
+    return sc
+
+
+def binning_expected(sc):
+    """(point_list, ranges [T, 2]) that sc["plan"] implies: instances ordered by (tile, fp32 depth bits, index), plain numpy."""
+    pl = sc["plan"]
+    T, Pn = pl["T"], len(pl["tile"])
+    vis = np.nonzero(pl["visible"])[0]
+    two = vis[pl["tile2"][vis] >= 0]
+    near = np.arange(Pn, Pn + pl["n_near"])
+    idx = np.concatenate([vis, two, np.repeat(near, T)])
+    til = np.concatenate([pl["tile"][vis], pl["tile2"][two], np.tile(np.arange(T), pl["n_near"])])
+    key = np.ascontiguousarray(pl["depth"]).view(np.uint32)[idx]
+    order = np.lexsort((idx, key, til))
+    cnt = np.bincount(til, minlength=T)
+    end = np.cumsum(cnt)
+    ranges = np.stack([end - cnt, end], -1)
+    ranges[cnt == 0] = 0
+    return idx[order].astype(np.uint32), ranges.astype(np.uint32)
+
+
 def upstream_grads(sc, variant, seed=101):
     """dL/d(outputs) ~ N(0,1)/(H*W) for every differentiable output."""
     rng = np.random.default_rng(seed)

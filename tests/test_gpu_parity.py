@@ -62,7 +62,11 @@ def _run_both(sc, variant, grads=None):
 
 def _check_binning(sc, variant, o, R):
     """Integer state compared directly with the oracle: instance list (a5), tile ranges (a6), last contributors (a7)."""
-    raw = runner.forward_raw(runner.to_torch(sc, _dev()), variant)
+    _check_binning_raw(runner.forward_raw(runner.to_torch(sc, _dev()), variant), o, R)
+
+
+def _check_binning_raw(raw, o, R):
+    """The same on a forward the caller has run (runner.forward_raw), so that one view can be checked for its images as well."""
     assert raw["num_rendered"] == R
     assert np.array_equal(raw["point_list"], o.get("point_list")[:R]), "depth-sorted instance list differs from the oracle's"
     assert np.array_equal(raw["ranges"].reshape(-1), o.get("ranges").reshape(-1)), "tile ranges differ"
