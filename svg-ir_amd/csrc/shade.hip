@@ -212,6 +212,7 @@ __global__ void __launch_bounds__(BLOCK) resample_kernel(const float* __restrict
 struct GaussConst {  // per-(Gaussian, corner) constants of a phase-2 lane
     float nraw[3], Nh[3], a2, kk, nom1, fd[3], r;
     float sgn, inv_len, NoV_raw;  // for the backward
+    float n2c;                    // 1 - |Nh|^2: exactly 0 for a normalised normal, > 0 for one under the 1e-12 norm clamp (see ggx_nom0)
 };
 
 // The GGX denominator term  nom0 = clamp(N.H, 1e-6, 1)^2 (alpha^2 - 1) + 1  (svgss.py:612-617) for unit N (flipped to the viewer) and
@@ -220,11 +221,13 @@ struct GaussConst {  // per-(Gaussian, corner) constants of a phase-2 lane
 // whose results are small and carry ~1e-7 ABSOLUTE error, i.e. ~1e-5 of their own size at the lobe's width; an error of N.H itself
 // enters squared)  nom0 = alpha^2 + |H - (N.H) N|^2 (1 - alpha^2)  is good to ~1e-5 where the literal form -- the reference's own fp32
 // code included -- is good to ~2e-3; the lower clamp (N.H < 1e-6: H behind the surface) keeps the reference's value.
-__device__ __forceinline__ float ggx_nom0(const float* N, const float* H, float a2) {
+// A normal shorter than the reference's 1e-12 norm clamp stays shorter than 1 after n / max(|n|, 1e-12): then
+// 1 - N.H^2 = |H - (N.H) N|^2 + N.H^2 (1 - |N|^2), and n2c = 1 - |N|^2 carries the second term (0 for every other normal).
+__device__ __forceinline__ float ggx_nom0(const float* N, const float* H, float a2, float n2c) {
     const float noh = N[0] * H[0] + N[1] * H[1] + N[2] * H[2];
 #if SHADE_PRECISE >= 2
     const float px = fmaf(-noh, N[0], H[0]), py = fmaf(-noh, N[1], H[1]), pz = fmaf(-noh, N[2], H[2]);
-    const float s2 = fminf(px * px + py * py + pz * pz, 1.f);
+    const float s2 = fminf(fmaf(noh * noh, n2c, px * px + py * py + pz * pz), 1.f);
     return noh >= 1e-6f ? fmaf(s2, 1.f - a2, a2) : 1e-12f * (a2 - 1.f) + 1.f;
 #else
     const float NoH = fminf(1.f, fmaxf(1e-6f, noh));
@@ -243,7 +246,8 @@ __device__ __forceinline__ CornerIn load_corner_in(const svgir_shade_params& p, 
 __device__ __forceinline__ void corner_consts(const CornerIn& ci, const float* V, GaussConst& c) {
     const float* n = ci.n;
     c.nraw[0] = n[0]; c.nraw[1] = n[1]; c.nraw[2] = n[2];
-    const float len = fmaxf(sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]), 1e-12f);
+    const float len_raw = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const float len = fmaxf(len_raw, 1e-12f);
 #if SHADE_PRECISE >= 1
     c.inv_len = 1.0f / len;
 #else
@@ -254,6 +258,7 @@ __device__ __forceinline__ void corner_consts(const CornerIn& ci, const float* V
     c.sgn = nov > 0.f ? 1.f : (nov < 0.f ? -1.f : 0.f);
     c.Nh[0] = Nn[0] * c.sgn; c.Nh[1] = Nn[1] * c.sgn; c.Nh[2] = Nn[2] * c.sgn;
     c.NoV_raw = c.Nh[0] * V[0] + c.Nh[1] * V[1] + c.Nh[2] * V[2];
+    c.n2c = len_raw < 1e-12f ? 1.f - (Nn[0] * Nn[0] + Nn[1] * Nn[1] + Nn[2] * Nn[2]) : 0.f;
     const float NoV = fminf(1.f, fmaxf(1e-6f, c.NoV_raw));
     c.r = ci.r;
     const float a = c.r * c.r;
@@ -435,7 +440,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
         const float* r = sS + s * SREC;
         const float ndi = fmaxf(c.nraw[0] * r[0] + c.nraw[1] * r[1] + c.nraw[2] * r[2], 0.f);
         const float NoL = fminf(1.f, fmaxf(1e-6f, c.Nh[0] * r[3] + c.Nh[1] * r[4] + c.Nh[2] * r[5]));
-        const float nom0 = ggx_nom0(c.Nh, r + 6, c.a2);
+        const float nom0 = ggx_nom0(c.Nh, r + 6, c.a2, c.n2c);
         const float nom = fminf(4.f * kPi, fmaxf(1e-6f, 4.f * kPi * nom0 * nom0 * c.nom1 * (NoL * (1.f - c.kk) + c.kk)));
         const float fs = r[9] * c.a2 * __builtin_amdgcn_rcpf(nom);
         const float ge = r[16] * ndi;
@@ -661,7 +666,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
             const float px = fmaf(-nohu, c.Nh[0], fmaf(r.d[0], r.il, V[0])), py = fmaf(-nohu, c.Nh[1], fmaf(r.d[1], r.il, V[1])),
                         pz = fmaf(-nohu, c.Nh[2], fmaf(r.d[2], r.il, V[2]));
             const float hs = 0.5f * r.ih;
-            const float s2 = fminf((px * px + py * py + pz * pz) * (hs * hs), 1.f);
+            const float s2 = fminf(fmaf(nohr * nohr, c.n2c, (px * px + py * py + pz * pz) * (hs * hs)), 1.f);
             const float nom0 = nohr >= 1e-6f ? fmaf(s2, -a2m1, c.a2) : 1e-12f * a2m1 + 1.f;
 #else
             const float NoH = fminf(1.f, fmaxf(1e-6f, nohr));
@@ -1004,6 +1009,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
             o[41 + ch] = gmi[ch] + gml[ch];   // constant part of dL/dradiance
             o[44 + ch] = dir_b[ch]; o[47 + ch] = dir_n[ch];
         }
+        o[50] = c.n2c;
         o[9] = c.a2; o[10] = c.kk; o[11] = c.nom1; o[15] = c.r; o[16] = c.sgn; o[17] = c.inv_len; o[18] = c.NoV_raw; o[19] = dir_r;
         }
     }
@@ -1027,7 +1033,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
             qd[0] = q8.x; qd[1] = q8.y; qd[2] = q8.z; ql[0] = q8.w; ql[1] = q9.x; ql[2] = q9.y;
             gmig[0] = q9.z; gmig[1] = q9.w; gmig[2] = q10.x;
             grad_const = k == 0 ? q10.y : (k == 1 ? q10.z : q10.w);   // lane k owns channel k (< 3) of dL/dradiance
-            dir_b[0] = q11.x; dir_b[1] = q11.y; dir_b[2] = q11.z; dir_n[0] = q11.w; dir_n[1] = q12.x; dir_n[2] = q12.y;
+            dir_b[0] = q11.x; dir_b[1] = q11.y; dir_b[2] = q11.z; dir_n[0] = q11.w; dir_n[1] = q12.x; dir_n[2] = q12.y; c.n2c = q12.z;
         }
         DEV_TRACE_MARK(0);   // inputs -> per-(Gaussian, corner) constants
         dev_n++;
@@ -1064,7 +1070,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
                 const float NoLr = c.Nh[0] * Lv[0] + c.Nh[1] * Lv[1] + c.Nh[2] * Lv[2];
                 const float NoHr = c.Nh[0] * r[4] + c.Nh[1] * r[5] + c.Nh[2] * r[6];
                 const float NoL = fminf(1.f, fmaxf(1e-6f, NoLr)), NoH = fminf(1.f, fmaxf(1e-6f, NoHr));
-                const float nom0 = ggx_nom0(c.Nh, r + 4, c.a2);   // (the VALUE; its derivative below is the literal form's)
+                const float nom0 = ggx_nom0(c.Nh, r + 4, c.a2, c.n2c);   // (the VALUE; its derivative below is the literal form's)
                 const float nom2 = NoL * (1.f - c.kk) + c.kk;
                 const float nomr = 4.f * kPi * nom0 * nom0 * c.nom1 * nom2;
                 const float nom = fminf(4.f * kPi, fmaxf(1e-6f, nomr));
@@ -1087,7 +1093,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
                     d_ndi += (cg * Lg + cl * Ll) * area;
                 }
                 {
-                    const float dm = ndr > 0.f ? d_ndi : 0.f;
+                    const float dm = ndr >= 0.f ? d_ndi : 0.f;   // (clamp(min=0) passes its gradient AT the bound: a zero normal, n.l = 0 exactly)
 #pragma unroll
                     for (int j = 0; j < 3; j++) d_n[j] += dm * r[j];
                 }
@@ -1155,7 +1161,10 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
 #pragma unroll
                 for (int j = 0; j < 3; j++) {
                     const int i = lane + 64 * j;
-                    if (i < 3 * cnt) ratio_acc += sS[(i / 3) * BREC + 12 + (i % 3)] * rawp[i];
+                    if (i < 3 * cnt) {   // (entries whose product was not finite carry a masked 0: they add nothing, whatever the raw value -- 0 * NaN)
+                        const float gk = sS[(i / 3) * BREC + 12 + (i % 3)];
+                        ratio_acc += gk != 0.f ? gk * rawp[i] : 0.f;
+                    }
                 }
             }
             if (a.d_radiance) {
@@ -1177,10 +1186,11 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
 #pragma unroll
             for (int j = 0; j < 3; j++) d_Nh[j] += d_NoV * V[j];
         }
-        // Nh = sgn * n / |n|  =>  dn += sgn/|n| * (dNh - Nn (Nn . dNh)),  Nn = n/|n|
+        // Nh = sgn * n / |n|  =>  dn += sgn/|n| * (dNh - Nn (Nn . dNh)),  Nn = n/|n|; under the norm clamp Nh = sgn * n * 1e12 is linear
+        // in n and the projection term is absent
         {
             const float Nn[3] = {c.nraw[0] * c.inv_len, c.nraw[1] * c.inv_len, c.nraw[2] * c.inv_len};
-            const float dot = Nn[0] * d_Nh[0] + Nn[1] * d_Nh[1] + Nn[2] * d_Nh[2];
+            const float dot = c.inv_len < 1.0f / 1e-12f ? Nn[0] * d_Nh[0] + Nn[1] * d_Nh[1] + Nn[2] * d_Nh[2] : 0.f;
 #pragma unroll
             for (int j = 0; j < 3; j++) d_n[j] += c.sgn * c.inv_len * (d_Nh[j] - Nn[j] * dot);
         }
