@@ -107,11 +107,12 @@ bool pinned_spin(volatile unsigned long long* at, uint32_t tag, uint32_t* w0, ui
     }
 }
 // Per-view counts that exist only behind the cull -- the surviving (sub-tile, instance) pairs (= gradient rows the svgss backward needs)
-// and the state slots the composite forward may dump into -- reach the host as tagged 8-byte stores of order_desc_kernel into pinned
-// memory (no copy operation, no event on the stream) and are kept per IMAGE BLOB together with the capacities the forward laid the
+// and the state slots the composite forward may dump into -- reach the host as tagged 8-byte stores of the first kernel behind the cull
+// (common.hpp dispatch_item; high fill: order_xcd_kernel) into pinned memory (no copy operation, no event on the stream) and are kept per IMAGE BLOB together with the capacities the forward laid the
 // binning blob out for: the backward and svgir_backward_scratch_bytes_for() find them there.  A host wait right behind the cull costs
 // nothing: the composite is still queued (measured with a full event synchronisation there: 0.4353 vs 0.4361 ms per cfg2 step).
 struct ViewEntry { const void* key = nullptr; uint32_t tag = 0; int cap_R = 0; long long cap_slots = -1; unsigned long long stamp = 0;
+                   bool queue = false;   // the dispatch order of its composite: the cull's buckets (else the list sub_order)
                    bool recorded = false;   // its slot total has entered the workload's history
                    hipStream_t stream = nullptr; };   // the stream the forward ran on: what a waiter without a stream of its own blocks on
 constexpr int kViewEntries = 1024;   // forwards whose backward may still come (least recently used entry replaced)
@@ -121,8 +122,8 @@ constexpr int kViewWords = 4;
 unsigned long long* g_view_pinned = nullptr;   // [kViewEntries][kViewWords] {tag << 32 | pairs, tag << 32 | slots, tag << 32 | non-empty sub-tiles, -}
 unsigned long long g_view_clock = 0;
 uint32_t g_view_tag = 0;
-// registers the launch sequence of the forward that owns `image_blob`: returns where order_desc_kernel writes its totals and the tag
-unsigned long long* view_note(const void* image_blob, int cap_R, long long cap_slots, uint32_t* tag, hipStream_t stream) {
+// registers the launch sequence of the forward that owns `image_blob`: returns where its totals are to be written and the tag
+unsigned long long* view_note(const void* image_blob, int cap_R, long long cap_slots, bool queue, uint32_t* tag, hipStream_t stream) {
     std::lock_guard<std::mutex> lk(g_view_mu);
     if (!g_view_pinned && !(g_view_pinned = pinned_words(kViewEntries * kViewWords))) return nullptr;
     int slot = 0;
@@ -132,16 +133,18 @@ unsigned long long* view_note(const void* image_blob, int cap_R, long long cap_s
     }
     ViewEntry& e = g_view[slot];
     e.key = image_blob; e.stamp = ++g_view_clock; e.cap_R = cap_R; e.cap_slots = cap_slots; e.recorded = false;
-    e.stream = stream;
+    e.stream = stream; e.queue = queue;
     e.tag = ++g_view_tag ? g_view_tag : ++g_view_tag;   // (never 0: the slots start as 0)
     *tag = e.tag;
     return g_view_pinned + kViewWords * slot;
 }
-// The same four numbers live in the image blob itself (ImageLayout::counters, written by order_desc_kernel): a blob the host table no
+// The same four numbers live in the image blob itself (ImageLayout::counters, written with the host copy): a blob the host table no
 // longer knows -- more than kViewEntries forwards ago, or a binder that moved / cloned the saved buffer -- is still self-describing, like
 // the reference's blobs; the table is the fast path (no device read, no synchronisation).
-constexpr uint32_t kBlobMagic = 0x53564931u;   // "SVI1" in counters[3]: order_desc_kernel of this library version wrote the words behind it
-struct ViewCounts { bool known = false; int cap_R = 0; long long cap_slots = -1, pairs = -1, slots = -1, nonempty = -1; hipError_t err = hipSuccess; };
+// counters[3]: this library version wrote the words behind it, and the view's composite waves find their sub-tiles in the list
+// sub_order ("SVI1") or in the cull's dispatch buckets ("SVI2", RenderArgs::queue_order) -- what a state re-dump has to know
+constexpr uint32_t kBlobMagic = 0x53564931u, kBlobMagicQueue = 0x53564932u;
+struct ViewCounts { bool known = false; bool queue = false; int cap_R = 0; long long cap_slots = -1, pairs = -1, slots = -1, nonempty = -1; hipError_t err = hipSuccess; };
 enum class Wait { kCaps, kLook, kBlock };
 // The capacities and counts of the forward that owns `image_blob` (known = false: an unknown view), found in this order:
 //   1. the host table: the capacities (no device read, no synchronisation; kCaps: nothing else);
@@ -167,7 +170,7 @@ ViewCounts resolve_view(const void* image_blob, const uint32_t* blob_counters, W
         std::lock_guard<std::mutex> lk(g_view_mu);
         while (g_view_pinned && i < kViewEntries && g_view[i].key != image_blob) i++;
         if (!g_view_pinned || i == kViewEntries) i = -1;
-        else { tag = g_view[i].tag; fwd_stream = g_view[i].stream; out.cap_R = g_view[i].cap_R; out.cap_slots = g_view[i].cap_slots; }
+        else { tag = g_view[i].tag; fwd_stream = g_view[i].stream; out.cap_R = g_view[i].cap_R; out.cap_slots = g_view[i].cap_slots; out.queue = g_view[i].queue; }
     }
     out.known = i >= 0;
     if (out.known && how != Wait::kCaps) {
@@ -203,8 +206,8 @@ ViewCounts resolve_view(const void* image_blob, const uint32_t* blob_counters, W
         out.err = stream ? hipStreamSynchronize(*stream) : hipDeviceSynchronize();
         const bool read = out.err == hipSuccess && hipMemcpy(w, blob_counters, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess;
         if (out.err == hipSuccess && !read) (void)hipGetLastError();
-        if (!read || w[3] != kBlobMagic) return out;
-        out.known = true; out.pairs = (long long)w[1]; out.slots = (long long)w[2]; out.cap_R = (int)w[4];
+        if (!read || (w[3] != kBlobMagic && w[3] != kBlobMagicQueue)) return out;
+        out.known = true; out.queue = w[3] == kBlobMagicQueue; out.pairs = (long long)w[1]; out.slots = (long long)w[2]; out.cap_R = (int)w[4];
         out.cap_slots = (long long)((unsigned long long)w[5] | ((unsigned long long)w[6] << 32));
     }
     return out;
@@ -425,7 +428,7 @@ RenderArgs render_args(const svgir_params* p, const ViewGrid& v, const GeomLayou
     ra.ranges = I.ranges; ra.point_list = B.val[fin]; ra.rec = G.rec; ra.features = p->features; ra.vfeatures = p->vfeatures;
     ra.bg = p->background; ra.cfg = cfg_ref(p);
     ra.sub_list = B.sub_list; ra.sub_total = I.sub_total; ra.sub_order = I.sub_order; ra.sub_count = I.sub_count; ra.sub_ndump = I.sub_ndump;
-    ra.sub_pair_base = I.sub_pair_base; ra.sub_slot_base = I.sub_slot_base;
+    ra.sub_pair_base = I.sub_pair_base; ra.sub_slot_base = I.sub_slot_base; ra.disp_ctr = I.disp_ctr; ra.disp_item = I.disp_item;
     ra.seg_list = B.seg_list; ra.seg_desc = B.seg_desc; ra.seg_count = I.counters; ra.seg_block = I.seg_block; ra.seg_state = B.seg_state;
     ra.slot_cap = (uint32_t)std::min<size_t>(B.slot_cap, 0xffffffffu);
     ra.order_n = (int)order_entries(v.gx, v.gy);
@@ -510,7 +513,7 @@ struct ForwardCall {
     int run_binning_and_render(char* bblob, int cap, long long cap_slots, bool timed, bool cull_only = false) {
         const BinLayout B = bin_layout(bblob, cap, v.T, nstate, cap_slots);
         launch_emit(P, depth_order, G.tiles, G.offsets, G.rec, o->radii, v.gx, v.gy, B.key[0], B.val[0], cap, I.ranges,
-                    I.counters, B.radix_tbl, G.counters + 3, s);
+                    I.counters, B.radix_tbl, G.counters + 3, I.disp_ctr, s);
         if (int rc = check("emit")) return rc;
         if (timed) stage_mark(tm, "emit");
         if (plan.single) {   // up to 4096 tiles: one counting pass over the whole tile id, which also yields the tile ranges
@@ -534,21 +537,31 @@ struct ForwardCall {
         const bool clear_stencil = !svgss && !p->computer_pseudo_normal;
         ra.zero_a = clear_stencil ? o->out_pseudo_normal : nullptr;
         ra.zero_b = clear_stencil ? o->out_surface_xyz : nullptr;
-        launch_cull(ra, s);
-        // dispatch order of the sub-tiles, first gradient row / first state slot of each, and the two totals (device + tagged host copy)
-        uint32_t vtag = 0;
-        unsigned long long* vslot = view_note(iblob, cap, cap_slots, &vtag, s);
-        const bool row_path = svgss && p->VS > 0 && render_specialised(p->S, p->VS, true);   // (only the svgss backward writes gradient rows)
-        // (a launch of many rounds of waves gets one longest-first list per XCD instead of one global list: common.hpp ORDER_NONE)
+        // Dispatch order of the sub-tiles, first gradient row / first state slot of each, and the two totals (device + tagged host copy):
+        // a launch of many rounds of waves gets one longest-first list per XCD from a kernel behind the cull (common.hpp ORDER_NONE);
+        // otherwise the cull itself fills the dispatch buckets and allocates rows and slots, and the first wave of the next kernel
+        // stores the totals (common.hpp DISP_NCLS).
         static const int xcd_forced = [] { const char* e = getenv("SVGIR_FWD_XCD"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
         const bool per_xcd = ra.bg_in_render && (xcd_forced >= 0 ? xcd_forced != 0 : ra.hi_fill != 0);   // (specialised composite kernels only)
-        launch_order_desc(I.sub_total, 4 * v.T, I.sub_order, row_path ? I.sub_pair_base : nullptr, I.sub_slot_base, I.counters, vslot, vtag,
-                          (uint32_t)cap, cap_slots, kBlobMagic, v.gx, ra.order_n, per_xcd, s);
+        uint32_t vtag = 0;
+        unsigned long long* vslot = view_note(iblob, cap, cap_slots, !per_xcd, &vtag, s);
+        ra.queue_order = per_xcd ? 0 : 1;
+        ra.pub_host = vslot; ra.pub_tag = vtag; ra.pub_cap_R = (uint32_t)cap; ra.pub_cap_slots = cap_slots; ra.pub_magic = kBlobMagicQueue;
+        ra.publish = ra.queue_order;   // (handed to the first kernel behind the cull, then cleared)
+        launch_cull(ra, s);
+        if (per_xcd) {
+            const bool row_path = svgss && p->VS > 0 && render_specialised(p->S, p->VS, true);   // (only the svgss backward writes gradient rows)
+            launch_order_desc(I.sub_total, 4 * v.T, I.sub_order, row_path ? I.sub_pair_base : nullptr, I.sub_slot_base, I.counters, vslot, vtag,
+                              (uint32_t)cap, cap_slots, kBlobMagic, v.gx, ra.order_n, s);
+        } else if (cull_only) {
+            launch_dispatch_publish(ra, s);
+        }
         if (int rc = check("cull")) return rc;
         if (timed) stage_mark(tm, "cull");
         if (cull_only) return 0;   // (the sizing phase of a workload's first view: see finish())
         if (prepass) {
             RenderArgs rp = ra;
+            ra.publish = 0;
             rp.S = 0; rp.VS = 0; rp.features = nullptr; rp.vfeatures = nullptr; rp.needed = G.needed;
             launch_contrib_prepass(rp, s);
             if (int rc = check("prepass")) return rc;
@@ -887,6 +900,7 @@ struct BackwardCall {
         RenderArgs rd = ra;
         rd.slot_cap = (uint32_t)std::min<long long>(slots, 0xffffffffll);
         rd.dump_only = 1;
+        rd.queue_order = vc.queue ? 1 : 0;   // (the dispatch order the forward left in the image blob)
         if (launch_render_fwd(rd, svgss, s) < 0) return fail(SVGIR_ERR_INVALID, "state re-dump: no specialised composite");
         stage_mark(tm, "state_redump");
         return 0;

@@ -463,11 +463,13 @@ __global__ void __launch_bounds__(BLOCK) emit_kernel(int P, const uint32_t* __re
                                                      uint32_t* __restrict__ tile_keys, uint32_t* __restrict__ vals,
                                                      uint32_t cap, uint32_t* __restrict__ ranges, int n_ranges,
                                                      uint32_t* __restrict__ seg_count, uint32_t* __restrict__ gtot,
-                                                     int n_gtot, const uint32_t* __restrict__ span) {
+                                                     int n_gtot, const uint32_t* __restrict__ span,
+                                                     uint32_t* __restrict__ disp_ctr) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
-    // piggy-backed initialisation of three small tables used by later stages (saves three memset launches)
+    // piggy-backed initialisation of four small tables used by later stages (saves as many memset launches)
     for (int j = i; j < n_ranges; j += gridDim.x * BLOCK) ranges[j] = 0u;
     for (int j = i; j < n_gtot; j += gridDim.x * BLOCK) gtot[j] = 0u;
+    for (int j = i; j < DISP_CTR_WORDS; j += gridDim.x * BLOCK) disp_ctr[j] = 0u;   // (the cull's dispatch buckets: common.hpp DISP_NCLS)
     if (i == 0) seg_count[0] = 0u;
     // One wave = 64 consecutive Gaussians of the depth order; their instances are one contiguous run of the output (offsets is the
     // exclusive scan in this order).  The run is written COOPERATIVELY: instance j of the wave goes to lane j & 63 of round j >> 6, which
@@ -537,141 +539,11 @@ __global__ void __launch_bounds__(BLOCK) ranges_kernel(int R_cap, const uint32_t
     if (i == R - 1) ranges[2 * cur + 1] = (uint32_t)R;
 }
 
-// One workgroup behind the cull: (a) counting sort of the n work items by descending size: order[] = item ids, largest first -- 1024
-// size buckets, one per count below 1023 (exact order there; everything longer shares the first bucket -- those waves start first
-// anyway); (b) exclusive prefix sums, in index order, of the counts (the first gradient row of every sub-tile) and of seg_slots(count)
-// (its first dumped-state slot), and their totals (device + tagged host copy).  Every wave owns a contiguous chunk of the items and walks
-// it 64 at a time; the counts are read ONCE (PIT rounds in registers) and serve the histogram, the wave totals, the prefixes and the
-// scatter: one global latency and three barriers from the first load to the last store.
-__global__ void __launch_bounds__(1024) order_desc_kernel(const uint32_t* __restrict__ counts, int n,
-                                                          uint32_t* __restrict__ order, uint32_t* __restrict__ prefix,
-                                                          uint32_t* __restrict__ slot_prefix, uint32_t* __restrict__ total,
-                                                          unsigned long long* __restrict__ host_total, uint32_t host_tag,
-                                                          uint32_t cap_R, long long cap_slots, uint32_t magic, int order_n) {
-    __shared__ uint32_t hist[1024];
-    __shared__ uint32_t wsum[16];
-    __shared__ unsigned long long wsum2[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    hist[t] = 0;
-    const int chunk = ((n + 15) / 16 + 63) / 64 * 64;   // items per wave
-    const int c0 = wave * chunk, c1 = min(n, c0 + chunk);
-    constexpr int PIT = 12;   // chunk rounds held in registers (n <= 12288 = an 880 x 880 image; beyond that the rounds re-read the counts)
-    const bool in_regs = chunk <= PIT * 64;
-    uint32_t cv[PIT];
-#pragma unroll
-    for (int r = 0; r < PIT; r++) cv[r] = (in_regs && c0 + r * 64 + lane < c1) ? counts[c0 + r * 64 + lane] : 0u;   // all loads in flight together
-    auto both = [](uint32_t c) { return (unsigned long long)c | ((unsigned long long)seg_slots(c) << 32); };   // low word: counts, high word: slots
-    __syncthreads();   // (hist is zero; the loads are still in flight)
-    // ---- pass 1: size histogram + wave totals.  Items of size 0 (most of an image is usually empty) all land in the last bucket: they
-    // are counted with one atomic per wave and round instead of one per item
-    unsigned long long wtot = 0;
-    auto count1 = [&](int i0, uint32_t len) {
-        const bool valid = i0 + lane < c1;
-        const unsigned long long zero = __ballot(valid && len == 0u);
-        if (valid && len != 0u) atomicAdd(&hist[1023u - min(1023u, len)], 1u);
-        if (lane == 0 && zero) atomicAdd(&hist[1023], (uint32_t)__popcll(zero));
-        wtot += both(valid ? len : 0u);
-    };
-    if (in_regs) {
-#pragma unroll
-        for (int r = 0; r < PIT; r++)
-            if (c0 + r * 64 < c1) count1(c0 + r * 64, cv[r]);   // (uniform)
-    } else {
-        for (int i0 = c0; i0 < c1; i0 += 64) count1(i0, i0 + lane < c1 ? counts[i0 + lane] : 0u);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wtot += (unsigned long long)__shfl_xor((long long)wtot, d);
-    if (lane == 0) wsum2[wave] = wtot;
-    __syncthreads();
-    // ---- exclusive scan of hist over the 1024 threads -> bucket cursors
-    const uint32_t hv = hist[t];
-    uint32_t incl = hv;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    // ---- prefixes in index order (between the two barriers of the bucket scan: they only need wsum2)
-    // inclusive wave scans on the VALU (DPP row shifts + row broadcasts; a __shfl_up scan is 6 LDS permutes per word)
-    auto scan32 = [](uint32_t v) {
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-        return v;
-    };
-    auto wave_incl = [&](unsigned long long v) {   // (two independent 32-bit scans: neither half overflows into the other)
-        return (unsigned long long)scan32((uint32_t)v) | ((unsigned long long)scan32((uint32_t)(v >> 32)) << 32);
-    };
-    unsigned long long run = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) { const unsigned long long x = wsum2[w]; run += w < wave ? x : 0ull; all += x; }
-    if (prefix || slot_prefix) {
-        auto round = [&](int i0, uint32_t c) {
-            const int i = i0 + lane;
-            const unsigned long long v = both(i < c1 ? c : 0u), inc = wave_incl(v);
-            if (i < c1) {
-                if (prefix) prefix[i] = (uint32_t)(run + inc - v);
-                if (slot_prefix) slot_prefix[i] = (uint32_t)((run + inc - v) >> 32);
-            }
-            run += ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)inc, 63)) |
-                   ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(inc >> 32), 63) << 32);
-        };
-        if (in_regs) {
-#pragma unroll
-            for (int r = 0; r < PIT; r++)
-                if (c0 + r * 64 < c1) round(c0 + r * 64, cv[r]);   // (uniform)
-        } else {
-            for (int i0 = c0; i0 < c1; i0 += 64) round(i0, i0 + lane < c1 ? counts[i0 + lane] : 0u);
-        }
-    }
-    if (t == 0) {
-        if (total) {
-            total[1] = (uint32_t)all; total[2] = (uint32_t)(all >> 32);
-            // the capacities the forward laid the binning blob out for: the image blob describes its view by itself (api.hip view_from_blob)
-            total[3] = magic; total[4] = cap_R; total[5] = (uint32_t)(unsigned long long)cap_slots; total[6] = (uint32_t)((unsigned long long)cap_slots >> 32);
-        }
-        // the host's copy: {sum, tag of this forward} as 8-byte stores into pinned host memory -- no copy operation and no event on the
-        // stream; the host recognises the values by their tag (api.hip view_lookup)
-        if (host_total) {
-            // (third word: the number of non-empty items -- composite waves with work; the forward picks its occupancy variant from it)
-            __hip_atomic_store(host_total + 2, ((unsigned long long)host_tag << 32) | (unsigned long long)((uint32_t)n - hist[1023]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_total, ((unsigned long long)host_tag << 32) | (all & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_total + 1, ((unsigned long long)host_tag << 32) | (all >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wave; w++) woff += wsum[w];
-    hist[t] = woff + incl - hv;   // first output position of bucket t
-    __syncthreads();
-    // ---- pass 2: scatter (items of equal size in arrival order; the zero-size items at the very end)
-    auto place = [&](int i0, uint32_t len) {
-        const int i = i0 + lane;
-        const bool valid = i < c1, z = valid && len == 0u;
-        const unsigned long long zero = __ballot(z);
-        if (valid && len != 0u) order[atomicAdd(&hist[1023u - min(1023u, len)], 1u)] = (uint32_t)i;
-        uint32_t zbase = 0;
-        if (lane == 0 && zero) zbase = atomicAdd(&hist[1023], (uint32_t)__popcll(zero));
-        zbase = (uint32_t)__shfl((int)zbase, 0);
-        if (z) order[zbase + (uint32_t)__popcll(zero & lt_mask)] = (uint32_t)i;
-    };
-    if (in_regs) {
-#pragma unroll
-        for (int r = 0; r < PIT; r++)
-            if (c0 + r * 64 < c1) place(c0 + r * 64, cv[r]);   // (uniform)
-    } else {
-        for (int i0 = c0; i0 < c1; i0 += 64) place(i0, i0 + lane < c1 ? counts[i0 + lane] : 0u);
-    }
-    for (int i = n + t; i < order_n; i += 1024) order[i] = ORDER_NONE;   // padding (common.hpp ORDER_NONE)
-}
-
-// The same products for launches that fill the machine several times over (api.hip high_fill): ONE LONGEST-FIRST LIST PER XCD, and one
-// workgroup per XCD to build it.  Workgroups are dealt to the eight XCDs round-robin (workgroup b of the composite runs on XCD b & 7), and
+// Dispatch order, first gradient row and first state slot of every sub-tile, and the view's totals, for launches that fill the machine
+// several times over (api.hip high_fill; at low fill the cull publishes all of it itself: common.hpp DISP_NCLS): counting sorts of the
+// sub-tiles by descending count -- 1024 size buckets, one per count below 1023, everything longer shares the first -- exclusive prefix
+// sums, in index order, of the counts and of seg_slots(count), and their sums (device + tagged host copy).  ONE LONGEST-FIRST LIST PER
+// XCD, and one workgroup per XCD to build it.  Workgroups are dealt to the eight XCDs round-robin (workgroup b of the composite runs on XCD b & 7), and
 // each XCD has its own 4 MiB L2: with one global order the ~3 sub-tiles that gather a splat's record and vfeature rows run on three
 // different XCDs, and each L2 fetches them again.  Here the image is cut into blocks of 4 x 4 tiles, block (bx, by) belongs to XCD
 // (bx + 3 by) & 7 (common.hpp xcd_of_tile); workgroup c counting-sorts the sub-tiles of XCD c by descending count and writes its j-th item
@@ -784,11 +656,9 @@ __global__ void __launch_bounds__(1024) order_xcd_kernel(const uint32_t* __restr
 
 void launch_order_desc(const uint32_t* counts, int n, uint32_t* order, uint32_t* prefix, uint32_t* slot_prefix, uint32_t* totals,
                        unsigned long long* host_totals, uint32_t host_tag, uint32_t cap_R, long long cap_slots, uint32_t magic, int gx, int order_n,
-                       bool per_xcd, hipStream_t s) {
-    if (per_xcd) hipLaunchKernelGGL(order_xcd_kernel, dim3(8), dim3(1024), 0, s, counts, n, order, prefix, slot_prefix, totals, host_totals,
-                                    host_tag, cap_R, cap_slots, magic, gx, order_n);
-    else hipLaunchKernelGGL(order_desc_kernel, dim3(1), dim3(1024), 0, s, counts, n, order, prefix, slot_prefix, totals, host_totals,
-                            host_tag, cap_R, cap_slots, magic, order_n);
+                       hipStream_t s) {
+    hipLaunchKernelGGL(order_xcd_kernel, dim3(8), dim3(1024), 0, s, counts, n, order, prefix, slot_prefix, totals, host_totals,
+                       host_tag, cap_R, cap_slots, magic, gx, order_n);
 }
 
 template <int ITEMS>
@@ -832,10 +702,10 @@ void launch_offsets_scan(const uint32_t* tiles, const uint32_t* order, uint32_t*
 
 void launch_emit(int P, const uint32_t* order, const uint32_t* tiles, const uint32_t* offsets, float* rec,
                  const int32_t* radii, int gx, int gy, uint32_t* tile_keys, uint32_t* vals, int cap, uint32_t* ranges,
-                 uint32_t* seg_count, uint32_t* sort_table, const uint32_t* span, hipStream_t s) {
+                 uint32_t* seg_count, uint32_t* sort_table, const uint32_t* span, uint32_t* disp_ctr, hipStream_t s) {
     hipLaunchKernelGGL(emit_kernel, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, P, order, tiles, offsets, rec,
                        radii, gx, gy, tile_keys, vals, (uint32_t)cap, ranges, 2 * gx * gy + (gx * gy + 255) / 256 * SEG_BLOCK_STRIDE, seg_count,
-                       radix_gtot(sort_table, cap), (int)radix_gtot_words(cap), span);
+                       radix_gtot(sort_table, cap), (int)radix_gtot_words(cap), span, disp_ctr);
 }
 
 void launch_tile_sort12(uint32_t* const key[2], uint32_t* const val[2], int n, const uint32_t* n_dev, uint32_t* table, uint32_t* ranges, int T,

@@ -111,10 +111,11 @@ inline GeomLayout geom_layout(char* base, int P) {
     return g;
 }
 
-// Dispatch order of the composite forward's waves (ImageLayout::sub_order, written by order_desc_kernel): workgroup b takes sub-tile
-// sub_order[b]; ORDER_NONE = padding (the workgroup exits).  Two orders exist (binning.hip): one global longest-first list, or one
-// longest-first list per XCD, interleaved (entry 8 j + c = the j-th item of XCD c), where an XCD owns the image blocks of 4 x 4 tiles
-// with (bx + 3 by) & 7 == c.  order_entries() = entries of the padded per-XCD form (>= 4 T): 8 x the longest XCD list.
+// Dispatch order of the composite forward's waves.  Two forms exist: at low fill the buckets the cull fills itself (DISP_NCLS below),
+// and for launches of many rounds of waves the list ImageLayout::sub_order, written by order_xcd_kernel (binning.hip): workgroup b takes
+// sub-tile sub_order[b]; ORDER_NONE = padding (the workgroup exits).  The list is one longest-first list per XCD, interleaved (entry
+// 8 j + c = the j-th item of XCD c), where an XCD owns the image blocks of 4 x 4 tiles with (bx + 3 by) & 7 == c.  order_entries() =
+// entries of the padded per-XCD form (>= 4 T): 8 x the longest XCD list; the composite's grid on both paths.
 constexpr uint32_t ORDER_NONE = 0xffffffffu;
 #if defined(__HIPCC__)
 __host__ __device__
@@ -165,17 +166,32 @@ struct ImageLayout {
     uint32_t* seg_block; // [ceil(T / 256)][SEG_BLOCK_STRIDE] live backward segments per block of 256 tiles and length class (summed by the
                          // forward; directly behind ranges)
     uint32_t* sub_total; // [4*T] #entries of each 8x8 sub-tile's compact candidate list (written by the cull kernel)
-    uint32_t* sub_order; // [order_entries] sub-tiles sorted by descending candidate count (heaviest work is dispatched first), see ORDER_NONE
+    uint32_t* sub_order; // [order_entries] high fill: sub-tiles sorted by descending candidate count (heaviest work is dispatched first), see ORDER_NONE
     uint32_t* sub_count; // [4*T] #candidates the forward composite consumed before every pixel was done (<= sub_total)
     uint32_t* sub_ndump; // [4*T] #segment-boundary states the forward dumped for the sub-tile (see SEG)
-    uint32_t* sub_pair_base; // [4*T] exclusive prefix of sub_total over the sub-tiles: first gradient row of a sub-tile's candidates
-    uint32_t* sub_slot_base; // [4*T] exclusive prefix of seg_slots(sub_total): first dumped-state slot of a sub-tile (BinLayout::seg_state)
+    uint32_t* sub_pair_base; // [4*T] first gradient row of a sub-tile's candidates: compact and private, in index order (high fill) or in the
+                             // order the cull's workgroups finished (DISP_NCLS)
+    uint32_t* sub_slot_base; // [4*T] the same for seg_slots(sub_total): first dumped-state slot of a sub-tile (BinLayout::seg_state)
     uint32_t* counters;  // [8]: [0] = number of live backward segments (entries of BinLayout::seg_list); [1] = sum of sub_total (pairs);
                          // [2] = sum of seg_slots(sub_total) (state slots); [3] = magic, [4] = instance capacity, [5..6] = state-slot
                          // capacity (int64; -1: worst case) the forward laid the binning blob out for (api.hip view_from_blob)
+    uint32_t* disp_ctr;  // [DISP_NCLS][DISP_SHARDS] entries of the dispatch buckets, then the 64-bit allocation word (see DISP_NCLS)
+    uint32_t* disp_item; // [DISP_NCLS * DISP_SHARDS][order_entries / 8] sub-tile ids of the dispatch buckets
     size_t ncontrib_off;
     size_t bytes;
 };
+// Dispatch buckets of the composite forward at low fill (RenderArgs::queue_order): the cull itself publishes the longest-first order, no
+// kernel between it and the composite.  A cull workgroup appends every NON-EMPTY sub-tile of its tile to the bucket of its size class --
+// descending and linear in the candidate count, DISP_STEP counts per class, everything beyond the range shares class 0 (those waves start
+// first anyway) -- with one returning atomic on the class counter of its XCD's shard (work id & 7: a small-count class would otherwise
+// collect many hundreds of hits on one word) and one store into the shard's slice; one lane per non-empty tile allocates the tile's
+// gradient rows and state slots from ONE 64-bit word (pairs low, slots high) and writes the eight bases as running sums inside the tile:
+// placement follows the order in which the cull's workgroups finish, every consumer goes through sub_pair_base / sub_slot_base.  Composite
+// wave `rank` finds its sub-tile in class-major, shard, arrival order (dispatch_item); the waves behind the non-empty count write the
+// pixels of the empty sub-tiles (dispatch_idle).  The final value of the allocation word is the two totals.  Counters and word are zeroed
+// by the emit kernel of the same launch sequence.
+constexpr int DISP_NCLS = 64, DISP_SHARDS = 8, DISP_STEP = 16;
+constexpr int DISP_CTR_WORDS = DISP_NCLS * DISP_SHARDS + 2;   // counters + the allocation word (8-byte aligned behind them)
 inline ImageLayout image_layout(char* base, int W, int H) {
     ImageLayout im;
     size_t off = 0;
@@ -195,6 +211,8 @@ inline ImageLayout image_layout(char* base, int W, int H) {
     im.sub_pair_base = (uint32_t*)take(T * 4 * 4);
     im.sub_slot_base = (uint32_t*)take(T * 4 * 4);
     im.counters = (uint32_t*)take(32);
+    im.disp_ctr = (uint32_t*)take(DISP_CTR_WORDS * 4);
+    im.disp_item = (uint32_t*)take(order_entries((W + TILE - 1) / TILE, (H + TILE - 1) / TILE) * DISP_NCLS * 4);
     im.bytes = off;
     return im;
 }
@@ -224,7 +242,7 @@ inline size_t grad_scratch_bytes(int cap, size_t rows, int S, int VS) {   // rev
 // (transmittance there, and "everything behind" = (final - prefix) / T) instead of from the end of the list.
 // State slots are COMPACT (round 4): a sub-tile whose list has `total` candidates dumps at most total / SEG boundary states + the final
 // one, and none at all below SEG candidates -- seg_slots(total) -- and its first slot is the exclusive prefix of that over the
-// sub-tiles (ImageLayout::sub_slot_base, a by-product of order_desc_kernel); slot of (sub-tile, segment k) = sub_slot_base + k.
+// sub-tiles (ImageLayout::sub_slot_base, allocated by the cull or by order_xcd_kernel); slot of (sub-tile, segment k) = sub_slot_base + k.
 // After the forward composite seg_build_kernel lists the live segments -- seg_list (compact ids) and seg_desc (everything a
 // backward wave needs to start: SegDesc) -- LONGEST FIRST: class 0 = full segments (SEG candidates), classes 1..4 = the
 // partial last segments of the sub-tiles by length quarter; tile order inside a class.  The backward's waves take the list
@@ -401,6 +419,11 @@ struct RenderArgs {
     float *out_color, *out_normal, *out_depth, *out_opacity, *out_feature, *out_vfeature, *out_weights;
     float *zero_a, *zero_b;   // [3,H,W] planes the cull pass clears (rgss pseudo normal / surface xyz when not computed), or null
     uint8_t* needed;          // [P] or null: contrib_prepass_kernel marks every Gaussian that receives a blend weight
+    // dispatch order (see DISP_NCLS): 1 = the cull's buckets (disp_ctr / disp_item), 0 = the list sub_order of order_xcd_kernel
+    int queue_order; uint32_t* disp_ctr; uint32_t* disp_item;
+    // queue_order: wave 0 of the first kernel behind the cull (publish != 0) stores the view's totals -- counters[1..6] of the image blob
+    // (seg_count + 1 ..) and the tagged host words, as order_xcd_kernel does on the other path
+    int publish; uint32_t pub_tag, pub_cap_R, pub_magic; long long pub_cap_slots; unsigned long long* pub_host;
 };
 
 struct RenderBwdArgs {
@@ -459,26 +482,30 @@ void launch_radix_sort(uint32_t* const key[2], uint32_t* const val[2], int n, co
 void launch_offsets_scan(const uint32_t* tiles, const uint32_t* order, uint32_t* offsets, uint32_t* scan_tmp, int n,
                          uint32_t* total_out, const uint32_t* key_top, int n_key_top, const uint32_t* violation,
                          unsigned long long* host_out, uint32_t host_tag, hipStream_t s);
-// also clears ranges[2*gx*gy] + the per-tile-block segment counts behind it, the live-segment counter and the group totals of the tile sort's table (`sort_table`,
-// sized for `cap` elements)
+// also clears ranges[2*gx*gy] + the per-tile-block segment counts behind it, the live-segment counter, the group totals of the tile sort's table (`sort_table`,
+// sized for `cap` elements) and the cull's dispatch buckets (`disp_ctr`: ImageLayout::disp_ctr, DISP_CTR_WORDS words)
 void launch_emit(int P, const uint32_t* order, const uint32_t* tiles, const uint32_t* offsets, float* rec,
                  const int32_t* radii, int gx, int gy, uint32_t* tile_keys, uint32_t* vals, int cap, uint32_t* ranges,
-                 uint32_t* seg_count, uint32_t* sort_table, const uint32_t* span, hipStream_t s);   // span: GeomLayout::counters + 3
+                 uint32_t* seg_count, uint32_t* sort_table, const uint32_t* span, uint32_t* disp_ctr, hipStream_t s);   // span: GeomLayout::counters + 3
 void launch_ranges(int R, const uint32_t* R_dev, const uint32_t* tile_keys, uint32_t* ranges, int T, hipStream_t s);
 // single-pass stable counting sort of (tile id, value) pairs for T <= TS12_BINS tiles: slot 0 -> slot 1; writes ranges[2 T] (zero for empty
 // tiles, like identifyTileRanges); table: tile12_table_words(n)
 void launch_tile_sort12(uint32_t* const key[2], uint32_t* const val[2], int n, const uint32_t* n_dev, uint32_t* table, uint32_t* ranges, int T,
                         hipStream_t s);
+// high-fill launches (one longest-first list per XCD; at low fill the cull publishes the order itself: DISP_NCLS):
 // order[] = item ids sorted by descending counts[] (longest-processing-time-first dispatch of the composite waves); also
 // prefix[i] = exclusive prefix sum of counts[], slot_prefix[i] = the same of seg_slots(counts[]), totals[1] / totals[2] = the two sums,
 // host_totals[0] / [1] = host_tag << 32 | sum in pinned host memory (any of them may be null)
 // totals[3..6] = {magic, cap_R, cap_slots lo, hi}: the capacities of the launch sequence, kept in the image blob
-// gx: tiles per image row; order_n: entries of order[] (>= n; the rest is padded with ORDER_NONE); per_xcd: one longest-first list per XCD
+// gx: tiles per image row; order_n: entries of order[] (>= n; the rest is padded with ORDER_NONE)
 void launch_order_desc(const uint32_t* counts, int n, uint32_t* order, uint32_t* prefix, uint32_t* slot_prefix, uint32_t* totals,
                        unsigned long long* host_totals, uint32_t host_tag, uint32_t cap_R, long long cap_slots, uint32_t magic, int gx, int order_n,
-                       bool per_xcd, hipStream_t s);
-// per-tile cull of the depth-ordered splat lists against the four 8x8 sub-tiles -> sub_list, sub_total
+                       hipStream_t s);
+// per-tile cull of the depth-ordered splat lists against the four 8x8 sub-tiles -> sub_list, sub_total; queue_order: also the dispatch
+// buckets and sub_pair_base / sub_slot_base
 void launch_cull(const RenderArgs& a, hipStream_t s);
+// queue_order: one wave that stores the view's totals (RenderArgs::publish) when no composite kernel follows the cull
+void launch_dispatch_publish(const RenderArgs& a, hipStream_t s);
 // fused shading: needed[id] = 1 for every surfel that receives a blend weight in this view (the composite's transmittance walk alone)
 void launch_contrib_prepass(const RenderArgs& a, hipStream_t s);
 // tile-ordered list of the live backward segments (seg_list, seg_desc, seg_count) from the forward's sub_count / sub_ndump; also zeroes
@@ -547,6 +574,138 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// inclusive wave64 scan on the VALU (DPP row shifts + row broadcasts); all 64 lanes must be active
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
+    return v;
+}
+
+// ---- dispatch order of the composite waves (see DISP_NCLS) ----
+__device__ __forceinline__ uint32_t disp_class(uint32_t count) {   // count >= 1
+    return (uint32_t)(DISP_NCLS - 1) - min((uint32_t)(DISP_NCLS - 1), (count - 1u) / (uint32_t)DISP_STEP);
+}
+// The cull's part: a workgroup that has counted the four lists of `tile` (c[], uniform) calls this with its threads 0..3.
+__device__ __forceinline__ void dispatch_publish_tile(const RenderArgs& a, int tile, uint32_t shard, const uint32_t c[4], int t) {
+    const uint32_t slice = (uint32_t)a.order_n >> 3;
+    const uint32_t mine = t == 0 ? c[0] : t == 1 ? c[1] : t == 2 ? c[2] : c[3];
+    if (mine != 0u) {
+        const uint32_t b = disp_class(mine) * (uint32_t)DISP_SHARDS + shard;
+        const uint32_t pos = atomicAdd(a.disp_ctr + b, 1u);
+        if (pos < slice) a.disp_item[(size_t)b * slice + pos] = (uint32_t)(4 * tile + t);   // (a shard's sub-tiles never exceed its slice)
+    }
+    if (t == 0 && (c[0] | c[1] | c[2] | c[3]) != 0u) {
+        unsigned long long inc[4], tot = 0;
+#pragma unroll
+        for (int w = 0; w < 4; w++) { inc[w] = tot; tot += (unsigned long long)c[w] | ((unsigned long long)seg_slots(c[w]) << 32); }
+        const unsigned long long base = atomicAdd(reinterpret_cast<unsigned long long*>(a.disp_ctr + DISP_NCLS * DISP_SHARDS), tot);
+        reinterpret_cast<uint4*>(a.sub_pair_base)[tile] = make_uint4((uint32_t)(base + inc[0]), (uint32_t)(base + inc[1]),
+                                                                     (uint32_t)(base + inc[2]), (uint32_t)(base + inc[3]));
+        reinterpret_cast<uint4*>(a.sub_slot_base)[tile] = make_uint4((uint32_t)((base + inc[0]) >> 32), (uint32_t)((base + inc[1]) >> 32),
+                                                                     (uint32_t)((base + inc[2]) >> 32), (uint32_t)((base + inc[3]) >> 32));
+    }
+}
+// The sub-tile of composite wave `rank` (uniform; one wave per workgroup).  queue_order: lane l sums the counters of class l, a scan gives
+// the class bases, a ballot the class of the rank, the class's shard counters its slice, one more load the id.  ORDER_NONE: no sub-tile with
+// candidates is left for this wave -- *n_ne = the number of non-empty sub-tiles, the wave is idle wave rank - *n_ne (dispatch_idle).
+// On the list path (*n_ne = 0xffffffff) ORDER_NONE is padding.
+__device__ __forceinline__ uint32_t dispatch_item(const RenderArgs& a, uint32_t rank, int lane, uint32_t* n_ne) {
+    *n_ne = 0xffffffffu;
+    if (!a.queue_order) return a.sub_order[rank];
+    static_assert(DISP_NCLS == 64 && DISP_SHARDS == 8, "one lane per class, two 16-byte loads per lane");
+    const uint4 x = reinterpret_cast<const uint4*>(a.disp_ctr)[2 * lane], y = reinterpret_cast<const uint4*>(a.disp_ctr)[2 * lane + 1];
+    const uint32_t cnt[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+    const uint32_t s = ((x.x + x.y) + (x.z + x.w)) + ((y.x + y.y) + (y.z + y.w));
+    const uint32_t incl = wave_incl_scan_u32(s);
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    *n_ne = n;
+    if (a.publish && rank == 0u && lane == 0) {   // the view's totals (device + tagged host copy), once per launch sequence
+        const unsigned long long all = *reinterpret_cast<const unsigned long long*>(a.disp_ctr + DISP_NCLS * DISP_SHARDS);
+        uint32_t* total = a.seg_count;   // (ImageLayout::counters)
+        total[1] = (uint32_t)all; total[2] = (uint32_t)(all >> 32);
+        total[3] = a.pub_magic; total[4] = a.pub_cap_R;
+        total[5] = (uint32_t)(unsigned long long)a.pub_cap_slots; total[6] = (uint32_t)((unsigned long long)a.pub_cap_slots >> 32);
+        if (a.pub_host) {
+            const unsigned long long tag = (unsigned long long)a.pub_tag << 32;
+            __hip_atomic_store(a.pub_host + 2, tag | (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(a.pub_host, tag | (all & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(a.pub_host + 1, tag | (all >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    if (rank >= n) return ORDER_NONE;
+    const int c = (int)__builtin_ctzll(__ballot(incl > rank));
+    uint32_t off = rank - (uint32_t)__builtin_amdgcn_readlane((int)(incl - s), c);
+    uint32_t sh = 0;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < DISP_SHARDS; k++) {
+        const uint32_t ck = (uint32_t)__builtin_amdgcn_readlane((int)cnt[k], c);
+        if (!found) {
+            if (off < ck) found = true;
+            else { off -= ck; sh = (uint32_t)k + 1u; }
+        }
+    }
+    const uint32_t slice = (uint32_t)a.order_n >> 3;
+    return a.disp_item[(size_t)((uint32_t)c * (uint32_t)DISP_SHARDS + min(sh, (uint32_t)DISP_SHARDS - 1u)) * slice + min(off, slice - 1u)];
+}
+
+// the result of a pixel nothing is blended into (forward.cu:665-700 with an empty list)
+__device__ __forceinline__ void write_background(const RenderArgs& a, size_t pid, size_t N_) {
+    const float T = (float)(1 - 0.000001);   // forward.cu:671
+    a.final_T[pid] = T; a.final_D[pid] = 0.f; a.n_contrib[pid] = 0;
+    a.out_color[pid] = T * a.bg[0]; a.out_color[N_ + pid] = T * a.bg[1]; a.out_color[2 * N_ + pid] = T * a.bg[2];
+    for (int ch = 0; ch < a.S; ch++) a.out_feature[ch * N_ + pid] = 0.f;
+    for (int ch = 0; ch < a.VS / 4; ch++) a.out_vfeature[ch * N_ + pid] = 0.f;
+    a.out_normal[pid] = 0.f; a.out_normal[N_ + pid] = 0.f; a.out_normal[2 * N_ + pid] = 0.f;
+    a.out_depth[pid] = cfg_flag(a.cfg, 1) ? 0.f / (1.f - T) : 0.f + T * 10.f;
+    a.out_opacity[pid] = 1.f - T;
+}
+__device__ __forceinline__ void write_zero_planes(const RenderArgs& a, size_t pid, size_t N_) {   // planes this call leaves at zero
+    if (a.zero_a) { a.zero_a[pid] = 0.f; a.zero_a[N_ + pid] = 0.f; a.zero_a[2 * N_ + pid] = 0.f; }
+    if (a.zero_b) { a.zero_b[pid] = 0.f; a.zero_b[N_ + pid] = 0.f; a.zero_b[2 * N_ + pid] = 0.f; }
+}
+
+// Idle composite wave `idle` of `E` (= grid - non-empty sub-tiles >= empty sub-tiles): the sub-tiles idle, idle + E, ... without a
+// candidate take no atomic in the cull and have no wave of their own; their pixels are the background.  64 sub-tiles per round, one per
+// lane, four rounds of loads in flight; at low fill E exceeds 4 T / 2 and a wave checks one or two, on a full image a few waves scan
+// everything next to the real work.  What the cull has written already (run-time widths: the empty TILES) is left alone.
+__device__ __forceinline__ void dispatch_idle(const RenderArgs& a, uint32_t idle, uint32_t E, int lane) {
+    if (a.dump_only) return;
+    const uint32_t n = (uint32_t)(4 * a.gx * a.gy);
+    const size_t N_ = (size_t)a.W * a.H;
+    constexpr int U = 4;
+    for (uint32_t j0 = idle; j0 < n; j0 += (uint32_t)(64 * U) * E) {
+        uint32_t tot[U];
+        uint2 rr[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t j = j0 + ((uint32_t)(64 * u) + (uint32_t)lane) * E;
+            const bool valid = j < n;
+            tot[u] = valid ? a.sub_total[j] : 1u;
+            rr[u] = valid ? reinterpret_cast<const uint2*>(a.ranges)[j >> 2] : make_uint2(0u, 1u);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const bool empty_tile = rr[u].x == rr[u].y;
+            unsigned long long todo = __ballot(empty_tile ? a.bg_in_render != 0 : tot[u] == 0u);
+            while (todo) {
+                const int l = (int)__builtin_ctzll(todo);
+                todo &= todo - 1ull;
+                const uint32_t sid = j0 + ((uint32_t)(64 * u) + (uint32_t)l) * E;
+                const int tile = (int)(sid >> 2), sub = (int)(sid & 3u);
+                const int px = (tile % a.gx) * TILE + (sub & 1) * 8 + (lane & 7), py = (tile / a.gx) * TILE + (sub >> 1) * 8 + (lane >> 3);
+                if (px < a.W && py < a.H) {
+                    write_background(a, (size_t)a.W * py + px, N_);
+                    if (a.bg_in_render) write_zero_planes(a, (size_t)a.W * py + px, N_);
+                }
+            }
+        }
+    }
 }
 #endif
 

@@ -10,7 +10,9 @@
 //     tile's four 8x8 pixel rectangles against the 1/255 alpha threshold (the per-splat part of the test is shared by
 //     the four rectangles, the header is gathered once instead of once per sub-tile).  Survivors are compacted in
 //     order (ballot + popcount in the wave, per-wave counts through LDS across the waves) into one list per sub-tile
-//     {Gaussian id, slot in the tile list}; forward and backward composite both consume these lists.
+//     {Gaussian id, slot in the tile list}; forward and backward composite both consume these lists.  At low fill the workgroup
+//     also enters its non-empty sub-tiles into the composite's dispatch buckets and allocates their gradient rows and state slots
+//     (common.hpp DISP_NCLS): no kernel between the cull and the composite.
 //   render_fwd_kernel: one wave64 per 8x8 sub-tile (one wave per workgroup, no barriers), sub-tiles dispatched by
 //     descending candidate count.  Candidates are staged CH at a time into LDS in the pair-interleaved layout of
 //     pairstage.hpp (16-byte gathers, all in flight together and issued one batch AHEAD) and consumed four at a time:
@@ -47,22 +49,6 @@ namespace {
 #endif
 constexpr int CT = CULL_THREADS, CNW = CT / 64;   // threads / waves of a cull workgroup (a tile's list is walked CT entries per round)
 
-// the result of a pixel nothing is blended into (forward.cu:665-700 with an empty list)
-__device__ __forceinline__ void write_background(const RenderArgs& a, size_t pid, size_t N_) {
-    const float T = (float)(1 - 0.000001);   // forward.cu:671
-    a.final_T[pid] = T; a.final_D[pid] = 0.f; a.n_contrib[pid] = 0;
-    a.out_color[pid] = T * a.bg[0]; a.out_color[N_ + pid] = T * a.bg[1]; a.out_color[2 * N_ + pid] = T * a.bg[2];
-    for (int ch = 0; ch < a.S; ch++) a.out_feature[ch * N_ + pid] = 0.f;
-    for (int ch = 0; ch < a.VS / 4; ch++) a.out_vfeature[ch * N_ + pid] = 0.f;
-    a.out_normal[pid] = 0.f; a.out_normal[N_ + pid] = 0.f; a.out_normal[2 * N_ + pid] = 0.f;
-    a.out_depth[pid] = cfg_flag(a.cfg, 1) ? 0.f / (1.f - T) : 0.f + T * 10.f;
-    a.out_opacity[pid] = 1.f - T;
-}
-__device__ __forceinline__ void write_zero_planes(const RenderArgs& a, size_t pid, size_t N_) {   // planes this call leaves at zero
-    if (a.zero_a) { a.zero_a[pid] = 0.f; a.zero_a[N_ + pid] = 0.f; a.zero_a[2 * N_ + pid] = 0.f; }
-    if (a.zero_b) { a.zero_b[pid] = 0.f; a.zero_b[N_ + pid] = 0.f; a.zero_b[2 * N_ + pid] = 0.f; }
-}
-
 __global__ void __launch_bounds__(CT) cull_kernel(const RenderArgs a) {
     __shared__ uint32_t wcnt[CNW][4];   // [wave][sub-tile] survivors of the current round
     // (the tiles are dealt to the XCDs in blocks of 4 x 4: a splat's tiles are culled on one XCD -- common.hpp xcd_tile_of_work)
@@ -82,6 +68,7 @@ __global__ void __launch_bounds__(CT) cull_kernel(const RenderArgs a) {
     if (len == 0) {
         // Empty tile: nothing will ever be blended here.  Run-time-width composite: the 256 threads write the background result of the
         // whole 16x16 tile (64-byte rows) and the four composite waves of the tile exit at once.
+        // (no candidates: the tile takes no dispatch entry, no gradient rows and no state slots -- common.hpp DISP_NCLS)
         if (t < 4) { a.sub_total[4 * tile + t] = 0u; a.sub_count[4 * tile + t] = 0u; a.sub_ndump[4 * tile + t] = 0u; }
         const int px = tx * TILE + (t & 15), py = ty * TILE + (t >> 4);
         if (!a.bg_in_render && t < 256 && px < a.W && py < a.H) write_background(a, (size_t)a.W * py + px, (size_t)a.W * a.H);
@@ -131,7 +118,20 @@ __global__ void __launch_bounds__(CT) cull_kernel(const RenderArgs a) {
         }
         __syncthreads();   // counts consumed before the next round overwrites them
     }
-    if (t < 4) a.sub_total[4 * tile + t] = t == 0 ? run[0] : t == 1 ? run[1] : t == 2 ? run[2] : run[3];
+    if (t < 4) {
+        const uint32_t mine = t == 0 ? run[0] : t == 1 ? run[1] : t == 2 ? run[2] : run[3];
+        a.sub_total[4 * tile + t] = mine;
+        // (a sub-tile without candidates has no composite wave of its own on the queue path: its counts are final here)
+        if (mine == 0u) { a.sub_count[4 * tile + t] = 0u; a.sub_ndump[4 * tile + t] = 0u; }
+        // dispatch entry of every non-empty sub-tile, gradient rows and state slots of the tile (shard = this workgroup's XCD)
+        if (a.queue_order) dispatch_publish_tile(a, tile, blockIdx.x & 7u, run, t);
+    }
+}
+
+// the view's totals for a launch sequence that ends behind the cull (api.hip: the sizing pass of a workload's first view)
+__global__ void __launch_bounds__(64) dispatch_publish_kernel(const RenderArgs a) {
+    uint32_t n_ne;
+    (void)dispatch_item(a, 0u, (int)threadIdx.x, &n_ne);
 }
 
 // ---- blend --------------------------------------------------------------------------------------------------
@@ -155,8 +155,12 @@ render_fwd_kernel(const RenderArgs a) {
     float* sP = reinterpret_cast<float*>(smem + PG::off_p);      // [PROWS][PS] blend-weight panel (MFMA A operand) / transposition tile
     constexpr int PS = PG::PS;
 
-    const uint32_t sid = a.sub_order[blockIdx.x];   // (grid = RenderArgs::order_n)
-    if (sid == ORDER_NONE) return;                  // padding of the per-XCD order (common.hpp)
+    uint32_t n_ne;
+    const uint32_t sid = dispatch_item(a, blockIdx.x, (int)threadIdx.x, &n_ne);   // (grid = RenderArgs::order_n)
+    if (sid == ORDER_NONE) {   // padding of the per-XCD order, or (the cull's buckets) a wave for the sub-tiles without candidates
+        if (a.queue_order) dispatch_idle(a, blockIdx.x - n_ne, gridDim.x - n_ne, (int)threadIdx.x);
+        return;
+    }
     const int tile = (int)(sid >> 2), sub = (int)(sid & 3u);
     const int tx = tile % a.gx, ty = tile / a.gx;
     const int lane = threadIdx.x;
@@ -493,8 +497,9 @@ __global__ void __launch_bounds__(64) contrib_prepass_kernel(const RenderArgs a)
     // one ds_read_b128 yields the aligned register pairs of TWO candidates and their alphas are packed fp32 instructions
     __shared__ __attribute__((aligned(16))) float sQ[2][32][12];
     __shared__ uint32_t sG[2][64];
-    const uint32_t sid = a.sub_order[blockIdx.x];
-    if (sid == ORDER_NONE) return;
+    uint32_t n_ne;
+    const uint32_t sid = dispatch_item(a, blockIdx.x, (int)threadIdx.x, &n_ne);
+    if (sid == ORDER_NONE) return;   // (padding, or no sub-tile with candidates left)
     const int tile = (int)(sid >> 2), sub = (int)(sid & 3u);
     const uint32_t r0 = a.ranges[2 * tile], r1 = a.ranges[2 * tile + 1];
     const int len = (int)(r1 - r0);
@@ -717,6 +722,10 @@ void launch_seg_build(const RenderArgs& a, void* clear, size_t clear_bytes, cons
 
 void launch_contrib_prepass(const RenderArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(contrib_prepass_kernel, dim3(a.order_n), dim3(64), 0, s, a);
+}
+
+void launch_dispatch_publish(const RenderArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(dispatch_publish_kernel, dim3(1), dim3(64), 0, s, a);
 }
 
 void launch_cull(const RenderArgs& a, hipStream_t s) {

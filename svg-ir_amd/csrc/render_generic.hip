@@ -51,7 +51,12 @@ __global__ void __launch_bounds__(64) render_fwd_generic_kernel(const RenderArgs
     extern __shared__ __attribute__((aligned(16))) float acc[];   // [(S + VC)][64] feature / vfeature accumulators
     const int S = a.S, VC = a.VS / 4;
     if ((int)blockIdx.x >= 4 * a.gx * a.gy) return;
-    const uint32_t sid = a.sub_order[blockIdx.x];
+    uint32_t n_ne;
+    const uint32_t sid = dispatch_item(a, blockIdx.x, (int)threadIdx.x, &n_ne);
+    if (sid == ORDER_NONE) {   // (a wave for the sub-tiles without candidates: common.hpp dispatch_idle)
+        if (a.queue_order) dispatch_idle(a, blockIdx.x - n_ne, gridDim.x - n_ne, (int)threadIdx.x);
+        return;
+    }
     const int tile = (int)(sid >> 2), sub = (int)(sid & 3u);
     const int tx = tile % a.gx, ty = tile / a.gx;
     const int lane = threadIdx.x;
