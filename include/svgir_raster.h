@@ -388,7 +388,10 @@ int svgir_resample_bilinear(const float* src, int32_t H, int32_t W, int32_t C, f
  *   training  (21): pbr | normal | base_color | roughness | diffuse | local_lights | visibility
  *   evaluation(27): pbr | normal | base_color | roughness | direct | indirect | lights | local_lights | visibility
  * (three planes per quantity; one-channel quantities are broadcast over the three background channels as in the
- * reference).  The backward maps dL/d(out) to dL/d(opacity, feature, vfeature); all outputs are overwritten. */
+ * reference).  The backward maps dL/d(out) to dL/d(opacity, feature, vfeature); all outputs are overwritten.
+ * Clamps behave as torch's: the opacity clamp passes its gradient AT opacity == 1e-5f (clamp_min: self >= min), and NaN inputs stay
+ * NaN through the opacity clamp and the sRGB clip (torch.clamp / clamp_min propagate NaN); a non-finite pixel affects no other pixel,
+ * forward or backward.  The same holds for svgir_unpack_rgss_* below. */
 int svgir_unpack_planes(int32_t training);
 int svgir_unpack_forward(int32_t W, int32_t H, int32_t training, const float* bg, const float* opacity, const float* feature,
                          const float* vfeature, float* out, void* stream);

@@ -9,7 +9,9 @@ Restates, in plain per-element math,
     F.interpolate(mode='bilinear', align_corners=False));
   * the image-space epilogue of `render_view` (gaussian_renderer/svgss.py:187-262): division by the rendered opacity,
     channel split, sRGB (`rgb_to_srgb`, utils/graphics_utils.py:198-215), compositing over the background;
-  * `depth2normal` (utils/image_utils.py:61-125);
+  * `depth2normal` (utils/image_utils.py:61-125), also in differentiable torch;
+  * the image-space tail of the stage-1 `render_view` (gaussian_renderer/render.py:107-114: features over the clamped opacity, masked
+    by num_contrib > 0, and the depth variance);
   * `ssim` + `F.l1_loss` as called on the rendered image (utils/loss_utils.py:21-64; svgss.py:281-289, render.py:150-151).
 Parity: PINNED -- tests/golden/{incident_dirs,lights,render_view}.npz hold inputs and outputs produced by running the
 reference's own functions (and its whole `render_view` with a recording stub rasterizer) in the authoring container
@@ -88,17 +90,25 @@ def resample_bilinear(img, out_h, out_w):
 
 
 # ---- f2: image-space epilogue ------------------------------------------------------------------------------------
+# The reference compares fp32 tensors against these two constants, i.e. against their fp32 roundings; the inputs of this stage are
+# fp32 values, so with the rounded thresholds an exact tie means the same here in fp64 as it does in the reference (float32(1e-5) lies
+# below the double 1e-5: unrounded, the oracle would clamp an opacity the reference passes through with its gradient).
+OPACITY_MIN = float(np.float32(1e-5))
+SRGB_KNEE = float(np.float32(0.0031308))
+
+
 def rgb_to_srgb(img, clip=True):
     img = np.asarray(img, dtype=np.float64)
-    out = np.where(img > 0.0031308, np.power(np.maximum(img, 0.0031308), 1.0 / 2.4) * 1.055 - 0.055, 12.92 * img)
+    with np.errstate(invalid="ignore"):
+        out = np.where(img > SRGB_KNEE, np.power(np.maximum(img, SRGB_KNEE), 1.0 / 2.4) * 1.055 - 0.055, 12.92 * img)
     return np.clip(out, 0.0, 1.0) if clip else out
 
 
 def unpack_svgss(opacity, feature, vfeature, bg, training):
     """svgss.py:187-246.  opacity [1,H,W], feature [S,H,W], vfeature [VS/4,H,W], bg [3] -> dict of images."""
     op = np.asarray(opacity, dtype=np.float64)
-    f = np.asarray(feature, dtype=np.float64) / np.maximum(op, 1e-5)
-    vf = np.asarray(vfeature, dtype=np.float64) / np.maximum(op, 1e-5)
+    f = np.asarray(feature, dtype=np.float64) / np.maximum(op, OPACITY_MIN)
+    vf = np.asarray(vfeature, dtype=np.float64) / np.maximum(op, OPACITY_MIN)
     bgc = np.asarray(bg, dtype=np.float64)[:, None, None]
 
     def over(r):
@@ -151,11 +161,11 @@ def unpack_svgss_torch(opacity, feature, vfeature, bg, training):
     import torch
 
     def srgb(img):
-        out = torch.where(img > 0.0031308, torch.pow(torch.clamp(img, min=0.0031308), 1.0 / 2.4) * 1.055 - 0.055, 12.92 * img)
+        out = torch.where(img > SRGB_KNEE, torch.pow(torch.clamp(img, min=SRGB_KNEE), 1.0 / 2.4) * 1.055 - 0.055, 12.92 * img)
         return out.clamp(0.0, 1.0)
 
-    f = feature / opacity.clamp_min(1e-5)
-    vf = vfeature / opacity.clamp_min(1e-5)
+    f = feature / opacity.clamp_min(OPACITY_MIN)
+    vf = vfeature / opacity.clamp_min(OPACITY_MIN)
     bgc = bg[:, None, None]
 
     def over(r):
@@ -176,6 +186,46 @@ def unpack_svgss_torch(opacity, feature, vfeature, bg, training):
     return res
 
 
+def depth2normal_torch(depth, mask, fovx, fovy, prcppoint=(0.5, 0.5)):
+    """depth2normal in differentiable torch (any dtype / device; the mask is `!= 0`, F.normalize's eps = 1e-12): torch.autograd of
+    this is the reference for the backward of the depth2normal kernel."""
+    import torch
+    d = depth[0]
+    m = (mask[0] != 0).to(d.dtype)
+    H, W = d.shape
+    k00 = H / (2 * math.tan(fovy / 2))
+    k11 = W / (2 * math.tan(fovx / 2))
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=d.dtype, device=d.device), torch.arange(W, dtype=d.dtype, device=d.device), indexing="ij")
+    ppx, ppy = float(prcppoint[0] * W), float(prcppoint[1] * H)     # (an fp32 principal point multiplies in fp32, as in depth2normal)
+    pos = torch.stack([(xs - ppx) * d / k00, (ys - ppy) * d / k11, d], dim=0)   # [3,H,W]
+    pad = lambda t: torch.nn.functional.pad(t[None], (1, 1, 1, 1), mode="replicate")[0]  # noqa: E731
+    p, mk = pad(pos), pad(m[None])
+    c = p[:, 1:-1, 1:-1] * mk[:, 1:-1, 1:-1]
+    u = (p[:, :-2, 1:-1] - c) * mk[:, :-2, 1:-1]
+    l_ = (p[:, 1:-1, :-2] - c) * mk[:, 1:-1, :-2]
+    b = (p[:, 2:, 1:-1] - c) * mk[:, 2:, 1:-1]
+    r = (p[:, 1:-1, 2:] - c) * mk[:, 1:-1, 2:]
+    cross = lambda a_, b_: torch.cross(a_, b_, dim=0)  # noqa: E731
+    n = cross(u, l_) + cross(r, u) + cross(b, r) + cross(l_, b)
+    return torch.nn.functional.normalize(n, dim=0, eps=1e-12) * mk[:, 1:-1, 1:-1]
+
+
+def unpack_rgss(num_contrib, opacity, depth, feature):
+    """render.py:107-114.  num_contrib [H,W] int, opacity / depth [1,H,W], feature [5,H,W] (normal 3, depth, depth^2) -> dict:
+    every feature plane / max(opacity, 1e-5) * (num_contrib > 0), and the depth variance E[d^2] - depth^2."""
+    op = np.asarray(opacity, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        x = np.asarray(feature, dtype=np.float64) / np.maximum(op, OPACITY_MIN) * (np.asarray(num_contrib) > 0)
+        var = x[4:5] - np.square(np.asarray(depth, dtype=np.float64))
+    return dict(feature_normal=x[0:3], feature_depth=x[3:4], feature_depth2=x[4:5], depth_var=var)
+
+
+def unpack_rgss_torch(num_contrib, opacity, depth, feature):
+    """The same as unpack_rgss in differentiable torch (any dtype / device)."""
+    x = feature / opacity.clamp_min(OPACITY_MIN) * (num_contrib > 0)
+    return dict(feature_normal=x[0:3], feature_depth=x[3:4], feature_depth2=x[4:5], depth_var=x[4:5] - depth.square())
+
+
 # ---- f2: image losses --------------------------------------------------------------------------------------------
 def ssim_window():
     """utils/loss_utils.py:21-23 `gaussian(11, 1.5)`: fp32 values, divided by their fp32 sum."""
@@ -183,14 +233,22 @@ def ssim_window():
     return (g / g.sum(dtype=np.float32)).astype(np.float64)
 
 
-def l1_ssim_torch(img1, img2):
+def l1_ssim_torch(img1, img2, keep_dtype=False):
     """(mean |img1 - img2|, mean SSIM map) in differentiable torch fp64 -- utils/loss_utils.py:44-61 with the 2-D window
-    written out (outer product of the 1-D one), zero padding, one depthwise convolution per windowed moment."""
+    written out (outer product of the 1-D one), zero padding, one depthwise convolution per windowed moment.
+    keep_dtype=True: everything in the dtype of img1, the window built as the reference builds it (the fp32 outer product of the
+    fp32 1-D window, used in ONE conv2d): with fp32 images this is the stand-in for the reference's own fp32 arithmetic."""
     import torch
-    a, b = img1.to(torch.float64), img2.to(torch.float64)
+    if keep_dtype:
+        a, b = img1, img2.to(img1.dtype)
+        g = torch.from_numpy(ssim_window().astype(np.float32)).to(a.device)
+        w2 = (g[:, None] * g[None, :]).to(a.dtype)
+    else:
+        a, b = img1.to(torch.float64), img2.to(torch.float64)
+        g = torch.from_numpy(ssim_window()).to(a.device)
+        w2 = g[:, None] * g[None, :]
     C = a.shape[0]
-    g = torch.from_numpy(ssim_window()).to(a.device)
-    w = (g[:, None] * g[None, :])[None, None].expand(C, 1, 11, 11)
+    w = w2[None, None].expand(C, 1, 11, 11)
 
     def blur(x):
         return torch.nn.functional.conv2d(x[None], w, padding=5, groups=C)[0]

@@ -25,15 +25,21 @@ namespace {
 enum PlaneKind { K_SRGB_OF_OVER = 0, K_PLAIN = 1, K_OVER_SRGB = 2, K_OVER_LIN = 3, K_SRGB = 4 };
 struct PlaneGroup { int kind, src, vf, n; };   // src: first source channel; vf: source is vfeature; n: source channels (1 or 3)
 
+// torch.clamp / clamp_min propagate NaN (fminf / fmaxf return the other operand): a NaN plane or opacity stays NaN in every result
+// it reaches, as in the reference, instead of turning into a valid-looking pixel.  Plain compares: false on NaN, so x passes through.
+__device__ __forceinline__ float clamp_min_nan(float x, float lo) { return x < lo ? lo : x; }
+__device__ __forceinline__ float clamp01_nan(float y) { return y < 0.f ? 0.f : (y > 1.f ? 1.f : y); }
+
 __device__ __forceinline__ float srgb(float x) {
-    const float y = x > 0.0031308f ? powf(fmaxf(x, 0.0031308f), 1.0f / 2.4f) * 1.055f - 0.055f : 12.92f * x;
-    return fminf(1.f, fmaxf(0.f, y));
+    const float y = x > 0.0031308f ? powf(x, 1.0f / 2.4f) * 1.055f - 0.055f : 12.92f * x;   // (NaN takes the linear branch: NaN)
+    return clamp01_nan(y);
 }
-// d srgb / dx (0 where the final clip to [0,1] is active)
+// d srgb / dx: 0 where the final clip to [0,1] is active -- and for a NaN argument, as torch.clamp's backward (its mask
+// min <= y <= max is false): the gradients of a NaN pixel stay confined to that pixel either way, the kernel being per-pixel
 __device__ __forceinline__ float dsrgb(float x) {
-    const float y = x > 0.0031308f ? powf(fmaxf(x, 0.0031308f), 1.0f / 2.4f) * 1.055f - 0.055f : 12.92f * x;
-    if (y < 0.f || y > 1.f) return 0.f;
-    return x > 0.0031308f ? (1.055f / 2.4f) * powf(fmaxf(x, 0.0031308f), 1.0f / 2.4f - 1.0f) : 12.92f;
+    const float y = x > 0.0031308f ? powf(x, 1.0f / 2.4f) * 1.055f - 0.055f : 12.92f * x;
+    if (!(y >= 0.f && y <= 1.f)) return 0.f;
+    return x > 0.0031308f ? (1.055f / 2.4f) * powf(x, 1.0f / 2.4f - 1.0f) : 12.92f;
 }
 
 template <bool TRAINING> struct Groups;
@@ -64,8 +70,8 @@ __global__ void __launch_bounds__(BLOCK) unpack_kernel(const UnpackArgs a) {
     if (i >= N) return;
     constexpr int S = G::S, VC = G::VC;
     const float o = a.opacity[i];
-    const bool clamped = !(o > 1e-5f);
-    const float inv = 1.f / fmaxf(o, 1e-5f);
+    const bool clamped = o < 1e-5f;                    // clamp_min passes the gradient AT the bound (torch: self >= min)
+    const float inv = 1.f / clamp_min_nan(o, 1e-5f);
     const float dinv = clamped ? 0.f : -inv * inv;     // d inv / d o
     const float bg[3] = {a.bg[0], a.bg[1], a.bg[2]};
     float d_o = 0.f;
@@ -267,8 +273,8 @@ __global__ void __launch_bounds__(BLOCK) unpack_rgss_kernel(int N, const int32_t
     if (i >= N) return;
     const float o = opacity[i];
     const float m = num_contrib[i] > 0 ? 1.f : 0.f;
-    const float inv = m / fmaxf(o, 1e-5f);
-    const float dinv = o > 1e-5f ? -inv / o : 0.f;
+    const float inv = m / clamp_min_nan(o, 1e-5f);
+    const float dinv = o < 1e-5f ? 0.f : -inv / o;     // the tie o == 1e-5f passes the gradient, like torch's clamp_min
     const float dep = depth[i];
     if (!BWD) {
 #pragma unroll

@@ -16,6 +16,14 @@ N.lib.svgir_l1_ssim_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c
                                          C.c_void_p, C.c_void_p, C.c_void_p]
 
 
+def _need_maps(dmaps):
+    """The forward keeps the derivative maps only when `image` requires grad; a backward without them was asked for the ground truth's
+    gradient alone, which the kernels do not compute (the reference's ssim would)."""
+    if dmaps is None:
+        raise RuntimeError("l1_ssim: only the rendered image is differentiable; the gradient w.r.t. the ground truth is not implemented "
+                           "(the image did not require grad in the forward)")
+
+
 class _L1Ssim(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, gt):
@@ -37,6 +45,7 @@ class _L1Ssim(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_l1, g_ssim):
         a, b, dmaps = ctx.saved_tensors
+        _need_maps(dmaps)
         Cc, H, W = a.shape[-3], a.shape[-2], a.shape[-1]
         out = torch.empty_like(a)
         # the upstream scalars stay on the device: a 2-float buffer {g_ssim, g_l1} the kernel reads (no blocking read-back)
@@ -79,6 +88,7 @@ class _L1SsimLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         a, b, dmaps = ctx.saved_tensors
+        _need_maps(dmaps)
         Cc, H, W = a.shape[-3], a.shape[-2], a.shape[-1]
         out = torch.empty_like(a)
         gdev = g.to(torch.float32).reshape(1).expand(2).contiguous()   # the upstream scalar stays on the device

@@ -122,9 +122,8 @@ def test_rgss_packing_and_unpacking_match_reference_render_view(built):
     wn = torch.randn(res["feature_normal"].shape, generator=torch.Generator().manual_seed(3)).to(dev)
     ((res["depth_var"] * wv).sum() + (res["feature_normal"] * wn).sum()).backward()
     ld = {k: ras[k].double().cpu().requires_grad_(True) for k in ("opacity", "depth", "feature")}
-    mask = (ras["num_contrib"] > 0).double().cpu()
-    xf = ld["feature"] / ld["opacity"].clamp_min(1e-5) * mask
-    ((((xf[4:5] - ld["depth"].square()) * wv.double().cpu()).sum()) + (xf[0:3] * wn.double().cpu()).sum()).backward()
+    ref = eo.unpack_rgss_torch(ras["num_contrib"].cpu(), ld["opacity"], ld["depth"], ld["feature"])
+    ((ref["depth_var"] * wv.double().cpu()).sum() + (ref["feature_normal"] * wn.double().cpu()).sum()).backward()
     for k in ("opacity", "depth", "feature"):
         _cmp("d_" + k, lv[k].grad, ld[k].grad.numpy(), tol=2e-5, flip_frac=1e-4)
     fovx, fovy = g["cam_fov"]

@@ -127,3 +127,62 @@ def test_l1_ssim_oracle_matches_the_reference_losses():
         ref = fx[f"{tag}_dssim"].astype(np.float64)
         assert np.abs(gs.numpy() - ref).max() <= 2e-4 * np.abs(ref).max(), tag    # (the reference's gradient is fp32 autograd)
         assert np.abs(gl.numpy() - fx[f"{tag}_dl1"]).max() <= 1e-9, tag
+
+
+def test_rgss_unpacking_matches_reference_render_view():
+    """render.py:107-114 on the stub rasterizer's buffers (tests/golden/render_view_rgss.npz): numpy and torch restatements."""
+    g = np.load(os.path.join(GOLD, "render_view_rgss.npz"))
+    res = eo.unpack_rgss(g["raster_num_contrib"], g["raster_opacity"], g["raster_depth"], g["raster_feature"])
+    np.testing.assert_allclose(res["depth_var"], g["res_depth_var"], rtol=2e-5, atol=2e-5)
+    tt = eo.unpack_rgss_torch(torch.from_numpy(g["raster_num_contrib"]), _t(g["raster_opacity"]), _t(g["raster_depth"]), _t(g["raster_feature"]))
+    for k in res:
+        np.testing.assert_allclose(tt[k].numpy(), res[k], rtol=1e-14, atol=0, err_msg=k)
+    covered = g["raster_num_contrib"] > 0
+    assert covered.any() and not covered.all() and not res["feature_normal"][:, ~covered].any()
+
+
+def test_depth2normal_torch_matches_reference_values_and_gradient(rv):
+    """The differentiable restatement against the recorded pseudo normals (render_view.npz, render_view_rgss.npz) and against the
+    reference's own autograd (depth2normal_grad.npz: normal and depth gradient; the gradient outside the degenerate pixels and the
+    pixels they touch, the rule of tests/test_gpu_render_view.py)."""
+    fovx, fovy = rv["cam_fov"]
+    for tag in ("train", "eval"):
+        n = eo.depth2normal_torch(_t(rv[f"{tag}_raster_depth"]), _t(rv["image_mask"]), fovx, fovy, rv["cam_prcppoint"])
+        np.testing.assert_allclose(n.numpy(), rv[f"{tag}_res_pseudo_normal"], rtol=0, atol=3e-5)
+    r = np.load(os.path.join(GOLD, "render_view_rgss.npz"))
+    n = eo.depth2normal_torch(_t(r["raster_depth"]), _t(r["image_mask"]), r["cam_fov"][0], r["cam_fov"][1], r["cam_prcppoint"])
+    np.testing.assert_allclose(n.numpy(), r["res_pseudo_normal"], rtol=0, atol=3e-5)
+    g = np.load(os.path.join(GOLD, "depth2normal_grad.npz"))
+    depth = _t(g["depth"]).requires_grad_(True)
+    n = eo.depth2normal_torch(depth, torch.from_numpy(g["mask"]), float(g["fovx"]), float(g["fovy"]), g["prcppoint"])
+    assert np.abs(n.detach().numpy() - g["normal"]).max() < 2e-5
+    np.testing.assert_allclose(n.detach().numpy(), eo.depth2normal(g["depth"], g["mask"], float(g["fovx"]), float(g["fovy"]), g["prcppoint"]),
+                               rtol=0, atol=1e-12)
+    (n * _t(g["upstream"])).sum().backward()
+    got, ref = depth.grad.numpy(), g["depth_grad"]
+    degenerate = (np.abs(g["normal"]).sum(0) == 0) & g["mask"][0]
+    touched = degenerate.copy()
+    touched[1:] |= degenerate[:-1]; touched[:-1] |= degenerate[1:]; touched[:, 1:] |= degenerate[:, :-1]; touched[:, :-1] |= degenerate[:, 1:]
+    ok = ~touched[None]
+    assert ok.mean() > 0.85
+    assert np.abs(got - ref)[ok].max() <= 2e-4 * np.abs(ref[ok]).max(), np.abs(got - ref)[ok].max() / np.abs(ref[ok]).max()
+
+
+def test_l1_ssim_oracle_in_fp32_is_the_reference_arithmetic():
+    """l1_ssim_torch(keep_dtype=True) on fp32 images -- the fp32 2-D window in one conv2d, as utils/loss_utils.py builds it -- against
+    the recorded fp32 results of the reference: values to a few ulp, gradients to fp32 rounding of the same expression graph."""
+    fx = np.load(os.path.join(GOLD, "losses.npz"))
+    for tag in ("a", "b", "c"):
+        img = torch.from_numpy(fx[f"{tag}_img"]).requires_grad_(True)
+        l1, s = eo.l1_ssim_torch(img, torch.from_numpy(fx[f"{tag}_gt"]), keep_dtype=True)
+        assert l1.dtype == s.dtype == torch.float32
+        gs, = torch.autograd.grad(s, img, retain_graph=True)
+        gl, = torch.autograd.grad(l1, img)
+        assert abs(float(s) - float(fx[f"{tag}_ssim"])) < 5e-7 and abs(float(l1) - float(fx[f"{tag}_l1"])) < 1e-7, tag
+        ref = fx[f"{tag}_dssim"]
+        assert np.abs(gs.numpy() - ref).max() <= 2e-5 * np.abs(ref).max(), (tag, np.abs(gs.numpy() - ref).max() / np.abs(ref).max())
+        assert np.array_equal(gl.numpy(), fx[f"{tag}_dl1"]), tag
+        # in fp64 the argument only changes how the window is rounded
+        l1d, sd = eo.l1_ssim_torch(img.detach().double(), torch.from_numpy(fx[f"{tag}_gt"]).double(), keep_dtype=True)
+        l1o, so_ = eo.l1_ssim_torch(img.detach(), torch.from_numpy(fx[f"{tag}_gt"]))
+        assert l1d.dtype == torch.float64 and abs(float(sd) - float(so_)) < 1e-7 and float(l1d) == float(l1o)
