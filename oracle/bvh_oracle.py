@@ -24,6 +24,7 @@ def lib():
         _lib = C.CDLL(_LIB_PATH)
         _lib.orc_bvh_leaf_boxes.argtypes = [C.c_int] + [C.c_void_p] * 4
         _lib.orc_bvh_trace.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 6 + [C.c_int]
+        _lib.orc_bvh_trace_margin.argtypes = _lib.orc_bvh_trace.argtypes + [C.c_void_p]
     return _lib
 
 
@@ -40,16 +41,22 @@ def leaf_boxes(means3D, scales, rotations):
     return out
 
 
-def trace_visibility(boxes, rays_o, rays_d, means3D, cov_inv, opacity, normals, t_offset=0.05, fp64=False):
+def trace_visibility(boxes, rays_o, rays_d, means3D, cov_inv, opacity, normals, t_offset=0.05, fp64=False, with_margin=False):
     """(contribute int32 [...], visibility float32 [...]) for rays of shape [..., 3] -- RayTracer.trace_visibility +
-    trace_bvh_opacity (submodules/bvh/__init__.py:60-71, src/trace.cu:186-262)."""
+    trace_bvh_opacity (submodules/bvh/__init__.py:60-71, src/trace.cu:186-262).  with_margin: a third result, float32 [...], the
+    smallest relative margin of any decision the ray made (bvh_oracle.cpp `Conj`); inf where nothing was decided by rounding."""
     ro, rd = _f(rays_o).reshape(-1, 3), _f(rays_d).reshape(-1, 3)
     boxes, means3D, cov_inv, opacity, normals = _f(boxes), _f(means3D), _f(cov_inv), _f(opacity).reshape(-1), _f(normals)
     n = ro.shape[0]
     contrib = np.zeros(n, dtype=np.int32)
     vis = np.ones(n, dtype=np.float32)
-    lib().orc_bvh_trace(means3D.shape[0], boxes.ctypes.data, n, ro.ctypes.data, rd.ctypes.data, float(t_offset),
-                        means3D.ctypes.data, cov_inv.ctypes.data, opacity.ctypes.data, normals.ctypes.data,
-                        contrib.ctypes.data, vis.ctypes.data, 1 if fp64 else 0)
+    args = (means3D.shape[0], boxes.ctypes.data, n, ro.ctypes.data, rd.ctypes.data, float(t_offset),
+            means3D.ctypes.data, cov_inv.ctypes.data, opacity.ctypes.data, normals.ctypes.data,
+            contrib.ctypes.data, vis.ctypes.data, 1 if fp64 else 0)
     shape = np.asarray(rays_o).shape[:-1]
+    if with_margin:
+        margin = np.zeros(n, dtype=np.float32)
+        lib().orc_bvh_trace_margin(*args, margin.ctypes.data)
+        return contrib.reshape(shape), vis.reshape(shape), margin.reshape(shape)
+    lib().orc_bvh_trace(*args)
     return contrib.reshape(shape), vis.reshape(shape)

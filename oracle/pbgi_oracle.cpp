@@ -174,11 +174,34 @@ inline bool box_hit(V3 o, V3 d, float t_min, float t_max, const float* b) {   //
     return true;
 }
 
+// ---- test-only instruments (tests/tracer_cases.py) ---------------------------------------------------------------------------------
+// g_exp_ulp: every expf result is moved that many ulps (+1 / -1 / 0): how far the outputs move when the exponential -- the only
+//            operation of this file that is not IEEE-exact -- is off by what two good implementations differ by.
+// Margin:    the comparisons that go through expf or a running product of such factors (alpha against 1/255 and 0.99, T against 0.2
+//            and 0.001), as the distance from the bound in ulps of the bound PER ACCUMULATED FACTOR; the smallest one of a ray is
+//            reported.  Everything else in this file is IEEE-exact in the kernel's operation order: a difference there is a fault.
+int g_exp_ulp = 0;
+inline float test_expf(float x) {
+    float e = std::exp(x);
+    if (g_exp_ulp > 0) e = std::nextafter(e, INFINITY);
+    if (g_exp_ulp < 0) e = std::nextafter(e, -INFINITY);
+    return e;
+}
+struct Margin {
+    double worst = INFINITY;
+    void add(float v, float bound, int factors) {
+        if (!std::isfinite(v)) return;
+        const double ulp = std::ldexp((double)bound, -23);
+        worst = std::fmin(worst, std::fabs((double)v - (double)bound) / (ulp * std::max(factors, 1)));
+    }
+};
+
 struct Hit { bool any; float t, keep; int index; float u, v; };   // keep = debug_res.x = 1 - alpha of the last accepted leaf
 
 // gs_bvh_hit, intersect_test.slang:251-437.  t / keep / index / uv are left untouched when nothing is accepted except that
 // the index becomes -1, exactly like the reference's inout parameters.
-void closest_hit(const Scene& S, V3 o, V3 d, float t_min, float t_max, float& t_hit, float& keep, int& index_hit, float& u, float& v, bool& any) {
+void closest_hit(const Scene& S, V3 o, V3 d, float t_min, float t_max, float& t_hit, float& keep, int& index_hit, float& u, float& v, bool& any,
+                 Margin* mg) {
     int stack[64];
     int count = 0;
     stack[count++] = 0;
@@ -237,7 +260,9 @@ void closest_hit(const Scene& S, V3 o, V3 d, float t_min, float t_max, float& t_
             const float power = -0.5f * (dd.x * dd.x * ci[0] + dd.y * dd.y * ci[3] + dd.z * dd.z * ci[5] + 2 * dd.x * dd.y * ci[1] +
                                          2 * dd.x * dd.z * ci[2] + 2 * dd.y * dd.z * ci[4]);
             if (power > 0.0f) continue;
-            const float alpha = std::fmin(0.99f, S.opacity[g] * std::exp(power));
+            const float alpha_raw = S.opacity[g] * test_expf(power);
+            const float alpha = std::fmin(0.99f, alpha_raw);
+            if (mg) { mg->add(alpha_raw, 1.0f / 255.0f, 1); mg->add(alpha_raw, 0.99f, 1); }
             if (alpha < 1.0f / 255.0f) continue;
             if (!(dot(d, nrm) < -0.0f)) hit = false;   // :399-404
             const bool update = hit && t_now < closest;
@@ -280,7 +305,8 @@ extern "C" {
 // Outputs: radiance [N,S,3], visibility [N,S], hit_indices [N,S] (first accepted primitive or -1), uvs [N,S,2].
 int orc_pbgi_trace(int P, const int32_t* info, const float* aabb, int N, int S, const float* ray_o, const float* ray_d, const float* centers,
                    const float* scales, const float* rotations, const float* normals, const float* opacity, const float* cov_inv,
-                   const float* shs, float* radiance, float* visibility, int32_t* hit_indices, float* uvs) {
+                   const float* shs, float* radiance, float* visibility, int32_t* hit_indices, float* uvs, float* margin, int32_t* queries) {
+    // margin [N,S] / queries [N,S] (closest-hit queries the ray took) are optional (nullptr)
     if (P <= 0 || N < 0 || S <= 0) return -1;
     const Scene Sc{P, info, aabb, centers, scales, rotations, normals, opacity, cov_inv, shs};
 #pragma omp parallel for schedule(dynamic, 4)
@@ -294,9 +320,12 @@ int orc_pbgi_trace(int P, const int32_t* info, const float* aabb, int N, int S, 
         const float t_max = 0.2f;
         bool done = false, visible = true;
         float sh[3] = {0.f, 0.f, 0.f};
+        Margin mg;
+        int nq = 0, factors = 0;
         while (T > 0.001f && !done) {
             bool hit;
-            closest_hit(Sc, o, dir, t_min, t_max, t_hit, keep, index_hit, u, v, hit);
+            closest_hit(Sc, o, dir, t_min, t_max, t_hit, keep, index_hit, u, v, hit, margin ? &mg : nullptr);
+            nq++;
             hit = index_hit == row ? false : hit;   // (Q-d)
             if (hit) {
                 if (first_hit == -1) { first_hit = index_hit; fu = u; fv = v; t_min = 0.01f; }
@@ -307,6 +336,8 @@ int orc_pbgi_trace(int P, const int32_t* info, const float* aabb, int N, int S, 
                 eval_sh(shs + 48 * (size_t)index_hit, sd, e);
                 for (int c = 0; c < 3; c++) sh[c] += e[c] * (1 - keep) * T;
                 T = T * keep;
+                factors++;
+                mg.add(T, 0.2f, factors); mg.add(T, 0.001f, factors);
                 if (T < 0.2f) visible = false;
             } else {
                 done = true;
@@ -316,8 +347,12 @@ int orc_pbgi_trace(int P, const int32_t* info, const float* aabb, int N, int S, 
         visibility[ri] = visible ? T : 0.0f;
         hit_indices[ri] = first_hit;
         uvs[2 * ri] = fu; uvs[2 * ri + 1] = fv;
+        if (margin) margin[ri] = (float)mg.worst;
+        if (queries) queries[ri] = nq;
     }
     return 0;
 }
+
+void orc_pbgi_set_exp_ulp(int ulps) { g_exp_ulp = ulps; }
 
 }  // extern "C"
