@@ -529,9 +529,10 @@ int svgir_pbgi_trace_radiance(int32_t P, char* bvh, int32_t N, int32_t S, const 
 
 /* Densification (scene/gaussian_model.py:1064-1248).
  * svgir_densify_masks : the selection of densify_and_clone / densify_and_split from the statistics densify_and_prune
- *   derives (grads = xyz_gradient_accum / denom and normal_gradient_accum / denom, NaN -> 0): selected when
- *   |grads| >= grad_threshold or |grads_normal| >= normal_threshold; clone_mask = selected and max(exp(scaling_raw)) <=
- *   size_limit (= percent_dense * scene_extent), split_mask = selected and > size_limit.  normal_gradient_accum may be NULL.
+ *   derives (grads = xyz_gradient_accum / denom and normal_gradient_accum / denom, NaN -> 0).  The clone test is on the norm, the
+ *   split test on the signed value, as in the reference: clone_mask = (|grads| >= grad_threshold or |grads_normal| >=
+ *   normal_threshold) and max(get_scaling) <= size_limit (= percent_dense * scene_extent); split_mask = (grads >= grad_threshold or
+ *   grads_normal >= normal_threshold) and max(get_scaling) > size_limit.  normal_gradient_accum may be NULL.
  * svgir_append_rows : cat_tensors_to_optimizer / densification_postfix for up to SVGIR_ADAM_MAX_TENSORS per-row tensors in
  *   one launch: dst = cat(src[0:rows_old], repeat(src[list[0:n]], repeat)), n = min(n_sel_max, *count_dev) (list / count_dev
  *   as produced by svgir_mask_scan); SVGIR_APPEND_ZERO_NEW leaves the new rows zero (the Adam moments of the new points).

@@ -165,15 +165,17 @@ __global__ void __launch_bounds__(BLOCK) densify_masks_kernel(int P, const float
 #pragma clang fp contract(off)
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= P) return;
-    // densify_and_prune: grads = accum / denom, NaN -> 0; norm over the last (size-1) axis = |.|
+    // densify_and_prune: grads = accum / denom, NaN -> 0.  densify_and_clone tests torch.norm over the last (size-1) axis = |.|
+    // (:1191-1192); densify_and_split tests the SIGNED padded_grad (:1143-1144), so a negative mean gradient clones but never splits
     float g = grad_accum[i] / denom[i], gn = normal_accum ? normal_accum[i] / denom[i] : 0.f;
-    g = g != g ? 0.f : fabsf(g);
-    gn = gn != gn ? 0.f : fabsf(gn);
-    const bool sel = g >= grad_threshold || gn >= normal_threshold;
+    g = g != g ? 0.f : g;
+    gn = gn != gn ? 0.f : gn;
+    const bool sel_clone = fabsf(g) >= grad_threshold || fabsf(gn) >= normal_threshold;
+    const bool sel_split = g >= grad_threshold || gn >= normal_threshold;
     // max of get_scaling over the three axes (NaN axes count as 1e-6, like the reference's nan_to_num)
     const float s = fmaxf(fmaxf(scaling_act(scaling_raw[3 * i]), scaling_act(scaling_raw[3 * i + 1])), scaling_act(scaling_raw[3 * i + 2]));
-    clone_mask[i] = sel && s <= size_limit;
-    split_mask[i] = sel && s > size_limit;
+    clone_mask[i] = sel_clone && s <= size_limit;
+    split_mask[i] = sel_split && s > size_limit;
 }
 
 struct AppendTable {

@@ -137,9 +137,9 @@ def prune_rows(tensors, keep):
     dev = keep.device
     P = keep.shape[0]
     k8 = keep.to(torch.uint8).contiguous() if keep.dtype != torch.uint8 else keep.contiguous()
-    kept = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    kept = N.out_tensor(max(P, 1), torch.int32, dev)   # (written up to the count; the rest is not promised)
     work = torch.empty(N.lib.svgir_mask_scan_work_words(P), dtype=torch.int32, device=dev)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
+    count = N.out_tensor(1, torch.int32, dev)
     N.check(N.lib.svgir_mask_scan(P, k8.data_ptr(), kept.data_ptr(), work.data_ptr(), count.data_ptr(), N.stream_ptr(dev)), "mask_scan")
     n = int(count.item())
     srcs = [t.contiguous() for t in tensors]
@@ -147,7 +147,7 @@ def prune_rows(tensors, keep):
     for t in srcs:
         if t.shape[0] != P:
             raise ValueError("prune_rows: every tensor must have one row per mask entry")
-        outs.append(torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev))
+        outs.append(N.out_tensor((n,) + tuple(t.shape[1:]), t.dtype, dev))
     for i in range(0, len(srcs), MAX_TENSORS):
         chunk = list(zip(srcs[i:i + MAX_TENSORS], outs[i:i + MAX_TENSORS]))
         arr = (_RowTensor * len(chunk))()
@@ -171,9 +171,9 @@ def _scan(mask):
     dev = mask.device
     P = mask.shape[0]
     k8 = mask.to(torch.uint8).contiguous()
-    kept = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    kept = N.out_tensor(max(P, 1), torch.int32, dev)   # (written up to the count; the rest is not promised)
     work = torch.empty(N.lib.svgir_mask_scan_work_words(P), dtype=torch.int32, device=dev)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
+    count = N.out_tensor(1, torch.int32, dev)
     N.check(N.lib.svgir_mask_scan(P, k8.data_ptr(), kept.data_ptr(), work.data_ptr(), count.data_ptr(), N.stream_ptr(dev)), "mask_scan")
     return kept, count, int(count.item())
 
@@ -187,7 +187,7 @@ def append_rows(tensors, sel_list, sel_count, n_sel, repeat=1, zero_new=()):
     dev = tensors[0].device
     P = tensors[0].shape[0]
     srcs = [t.contiguous() for t in tensors]
-    outs = [torch.empty((P + n_sel * repeat,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in srcs]
+    outs = [N.out_tensor((P + n_sel * repeat,) + tuple(t.shape[1:]), t.dtype, dev) for t in srcs]
     for i in range(0, len(srcs), MAX_TENSORS):
         chunk = list(zip(range(i, min(i + MAX_TENSORS, len(srcs))), srcs[i:i + MAX_TENSORS], outs[i:i + MAX_TENSORS]))
         arr = (_AppendTensor * len(chunk))()
@@ -301,16 +301,18 @@ class DensifyState:
             self._install(group, st, outs[k], outs[k + 1] if st is not None else None, outs[k + 2] if st is not None else None)
         self.weights_accum, self.xyz_gradient_accum, self.normal_gradient_accum, self.denom, self.max_radii2D = outs[len(tensors):]
 
-    def _masks(self, grad_threshold, scene_extent, grad_normal_threshold):
+    def _masks(self, grad_threshold, scene_extent, grad_normal_threshold, raw=False):
+        """(clone, split) selection of densify_and_prune; `raw`: the uint8 arrays as the kernel wrote them (the tests compare
+        those, so a byte the kernel forgot is not read as True)."""
         dev = self.params["xyz"].device
         P = self.params["xyz"].shape[0]
-        clone = torch.empty(P, dtype=torch.uint8, device=dev)
-        split = torch.empty(P, dtype=torch.uint8, device=dev)
+        clone = N.out_tensor(P, torch.uint8, dev)
+        split = N.out_tensor(P, torch.uint8, dev)
         N.check(N.lib.svgir_densify_masks(P, self.xyz_gradient_accum.data_ptr(), self.normal_gradient_accum.data_ptr(),
                                           self.denom.data_ptr(), self.params["scaling"].detach().contiguous().data_ptr(),
                                           float(grad_threshold), float(grad_normal_threshold), float(self.percent_dense * scene_extent),
                                           clone.data_ptr(), split.data_ptr(), N.stream_ptr(dev)), "densify_masks")
-        return clone.bool(), split.bool()
+        return (clone, split) if raw else (clone.bool(), split.bool())
 
     def densify_and_clone(self, clone_mask):
         return self._append_selected(clone_mask, 1)
