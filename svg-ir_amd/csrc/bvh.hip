@@ -9,12 +9,11 @@
 // A leaf is reached by the reference's traversal exactly when its own box passes the slab test (every ancestor's box
 // contains it), so the result does not depend on the shape of the tree: only the leaf boxes, the slab test and the per-leaf
 // arithmetic are the reference's; the tree layout is ours:
-//   * internal node = one 64-byte record {box of child 0, box of child 1, child ids, parent}: one fetch per visited node,
-//     both slab tests from it (the reference reads node[5] and two separate boxes);
+//   * the tree is the shared builder's (lbvh.hpp: sort, Karras hierarchy, one-launch refit) on the unique keys above, leaves
+//     named ~position: per internal node one 64-byte record {box of child 0, box of child 1, child ids, parent}, one fetch
+//     per visited node, both slab tests from it (the reference reads node[5] and two separate boxes);
 //   * the per-surfel data the leaf test needs {mean, opacity, inverse covariance, normal, id} is gathered once per trace
 //     call into 64-byte records in Morton order, so neighbouring leaves are neighbouring memory;
-//   * Morton sort = the rasterizer's radix sort (binning.hip); the refit hands boxes upward through the parents' records
-//     with one device-scope acquire-release counter per node (no second pass to lay the child boxes out);
 //   * one lane per ray, traversal stack of child ids in private memory; rays are taken in memory order (the reference's
 //     callers pass [surfels, samples] blocks: 64 consecutive rays share their origin).
 #include <algorithm>
@@ -27,35 +26,18 @@ namespace svgir {
 namespace {
 
 struct BvhLayout {
-    float* leaf_box;        // [P][6] lower.xyz, upper.xyz (surfel order)
-    uint32_t* key[2];       // [P] Morton codes ping/pong
-    uint32_t* val[2];       // [P] surfel ids ping/pong (val[sorted] = Morton order)
-    uint32_t* radix_tbl;    // radix scratch
-    float4* nodes;          // [P-1][4]: {lo0.xyz, hi0.x} {hi0.yz, lo1.xy} {lo1.z, hi1.xyz} {child0, child1, parent, -} (bits)
-    uint32_t* leaf_parent;  // [P] internal node above leaf i (Morton position) | slot << 31
-    uint32_t* arrive;       // [P-1] refit arrival counters
-    uint32_t* whole;        // [8] whole box as order-preserving integers: min xyz, max xyz
+    LbvhTree t;             // t.box = the leaf boxes (surfel order), leaves named ~position
     float4* leaf_rec;       // [P][4]: {mean.xyz, opacity} {c0 c1 c2 c3} {c4 c5 n.x n.y} {n.z, id, -, -}
     size_t bytes;
 };
 BvhLayout bvh_layout(char* base, int P) {
     BvhLayout b;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-    const size_t p = (size_t)(P > 0 ? P : 1);
-    b.leaf_box = (float*)take(p * 6 * 4);
-    b.key[0] = (uint32_t*)take(p * 4); b.key[1] = (uint32_t*)take(p * 4);
-    b.val[0] = (uint32_t*)take(p * 4); b.val[1] = (uint32_t*)take(p * 4);
-    b.radix_tbl = (uint32_t*)take(radix_table_words(P) * 4);
-    b.nodes = (float4*)take(p * 64);
-    b.leaf_parent = (uint32_t*)take(p * 4);
-    b.arrive = (uint32_t*)take(p * 4);
-    b.whole = (uint32_t*)take(32);
-    b.leaf_rec = (float4*)take(p * 64);
-    b.bytes = off;
+    BlobCursor c{base};
+    b.t = lbvh_tree_layout(c, P);
+    b.leaf_rec = c.take<float4>((size_t)(P > 0 ? P : 1) * 64);
+    b.bytes = c.off;
     return b;
 }
-constexpr int BVH_SORT_BITS = 30, BVH_SORT_PASSES = 4;   // 10 bits per axis; 8 + 8 + 8 + 6
 
 // ---- leaf boxes (__init__.py:32-58) + whole box (construct.cu:164-173) -------------------------------------------------
 __global__ void __launch_bounds__(BLOCK) bvh_leaf_kernel(int P, const float* __restrict__ means, const float* __restrict__ scales,
@@ -89,14 +71,7 @@ __global__ void __launch_bounds__(BLOCK) bvh_leaf_kernel(int P, const float* __r
             leaf_box[6 * i + c] = mn; leaf_box[6 * i + 3 + c] = mx;
         }
     }
-    // whole box: wave reduce, one atomic per wave and component
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        float mn = lo[c], mx = hi[c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn = fminf(mn, __shfl_xor(mn, d)); mx = fmaxf(mx, __shfl_xor(mx, d)); }
-        if ((threadIdx.x & 63) == 0) { atomicMin(&whole[c], f2ord(mn)); atomicMax(&whole[3 + c], f2ord(mx)); }
-    }
+    whole_box_add(lo, hi, whole);
 }
 
 // ---- Morton codes of the box centroids (construct.cu:6-52) -------------------------------------------------------------
@@ -119,84 +94,15 @@ __global__ void __launch_bounds__(BLOCK) bvh_morton_kernel(int P, const float* _
     vals[i] = (uint32_t)i;
 }
 
-// ---- Karras hierarchy on the unique keys morton << 31 | id (construct.cu:54-149, 204-229) --------------------------------
-__device__ __forceinline__ int delta_of(const uint32_t* __restrict__ mk, const uint32_t* __restrict__ id, int n, unsigned long long self, int j) {
-    if (j < 0 || j >= n) return -1;
-    const unsigned long long o = ((unsigned long long)mk[j] << 31) | id[j];
-    return __clzll((long long)(self ^ o));
-}
-__global__ void __launch_bounds__(BLOCK) bvh_hierarchy_kernel(int P, const uint32_t* __restrict__ mk, const uint32_t* __restrict__ id,
-                                                              float4* __restrict__ nodes, uint32_t* __restrict__ leaf_parent) {
-    const int idx = blockIdx.x * BLOCK + threadIdx.x;
-    if (idx >= P - 1) return;
-    const unsigned long long self = ((unsigned long long)mk[idx] << 31) | id[idx];
-    int first = 0, last = P - 1;
-    if (idx != 0) {
-        const int Ld = delta_of(mk, id, P, self, idx - 1), Rd = delta_of(mk, id, P, self, idx + 1);
-        const int d = Rd > Ld ? 1 : -1;
-        const int dmin = min(Ld, Rd);
-        int lmax = 2;
-        while (delta_of(mk, id, P, self, idx + d * lmax) > dmin) lmax <<= 1;
-        int l = 0;
-        for (int t = lmax >> 1; t > 0; t >>= 1)
-            if (delta_of(mk, id, P, self, idx + (l + t) * d) > dmin) l += t;
-        const int j = idx + l * d;
-        first = min(idx, j); last = max(idx, j);
-    }
-    // split: highest key bit that differs inside [first, last] (the keys are unique)
-    const unsigned long long fk = ((unsigned long long)mk[first] << 31) | id[first];
-    const int dnode = delta_of(mk, id, P, fk, last);
-    int split = first, stride = last - first;
-    do {
-        stride = (stride + 1) >> 1;
-        const int mid = split + stride;
-        if (mid < last && delta_of(mk, id, P, fk, mid) > dnode) split = mid;
-    } while (stride > 1);
-    // children: leaf (encoded ~position) when the range ends there, internal node otherwise
-    const bool lleaf = first == split, rleaf = last == split + 1;
-    const uint32_t c0 = lleaf ? ~(uint32_t)split : (uint32_t)split, c1 = rleaf ? ~(uint32_t)(split + 1) : (uint32_t)(split + 1);
-    // (component stores: .z of this record is written by the parent's thread)
-    nodes[4 * idx + 3].x = __builtin_bit_cast(float, c0); nodes[4 * idx + 3].y = __builtin_bit_cast(float, c1);
-    if (idx == 0) nodes[3].z = __builtin_bit_cast(float, 0xffffffffu);
-    // parent links (slot in bit 31)
-    if (lleaf) leaf_parent[split] = (uint32_t)idx; else nodes[4 * split + 3].z = __builtin_bit_cast(float, (uint32_t)idx);
-    if (rleaf) leaf_parent[split + 1] = (uint32_t)idx | 0x80000000u;
-    else nodes[4 * (split + 1) + 3].z = __builtin_bit_cast(float, (uint32_t)idx | 0x80000000u);
-}
-
-// ---- bottom-up refit (construct.cu:234-264): every leaf walks up; the second child to arrive at a node carries the union on ----
-__device__ __forceinline__ void store_child_box(float4* node, int slot, const float lo[3], const float hi[3]) {
-    float* f = reinterpret_cast<float*>(node);
-    float* d = f + 6 * slot;
-    d[0] = lo[0]; d[1] = lo[1]; d[2] = lo[2]; d[3] = hi[0]; d[4] = hi[1]; d[5] = hi[2];
-}
-__global__ void __launch_bounds__(BLOCK) bvh_refit_kernel(int P, const uint32_t* __restrict__ id, const float* __restrict__ leaf_box,
-                                                          float4* nodes, const uint32_t* __restrict__ leaf_parent, uint32_t* arrive) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= P) return;
-    const uint32_t g = id[i];
-    float lo[3], hi[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) { lo[c] = leaf_box[6 * g + c]; hi[c] = leaf_box[6 * g + 3 + c]; }
-    uint32_t link = leaf_parent[i];
-    for (int guard = 0; guard < 128; guard++) {
-        const uint32_t parent = link & 0x7fffffffu;
-        const int slot = (int)(link >> 31);
-        float4* node = nodes + 4 * (size_t)parent;
-        store_child_box(node, slot, lo, hi);
-        // release our box / acquire the sibling's: device-scope acquire-release on the arrival counter
-        const uint32_t old = __hip_atomic_fetch_add(&arrive[parent], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == 0) return;   // first to arrive: the sibling's thread finishes this node
-        const float* s = reinterpret_cast<const float*>(node) + 6 * (1 - slot);
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            lo[c] = fminf(lo[c], __hip_atomic_load(s + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            hi[c] = fmaxf(hi[c], __hip_atomic_load(s + 3 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        }
-        link = __builtin_bit_cast(uint32_t, __hip_atomic_load(reinterpret_cast<const float*>(node) + 14, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (link == 0xffffffffu) return;   // the root
-    }
-}
+// ---- the unique keys morton << 31 | index of the hierarchy (construct.cu:54-149, 204-229); a leaf is ~position ---------------------
+struct BvhKeys {
+    const uint32_t* __restrict__ mk;
+    const uint32_t* __restrict__ id;
+    int n;
+    __device__ unsigned long long key(int j) const { return ((unsigned long long)mk[j] << 31) | id[j]; }
+    __device__ int delta(int i, int j) const { return j < 0 || j >= n ? -1 : __clzll((long long)(key(i) ^ key(j))); }
+    __device__ uint32_t leaf(int j) const { return ~(uint32_t)j; }
+};
 
 // ---- per-trace leaf records in Morton order ----------------------------------------------------------------------------
 __global__ void __launch_bounds__(BLOCK) bvh_leaf_rec_kernel(int P, const uint32_t* __restrict__ id, const float* __restrict__ means,
@@ -331,18 +237,10 @@ int svgir_bvh_build(int32_t P, const float* means3D, const float* scales, const 
     hipStream_t s = (hipStream_t)stream;
     const BvhLayout B = bvh_layout(bvh, P);
     const int nb = (P + BLOCK - 1) / BLOCK;
-    if (hipMemsetAsync(B.whole, 0xff, 12, s) != hipSuccess) return SVGIR_ERR_HIP;
-    if (hipMemsetAsync(B.whole + 3, 0, 12, s) != hipSuccess) return SVGIR_ERR_HIP;
-    if (hipMemsetAsync(radix_gtot(B.radix_tbl, P), 0, radix_gtot_words(P) * 4, s) != hipSuccess) return SVGIR_ERR_HIP;
-    if (hipMemsetAsync(B.arrive, 0, (size_t)P * 4, s) != hipSuccess) return SVGIR_ERR_HIP;
-    hipLaunchKernelGGL(bvh_leaf_kernel, dim3(nb), dim3(BLOCK), 0, s, P, means3D, scales, rotations, B.leaf_box, B.whole);
-    hipLaunchKernelGGL(bvh_morton_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.leaf_box, B.whole, B.key[0], B.val[0]);
-    launch_radix_sort(B.key, B.val, P, nullptr, BVH_SORT_BITS, 8, B.radix_tbl, s);
-    const int fin = BVH_SORT_PASSES & 1;
-    if (P > 1) {
-        hipLaunchKernelGGL(bvh_hierarchy_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.key[fin], B.val[fin], B.nodes, B.leaf_parent);
-        hipLaunchKernelGGL(bvh_refit_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.val[fin], B.leaf_box, B.nodes, B.leaf_parent, B.arrive);
-    }
+    if (!lbvh_begin(B.t, P, s)) return SVGIR_ERR_HIP;
+    hipLaunchKernelGGL(bvh_leaf_kernel, dim3(nb), dim3(BLOCK), 0, s, P, means3D, scales, rotations, B.t.box, B.t.whole);
+    hipLaunchKernelGGL(bvh_morton_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.t.box, B.t.whole, B.t.key[0], B.t.val[0]);
+    lbvh_finish(B.t, P, BvhKeys{B.t.key[0], B.t.val[0], P}, LbvhNoSink{}, s);   // (a single surfel: the sort only)
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
 
@@ -361,11 +259,10 @@ int svgir_bvh_trace_visibility(int32_t P, char* bvh, int64_t num_rays, const flo
     }
     if (!bvh || !means3D || !cov_inv || !opacity || !normals) return SVGIR_ERR_INVALID;
     const BvhLayout B = bvh_layout(bvh, P);
-    const int fin = BVH_SORT_PASSES & 1;
-    hipLaunchKernelGGL(bvh_leaf_rec_kernel, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, P, B.val[fin], means3D, cov_inv, opacity,
+    hipLaunchKernelGGL(bvh_leaf_rec_kernel, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, P, B.t.val[0], means3D, cov_inv, opacity,
                        normals, B.leaf_rec);
     hipLaunchKernelGGL(bvh_trace_kernel, dim3((unsigned)((num_rays + BVH_WAVE - 1) / BVH_WAVE)), dim3(BVH_WAVE), 0, s, P, (long long)num_rays,
-                       B.nodes, B.leaf_rec, rays_o, rays_d, t_offset, contribute, visibility);
+                       B.t.pair, B.leaf_rec, rays_o, rays_d, t_offset, contribute, visibility);
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
 

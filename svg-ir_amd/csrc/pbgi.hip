@@ -6,8 +6,8 @@
 //     lbvh_hierarchy,lbvh_bounding_boxes}.slang: boxes centre +- 3 max|scale|, 30-bit Morton codes of the box centres in
 //     the scene extent, a stable sort by code, the Karras hierarchy with duplicate codes resolved by sorted position,
 //     bottom-up box unions.  The reference sorts with ONE 256-thread workgroup and refits with one launch per tree level
-//     (each with a host round trip for the height); here: the library's multi-block radix sort and ONE refit launch
-//     (arrival counters, device-scope acquire/release);
+//     (each with a host round trip for the height); here: the builder shared with bvh.hip (lbvh.hpp: the library's multi-block
+//     radix sort, ONE refit launch) with this tracer's keys, leaf numbering and a sink for the reference-numbered nodes;
 //   * pbgi/renderer.py:596-615 render_radiance_with_sampling_SH + bvhworkers/intersect_test.slang:1879-1990 (the ray loop),
 //     :251-437 (gs_bvh_hit), :94-148 (ellipse_hit), :21-42 (aabb_hit), sh_utils.slang (eval_sh).
 //
@@ -16,9 +16,10 @@
 // lists this and the other reproduced quirks, Q-a .. Q-e).  So the tree is the reference's tree -- same node numbering
 // (internal nodes 0 .. P-2, leaf of sorted position j at P-1+j), children pushed left then right, boxes tested when popped
 // against the closest hit so far -- and the kernels keep fp contraction off.  What is ours is the data layout: 32-byte node
-// records {box, left, right} (one fetch per visited node instead of 3 + 6 scalar loads), and 96-byte leaf records in sorted
-// order prepared once per trace call (centre, scales, plane normal, the two rows of the inverse rotation the ellipse test
-// needs, unit normal, inverse covariance) instead of a quaternion -> matrix -> inverse evaluation at every visited leaf.
+// records {box, left, right} beside the builder's 64-byte child-pair records (one fetch per visited node instead of 3 + 6
+// scalar loads), and 96-byte leaf records in sorted order prepared once per trace call (centre, scales, plane normal, the
+// two rows of the inverse rotation the ellipse test needs, unit normal, inverse covariance) instead of a quaternion ->
+// matrix -> inverse evaluation at every visited leaf.
 // One lane per ray, rays in memory order ([rows, samples]: the 64 rays of a wave share their origin).
 #include <algorithm>
 #include <cstdlib>
@@ -34,15 +35,8 @@ struct PbgiNode { float lo[3], hi[3]; int32_t left, right; };   // 32 bytes
 static_assert(sizeof(PbgiNode) == 32, "node record");
 
 struct PbgiLayout {
-    float* box;             // [P][6] element boxes (primitive order)
-    uint32_t* whole;        // [8] scene extent as order-preserving integers: min xyz, max xyz
-    uint32_t* key[2];       // [P] Morton codes ping/pong
-    uint32_t* val[2];       // [P] primitive ids ping/pong
-    uint32_t* radix_tbl;
-    PbgiNode* node;         // [2P-1]
-    float4* pair;           // [P-1][4] traversal records of the internal nodes: the boxes of BOTH children + their ids (64 bytes)
-    uint32_t* parent;       // [2P-1]
-    uint32_t* arrive;       // [P-1]
+    LbvhTree t;             // t.box = the element boxes (primitive order), t.pair = the traversal records of the internal nodes
+    PbgiNode* node;         // [2P-1] the reference's tree: internal nodes 0 .. P-2, leaf of sorted position j at P-1+j
     float4* rec;            // [P][6] leaf records (sorted order), filled per trace call
     unsigned long long* queue;   // [8] per XCD: next ray of its part of the launch that no wave has claimed yet (reset per trace call)
     uint32_t* rkey[2];      // [P] Morton codes of the ray origins of a trace call (rows are traced in that order), ping/pong
@@ -51,26 +45,17 @@ struct PbgiLayout {
 };
 PbgiLayout pbgi_layout(char* base, int P) {
     PbgiLayout b;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
+    BlobCursor c{base};
     const size_t p = (size_t)(P > 0 ? P : 1);
-    b.box = (float*)take(p * 24);
-    b.whole = (uint32_t*)take(32);
-    b.key[0] = (uint32_t*)take(p * 4); b.key[1] = (uint32_t*)take(p * 4);
-    b.val[0] = (uint32_t*)take(p * 4); b.val[1] = (uint32_t*)take(p * 4);
-    b.radix_tbl = (uint32_t*)take(radix_table_words(P) * 4);
-    b.node = (PbgiNode*)take(2 * p * 32);
-    b.pair = (float4*)take(p * 64);
-    b.parent = (uint32_t*)take(2 * p * 4);
-    b.arrive = (uint32_t*)take(p * 4);
-    b.rec = (float4*)take(p * 96);
-    b.queue = (unsigned long long*)take(64);
-    b.rkey[0] = (uint32_t*)take(p * 4); b.rkey[1] = (uint32_t*)take(p * 4);
-    b.rval[0] = (uint32_t*)take(p * 4); b.rval[1] = (uint32_t*)take(p * 4);
-    b.bytes = off;
+    b.t = lbvh_tree_layout(c, P);
+    b.node = c.take<PbgiNode>(2 * p * 32);
+    b.rec = c.take<float4>(p * 96);
+    b.queue = c.take<unsigned long long>(64);
+    b.rkey[0] = c.take<uint32_t>(p * 4); b.rkey[1] = c.take<uint32_t>(p * 4);
+    b.rval[0] = c.take<uint32_t>(p * 4); b.rval[1] = c.take<uint32_t>(p * 4);
+    b.bytes = c.off;
     return b;
 }
-constexpr int PBGI_SORT_BITS = 30, PBGI_SORT_PASSES = 4;
 
 // ---- element boxes + scene extent (get_elements.slang:74-107, bvhhelpers.py:105-111) ---------------------------------------
 __global__ void __launch_bounds__(BLOCK) pbgi_box_kernel(int P, const float* __restrict__ centers, const float* __restrict__ scales,
@@ -86,13 +71,7 @@ __global__ void __launch_bounds__(BLOCK) pbgi_box_kernel(int P, const float* __r
             box[6 * i + c] = lo[c]; box[6 * i + 3 + c] = hi[c];
         }
     }
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        float mn = lo[c], mx = hi[c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn = fminf(mn, __shfl_xor(mn, d)); mx = fmaxf(mx, __shfl_xor(mx, d)); }
-        if ((threadIdx.x & 63) == 0) { atomicMin(&whole[c], f2ord(mn)); atomicMax(&whole[3 + c], f2ord(mx)); }
-    }
+    whole_box_add(lo, hi, whole);
 }
 
 // ---- Morton codes (lbvh_morton_codes.slang:22-80) ------------------------------------------------------------------------
@@ -115,89 +94,28 @@ __global__ void __launch_bounds__(BLOCK) pbgi_morton_kernel(int P, const float* 
     vals[i] = (uint32_t)i;
 }
 
-// ---- hierarchy (lbvh_hierarchy.slang:40-244): Karras 2012 on the sorted codes, equal codes told apart by position ----------
-__device__ __forceinline__ int pbgi_lcp(const uint32_t* __restrict__ code, int n, int i, uint32_t ci, int j) {
-    if (j < 0 || j > n - 1) return -1;
-    const uint32_t cj = code[j];
-    if (ci == cj) return 32 + __clz((int)((uint32_t)i ^ (uint32_t)j));
-    return __clz((int)(ci ^ cj));
-}
-__global__ void __launch_bounds__(BLOCK) pbgi_hierarchy_kernel(int P, const uint32_t* __restrict__ code, const uint32_t* __restrict__ prim,
-                                                               const float* __restrict__ box, PbgiNode* __restrict__ node,
-                                                               uint32_t* __restrict__ parent) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= P) return;
-    const int L = P - 1;
-    {   // leaf of sorted position i
-        PbgiNode nd;
-        const uint32_t g = prim[i];
-#pragma unroll
-        for (int c = 0; c < 3; c++) { nd.lo[c] = box[6 * g + c]; nd.hi[c] = box[6 * g + 3 + c]; }
-        nd.left = 0; nd.right = 0;
-        node[L + i] = nd;
+// ---- the keys of the hierarchy (lbvh_hierarchy.slang:40-244): the sorted codes, equal codes told apart by position ---------------
+struct PbgiKeys {
+    const uint32_t* __restrict__ code;
+    int n;
+    __device__ int delta(int i, int j) const {
+        if (j < 0 || j > n - 1) return -1;
+        const uint32_t ci = code[i], cj = code[j];
+        if (ci == cj) return 32 + __clz((int)((uint32_t)i ^ (uint32_t)j));
+        return __clz((int)(ci ^ cj));
     }
-    if (i >= P - 1) return;
-    const uint32_t ci = code[i];
-    const int dl = pbgi_lcp(code, P, i, ci, i - 1), dr = pbgi_lcp(code, P, i, ci, i + 1);
-    const int d = dr >= dl ? 1 : -1;
-    const int dmin = min(dl, dr);
-    int lmax = 2;
-    while (pbgi_lcp(code, P, i, ci, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t > 0; t >>= 1)
-        if (pbgi_lcp(code, P, i, ci, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int first = min(i, j), last = max(i, j);
-    const uint32_t cf = code[first];
-    const int common = pbgi_lcp(code, P, first, cf, last);
-    int split = first, stride = last - first;
-    do {
-        stride = (stride + 1) >> 1;
-        const int cand = split + stride;
-        if (cand < last && pbgi_lcp(code, P, first, cf, cand) > common) split = cand;
-    } while (stride > 1);
-    const int left = split == first ? L + split : split, right = split + 1 == last ? L + split + 1 : split + 1;
-    node[i].left = left; node[i].right = right;
-    parent[left] = (uint32_t)i; parent[right] = (uint32_t)i;
-    if (i == 0) parent[0] = 0xffffffffu;
-}
-
-// ---- boxes of the internal nodes, bottom-up in one launch (lbvh_bounding_boxes.slang does one launch per tree level) --------
-__global__ void __launch_bounds__(BLOCK) pbgi_refit_kernel(int P, PbgiNode* node, const uint32_t* __restrict__ parent, uint32_t* arrive) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= P) return;
-    uint32_t p = parent[P - 1 + i];
-    for (int guard = 0; guard < 128 && p != 0xffffffffu; guard++) {
-        // the second child to arrive owns the node: release / acquire of the children's boxes on the arrival counter
-        const uint32_t old = __hip_atomic_fetch_add(&arrive[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == 0) return;
-        const int a = node[p].left, b = node[p].right;
-        const float* fa = reinterpret_cast<const float*>(node + a);
-        const float* fb = reinterpret_cast<const float*>(node + b);
-        float* fo = reinterpret_cast<float*>(node + p);
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float la = __hip_atomic_load(fa + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), lb = __hip_atomic_load(fb + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float ha = __hip_atomic_load(fa + 3 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), hb = __hip_atomic_load(fb + 3 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(fo + c, fminf(la, lb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(fo + 3 + c, fmaxf(ha, hb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        p = parent[p];
+    __device__ uint32_t leaf(int j) const { return (uint32_t)(n - 1 + j); }
+};
+// ---- what the refit writes beside the traversal records: the reference-numbered nodes (lbvh_bounding_boxes.slang does one launch
+// per tree level); pbgi_trace_kernel tests a node's own box from them, pbgi_export_kernel copies them out ------------------------------
+struct PbgiNodeSink {
+    PbgiNode* __restrict__ out;
+    int n;
+    __device__ void node(uint32_t i, const float lo[3], const float hi[3], uint32_t left, uint32_t right) const {
+        out[i] = PbgiNode{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}, (int32_t)left, (int32_t)right};
     }
-}
-
-// ---- traversal records: {box of the left child, box of the right child, left, right} per internal node ------------------------
-__global__ void __launch_bounds__(BLOCK) pbgi_pair_kernel(int P, const PbgiNode* __restrict__ node, float4* __restrict__ pair) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= P - 1) return;
-    const int l = node[i].left, r = node[i].right;
-    const PbgiNode a = node[l], b = node[r];
-    float4* o = pair + 4 * (size_t)i;
-    o[0] = make_float4(a.lo[0], a.lo[1], a.lo[2], a.hi[0]);
-    o[1] = make_float4(a.hi[1], a.hi[2], b.lo[0], b.lo[1]);
-    o[2] = make_float4(b.lo[2], b.hi[0], b.hi[1], b.hi[2]);
-    o[3] = make_float4(__builtin_bit_cast(float, l), __builtin_bit_cast(float, r), 0.f, 0.f);
-}
+    __device__ void leaf(int j, const float lo[3], const float hi[3]) const { node((uint32_t)(n - 1 + j), lo, hi, 0, 0); }
+};
 
 // ---- the tree in the reference's tensors: LBVHNode_info [2P-1][3] = {left, right, primitive}, LBVHNode_aabb [2P-1][6] ------
 __global__ void __launch_bounds__(BLOCK) pbgi_export_kernel(int P, const PbgiNode* __restrict__ node, const uint32_t* __restrict__ code,
@@ -684,17 +602,10 @@ int svgir_pbgi_bvh_build(int32_t P, const float* centers, const float* scales, c
     hipStream_t s = (hipStream_t)stream;
     const PbgiLayout B = pbgi_layout(bvh, P);
     const int nb = (P + BLOCK - 1) / BLOCK;
-    if (hipMemsetAsync(B.whole, 0xff, 12, s) != hipSuccess) return SVGIR_ERR_HIP;
-    if (hipMemsetAsync(B.whole + 3, 0, 12, s) != hipSuccess) return SVGIR_ERR_HIP;
-    if (hipMemsetAsync(radix_gtot(B.radix_tbl, P), 0, radix_gtot_words(P) * 4, s) != hipSuccess) return SVGIR_ERR_HIP;
-    if (hipMemsetAsync(B.arrive, 0, (size_t)P * 4, s) != hipSuccess) return SVGIR_ERR_HIP;
-    hipLaunchKernelGGL(pbgi_box_kernel, dim3(nb), dim3(BLOCK), 0, s, P, centers, scales, B.box, B.whole);
-    hipLaunchKernelGGL(pbgi_morton_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.box, B.whole, B.key[0], B.val[0]);
-    launch_radix_sort(B.key, B.val, P, nullptr, PBGI_SORT_BITS, 8, B.radix_tbl, s);
-    const int fin = PBGI_SORT_PASSES & 1;
-    hipLaunchKernelGGL(pbgi_hierarchy_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.key[fin], B.val[fin], B.box, B.node, B.parent);
-    if (P > 1) hipLaunchKernelGGL(pbgi_refit_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.node, B.parent, B.arrive);
-    if (P > 1) hipLaunchKernelGGL(pbgi_pair_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.node, B.pair);
+    if (!lbvh_begin(B.t, P, s)) return SVGIR_ERR_HIP;
+    hipLaunchKernelGGL(pbgi_box_kernel, dim3(nb), dim3(BLOCK), 0, s, P, centers, scales, B.t.box, B.t.whole);
+    hipLaunchKernelGGL(pbgi_morton_kernel, dim3(nb), dim3(BLOCK), 0, s, P, B.t.box, B.t.whole, B.t.key[0], B.t.val[0]);
+    lbvh_finish(B.t, P, PbgiKeys{B.t.key[0], P}, PbgiNodeSink{B.node, P}, s);
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
 
@@ -702,9 +613,8 @@ int svgir_pbgi_bvh_export(int32_t P, char* bvh, int32_t* info, float* aabb, int3
     using namespace svgir;
     if (P <= 0 || !bvh || !info || !aabb) return SVGIR_ERR_INVALID;
     const PbgiLayout B = pbgi_layout(bvh, P);
-    const int fin = PBGI_SORT_PASSES & 1;
-    hipLaunchKernelGGL(pbgi_export_kernel, dim3((2 * P - 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)stream, P, B.node, B.key[fin],
-                       B.val[fin], info, aabb, sorted);
+    hipLaunchKernelGGL(pbgi_export_kernel, dim3((2 * P - 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)stream, P, B.node, B.t.key[0],
+                       B.t.val[0], info, aabb, sorted);
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
 
@@ -720,8 +630,7 @@ int svgir_pbgi_trace_radiance(int32_t P, char* bvh, int32_t N, int32_t S, const 
         return SVGIR_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const PbgiLayout B = pbgi_layout(bvh, P);
-    const int fin = PBGI_SORT_PASSES & 1;
-    hipLaunchKernelGGL(pbgi_leaf_rec_kernel, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, P, B.val[fin], centers, scales, rotations, normals,
+    hipLaunchKernelGGL(pbgi_leaf_rec_kernel, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, P, B.t.val[0], centers, scales, rotations, normals,
                        opacity, cov3D_inverse, B.rec);
     // Persistent waves (one per resident slot: 10 KB of LDS each, 16 per CU) take chunks of consecutive rays (whole rows: the rays of a row
     // share their origin) from a launch-wide queue, so no wave slot idles while rays are left and the end of the launch is one ray deep.
@@ -733,16 +642,16 @@ int svgir_pbgi_trace_radiance(int32_t P, char* bvh, int32_t N, int32_t S, const 
     for (int row0 = 0; row0 < N; row0 += P) {   // (the row-order buffers hold P rows: more rows than surfels go in blocks)
         const int n = std::min(P, N - row0);
         // rows in the Morton order of their origins
-        if (hipMemsetAsync(radix_gtot(B.radix_tbl, n), 0, radix_gtot_words(n) * 4, s) != hipSuccess) return SVGIR_ERR_HIP;   // (n <= P: within the table)
-        hipLaunchKernelGGL(pbgi_row_code_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, n, ray_o + 3 * (size_t)row0, B.whole, B.rkey[0], B.rval[0]);
-        launch_radix_sort(B.rkey, B.rval, n, nullptr, PBGI_SORT_BITS, 8, B.radix_tbl, s);
+        if (hipMemsetAsync(radix_gtot(B.t.radix_tbl, n), 0, radix_gtot_words(n) * 4, s) != hipSuccess) return SVGIR_ERR_HIP;   // (n <= P: within the table)
+        hipLaunchKernelGGL(pbgi_row_code_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, n, ray_o + 3 * (size_t)row0, B.t.whole, B.rkey[0], B.rval[0]);
+        launch_radix_sort(B.rkey, B.rval, n, nullptr, LBVH_SORT_BITS, 8, B.t.radix_tbl, s);
         const long long rays = (long long)n * S;
         const long long nw = std::min<long long>((rays + chunk - 1) / chunk, slots);
         const long long nchunks = (rays + chunk - 1) / chunk;
         const long long part = (nchunks + 7) / 8 * chunk;   // rays per XCD part (whole chunks)
         hipLaunchKernelGGL(pbgi_queue_init_kernel, dim3(1), dim3(64), 0, s, B.queue, (unsigned long long)part, (unsigned long long)chunk, (unsigned)nw);
-        hipLaunchKernelGGL(pbgi_trace_kernel, dim3((unsigned)nw), dim3(PBGI_WAVE), 0, s, P, B.node, B.pair, B.rec, B.val[fin], n, S, ray_o,
-                           ray_d, centers, shs, radiance, visibility, hit_indices, uvs, (int)chunk, B.queue, part, B.rval[PBGI_SORT_PASSES & 1], row0);
+        hipLaunchKernelGGL(pbgi_trace_kernel, dim3((unsigned)nw), dim3(PBGI_WAVE), 0, s, P, B.node, B.t.pair, B.rec, B.t.val[0], n, S, ray_o,
+                           ray_d, centers, shs, radiance, visibility, hit_indices, uvs, (int)chunk, B.queue, part, B.rval[0], row0);
     }
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
