@@ -527,6 +527,24 @@ int svgir_pbgi_trace_radiance(int32_t P, char* bvh, int32_t N, int32_t S, const 
                               const float* cov3D_inverse, const float* shs, float* radiance, float* visibility, int32_t* hit_indices,
                               float* uvs, void* stream);
 
+/* Exact k-nearest-neighbour search over a point cloud: simple_knn's `distCUDA2` (submodules/simple-knn/simple_knn.cu:147-221; the initial
+ * scales of GaussianModel.create_from_pcd) and custom_knn's `topKdistCUDA2` (no source upstream; get_knn_loss,
+ * scene/gaussian_model.py:577-592).  points [P,3]; `work` is svgir_knn_bytes bytes of scratch, written by the call and free again when the
+ * call's kernels have run; everything is launched on `stream` and nothing waits on the host.
+ *   The result is a pure function of the input.  For point i and every j != i: d = p_j - p_i per component,
+ *   dist = (d.x*d.x + d.y*d.y) + d.z*d.z in fp32, each operation rounded (no fused multiply-add).  Candidates are ordered by
+ *   (dist, j) ascending; a candidate whose dist is NaN or +inf is not a neighbour.  i is never its own neighbour; a coincident point is
+ *   one, at distance 0.
+ *   svgir_knn_bytes     : size of the scratch for P points.
+ *   svgir_knn_mean_dist : out_mean [P] = ((b0 + b1) + b2) / 3.0f in fp32 (correctly rounded), b = the three smallest dist in ascending
+ *       order, FLT_MAX where there is no neighbour (simple_knn's values: +inf for P <= 2, about 1.13e38 for P = 3).
+ *   svgir_knn_topk      : K = 8.  out_dist [P,8], out_idx [P,8] int32, row i = the 8 first candidates of i in the order above; a slot
+ *       without a neighbour holds dist = +inf and idx = i (an index that is always in range).
+ * P = 0 launches nothing. */
+size_t svgir_knn_bytes(int32_t P);
+int svgir_knn_mean_dist(int32_t P, const float* points, float* out_mean, char* work, void* stream);
+int svgir_knn_topk(int32_t P, const float* points, float* out_dist, int32_t* out_idx, char* work, void* stream);
+
 /* Densification (scene/gaussian_model.py:1064-1248).
  * svgir_densify_masks : the selection of densify_and_clone / densify_and_split from the statistics densify_and_prune
  *   derives (grads = xyz_gradient_accum / denom and normal_gradient_accum / denom, NaN -> 0).  The clone test is on the norm, the
