@@ -527,6 +527,60 @@ int svgir_pbgi_trace_radiance(int32_t P, char* bvh, int32_t N, int32_t S, const 
                               const float* cov3D_inverse, const float* shs, float* radiance, float* visibility, int32_t* hit_indices,
                               float* uvs, void* stream);
 
+/* The consumers of those caches: the pbgi irradiance kernels (pbgi/renderer.py:100-226, 743-751 `render_irradiance`,
+ * `render_irradiance_sample`; pbgi/bvhworkers/intersect_test.slang:901-1360; the brdf is `shading_brdf_simple`, pbr.slang:283-329), called
+ * by GaussianModel.get_radiance_loss on every stage-2 iteration and by GaussianModel.calculate_radiance at relighting
+ * (scene/gaussian_model.py:530-575).  They trace nothing: they gather through the cached first hits.
+ *   All arithmetic is fp32, all indices int32, and N = P: rows and hit surfels index the same arrays.
+ *   ray_d [N,S,3]; envmap [N,S,3] (the caller's direct_light(incident_dirs) * incident_areas); normals [N,12] and albedos [N,12] as
+ *   channel * 4 + corner (get_shading_normal.transpose(1,2).reshape(N,-1)); roughnesses [N,4]; hit_indices [N,S] (first hit or -1);
+ *   uvs [N,S,2]; sample_indices [N] (the sample form).
+ *   brdf(V, L, n, albedo, r): n, V, L normalised (x / sqrt((x.x*x.x + x.y*x.y) + x.z*x.z)), H = normalize(V + L); NoL, NoV, NoH, VoH =
+ *   clamp(dot, 1e-6, 1) (the reference's abs on NoV is overwritten and has no effect); a = r*r, a2 = a*a, k = ((a + 2r) + 1) / 8;
+ *   F = 0.04 + 0.96 * 2^((-5.55473 VoH - 6.98316) VoH); n0 = NoH*NoH*(a2 - 1) + 1, n1 = NoV (1 - k) + k, n2 = NoL (1 - k) + k;
+ *   spec = (F a2) / clamp(4pi n0 n0 n1 n2, 1e-6, 4pi); brdf = spec + albedo * (1/pi).
+ *   Corner weights of uv = (u, v): w = ((1-u)(1-v), u(1-v), (1-u)v, uv).
+ *   svgir_pbgi_irradiance_sample : out [N,3].  Per row i: p = sample_indices[i], h = hit_indices[i,p],
+ *       out[i,c] = sum over s with hit_indices[h,s] == -1 of
+ *                  (sum_k w_k(uvs[h,s]) brdf(-ray_d[i,p], ray_d[h,s], normal_k[h], albedo_k[h], roughnesses[h,0])_c) * envmap[h,s,c] / S.
+ *       Two quirks of the reference are kept: corner 0's roughness serves all four corners, and there is no n.l cosine factor.
+ *   svgir_pbgi_irradiance : out [N,S,3], forward only.  Per (i,p) the same sum with roughnesses[h,k] per corner and every corner term
+ *       multiplied by clamp(dot(normal_k[h], normalize(ray_d[h,s])), 1e-6, 1) (the stored normal, not the normalised one).
+ *   svgir_pbgi_irradiance_sample_backward : with g = d_out [N,3], summed over all rows i and samples s that contribute:
+ *       d_albedos[h,4c+k] += g_c w_k envmap[h,s,c] / (pi S);  d_envmap[h,s,c] += g_c irr_c / S (irr = the corner-blended brdf);
+ *       d_roughnesses[h,0] += (sum_c g_c envmap[h,s,c] / S) (sum_k w_k d spec_k / d r): where the denominator lies inside
+ *       [1e-6, 4pi] its derivative is passed, outside it is zero; columns 1-3 of d_roughnesses are zero.  Directions, normals and uvs
+ *       get no gradient (no_diff in the reference).  The call writes every element of d_envmap [N,S,3], d_albedos [N,12] and
+ *       d_roughnesses [N,4]: it clears them itself.
+ *   Three things the reference leaves undefined are decided here:
+ *     - A missed primary ray gives zeros.  When h == -1 the row (the [i,p] entry) is zero and contributes no gradient.  (The
+ *       reference stores through a three-index access into its [N,3] result there; the intended value is the zero the tensor was
+ *       created with.)
+ *     - The sum is a sum.  The reference accumulates with a non-atomic += from S threads; here the result is the mathematical sum
+ *       over s, in a free but fixed order: the forward gives the same bits for the same input.  The backward adds with float
+ *       atomics where rows share a hit surfel and is repeatable only up to the order of those adds.
+ *     - Nothing reads out of bounds.  sample_indices[i] outside [0,S), or a first hit h outside [-1,N), is treated as a miss.  The
+ *       hit index of a SECONDARY sample is never used as an address: the sample contributes when it is exactly -1.
+ *   A fourth decision is this project's own:
+ *     - n0 is evaluated without cancellation.  Where n.H >= 1e-6 the kernels compute n0 = |H - (n.H) n|^2 (1 - a2) + a2 instead of
+ *       the reference's NoH*NoH*(a2 - 1) + 1.  For unit vectors it is the same number, so the contract's value is unchanged, but
+ *       the reference's form loses fp32's absolute 1e-7 against an n0 that goes down to a2 (4e-4 of a term at r = 0.14,
+ *       NoH = 0.9997; this form 2e-5 there).  The results therefore differ from an fp32 evaluation of the reference's formula
+ *       by that formula's own error: up to 2e-2 absolute in single outputs at N = 200 k.
+ *   With -ray_d[i,p] == ray_d[h,s] (a zero half vector) or non-finite inputs the arithmetic propagates as it does in the reference.
+ *   The reference's kernels also read metallics, opacities, SHs, centers, scales, rotates and the LBVH tensors; none of them reaches
+ *   the result (eval_sh is dead code there), so they are no arguments here.
+ * Everything is launched on `stream`; nothing waits on the host; N = 0 launches nothing. */
+int svgir_pbgi_irradiance_sample(int32_t N, int32_t S, const int32_t* sample_indices, const float* ray_d, const float* envmap,
+                                 const float* normals, const float* albedos, const float* roughnesses, const int32_t* hit_indices,
+                                 const float* uvs, float* out, void* stream);
+int svgir_pbgi_irradiance_sample_backward(int32_t N, int32_t S, const int32_t* sample_indices, const float* ray_d, const float* envmap,
+                                          const float* normals, const float* albedos, const float* roughnesses,
+                                          const int32_t* hit_indices, const float* uvs, const float* d_out, float* d_envmap,
+                                          float* d_albedos, float* d_roughnesses, void* stream);
+int svgir_pbgi_irradiance(int32_t N, int32_t S, const float* ray_d, const float* envmap, const float* normals, const float* albedos,
+                          const float* roughnesses, const int32_t* hit_indices, const float* uvs, float* out, void* stream);
+
 /* Exact k-nearest-neighbour search over a point cloud: simple_knn's `distCUDA2` (submodules/simple-knn/simple_knn.cu:147-221; the initial
  * scales of GaussianModel.create_from_pcd) and custom_knn's `topKdistCUDA2` (no source upstream; get_knn_loss,
  * scene/gaussian_model.py:577-592).  points [P,3]; `work` is svgir_knn_bytes bytes of scratch, written by the call and free again when the

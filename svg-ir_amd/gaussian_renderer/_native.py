@@ -117,6 +117,13 @@ def _load():
     lib.svgir_last_timings.restype = C.c_int
     lib.svgir_last_timings.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int]
     lib.svgir_last_error.restype = C.c_char_p
+    # the pbgi irradiance kernels (pbgi/renderer.py): N, S, device pointers, stream
+    lib.svgir_pbgi_irradiance_sample.restype = C.c_int
+    lib.svgir_pbgi_irradiance_sample.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 10
+    lib.svgir_pbgi_irradiance_sample_backward.restype = C.c_int
+    lib.svgir_pbgi_irradiance_sample_backward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 13
+    lib.svgir_pbgi_irradiance.restype = C.c_int
+    lib.svgir_pbgi_irradiance.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 9
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -134,7 +141,8 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_mask_scan_work_words", "svgir_mask_scan", "svgir_gather_rows", "svgir_densify_masks", "svgir_append_rows",
            "svgir_split_transform", "svgir_bvh_bytes", "svgir_bvh_build",
            "svgir_bvh_trace_visibility", "svgir_pbgi_bvh_bytes", "svgir_pbgi_bvh_build", "svgir_pbgi_bvh_export",
-           "svgir_pbgi_trace_radiance", "svgir_knn_bytes", "svgir_knn_mean_dist", "svgir_knn_topk")
+           "svgir_pbgi_trace_radiance", "svgir_knn_bytes", "svgir_knn_mean_dist", "svgir_knn_topk", "svgir_pbgi_irradiance_sample",
+           "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance")
 
 
 _scope = threading.local()

@@ -2,12 +2,74 @@
 `set_proxy_from_gaussian_model` (pbgi/renderer.py:429-466), `build_bvh` (:582-594) and `render_radiance_with_sampling_SH`
 (:596-615) with their names, arguments, result order / shapes / dtypes and the attributes the caller reads back
 (`LBVHNode_info`, `LBVHNode_aabb`, `hemi_index_buffers`, `uv_buffers`).  The slang kernels are the HIP kernels of
-svg-ir_amd/csrc/pbgi.hip; no CPU / PyTorch fallback."""
+svg-ir_amd/csrc/pbgi.hip; no CPU / PyTorch fallback.
+
+The consumers of those caches are here as well: `render_irradiance_sample` (:181-226, 748-751; the radiance-consistency loss of
+`GaussianModel.get_radiance_loss`, scene/gaussian_model.py:544-575) and `render_irradiance` (:100-178, 743-746;
+`GaussianModel.calculate_radiance`, :530-542), with the reference's names and positional arguments -> svg-ir_amd/csrc/irradiance.hip.
+The contract, and what it decides where the reference is undefined, is in include/svgir_raster.h."""
 import torch
 
 from gaussian_renderer import _native
 
 from .bvhhelpers import GsBvh, _lib
+
+
+def _irradiance_inputs(what, N, S, hit, uvs, envmap, ray_directions, normals, albedos, roughnesses):
+    """Contiguous fp32 / int32 views of the kernels' arguments on the caches' device, shapes checked."""
+    if hit is None or uvs is None:
+        raise RuntimeError(f"{what}: hemi_index_buffers / uv_buffers are not set (GaussianModel.update_radiace sets them after "
+                           "render_radiance_with_sampling_SH)")
+    N, S = int(N), int(S)
+    for t in (hit, uvs, envmap, ray_directions, normals, albedos, roughnesses):
+        if not t.is_cuda:
+            raise RuntimeError(f"{what} needs CUDA/HIP tensors (there is no CPU path)")
+    if hit.numel() != N * S or uvs.numel() != N * S * 2 or int(hit.shape[0]) != N:
+        raise ValueError(f"{what}: hemi_index_buffers {tuple(hit.shape)} / uv_buffers {tuple(uvs.shape)} do not hold N = {N} rows of S = {S} samples")
+    if S < 1:
+        raise ValueError(f"{what}: S must be at least 1")
+    dev = hit.device
+    f = lambda t, shape: _native.f32c(t.detach(), dev).reshape(shape)
+    hit_i = hit.detach().reshape(N, S)
+    if hit_i.dtype != torch.int32:
+        hit_i = hit_i.to(torch.int32)
+    return dev, (f(ray_directions, (N, S, 3)), f(envmap, (N, S, 3)), f(normals, (N, 12)), f(albedos, (N, 12)), f(roughnesses, (N, 4)),
+                 hit_i.contiguous(), f(uvs, (N, S, 2)))
+
+
+class _IrradianceSample(torch.autograd.Function):
+    """svgir_pbgi_irradiance_sample / _backward: differentiable in envmap, albedos and roughnesses (the reference's DiffTensorViews whose
+    gradient is not identically zero); directions, normals, uvs and the indices get none."""
+
+    @staticmethod
+    def forward(ctx, N, S, sample_indices, envmap, albedos, roughnesses, ray_directions, normals, hit, uvs):
+        dev, t = _irradiance_inputs("render_irradiance_sample", N, S, hit, uvs, envmap, ray_directions, normals, albedos, roughnesses)
+        N, S = int(N), int(S)
+        if not sample_indices.is_cuda or sample_indices.numel() != N:
+            raise ValueError("render_irradiance_sample: sample_indices must be N indices on the GPU")
+        idx = sample_indices.detach().reshape(N).to(device=dev, dtype=torch.int32).contiguous()
+        with torch.cuda.device(dev):
+            out = _native.out_tensor((N, 3), torch.float32, dev)
+            _native.check(_lib.svgir_pbgi_irradiance_sample(N, S, _native.ptr(idx), *[_native.ptr(x) for x in t], _native.ptr(out),
+                                                            _native.stream_ptr(dev)), "pbgi_irradiance_sample")
+        ctx.save_for_backward(idx, *t)
+        ctx.dims = (N, S, envmap.shape, albedos.shape, roughnesses.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, *t = ctx.saved_tensors
+        N, S, env_shape, alb_shape, rough_shape = ctx.dims
+        dev = idx.device
+        with torch.cuda.device(dev):
+            g = _native.f32c(g, dev)
+            d_env = _native.out_tensor((N, S, 3), torch.float32, dev)
+            d_alb = _native.out_tensor((N, 12), torch.float32, dev)
+            d_rough = _native.out_tensor((N, 4), torch.float32, dev)
+            _native.check(_lib.svgir_pbgi_irradiance_sample_backward(N, S, _native.ptr(idx), *[_native.ptr(x) for x in t], _native.ptr(g),
+                                                                     _native.ptr(d_env), _native.ptr(d_alb), _native.ptr(d_rough),
+                                                                     _native.stream_ptr(dev)), "pbgi_irradiance_sample_backward")
+        return (None, None, None, d_env.reshape(env_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape), None, None, None, None)
 
 
 class Renderer:
@@ -62,3 +124,26 @@ class Renderer:
                                                         *[_native.ptr(t) for t in args], rad.data_ptr(), vis.data_ptr(), hit.data_ptr(),
                                                         uvs.data_ptr(), _native.stream_ptr(dev)), "pbgi_trace_radiance")
         return rad, vis, hit, uvs
+
+    def render_irradiance(self, N, S, envmap, ray_directions, centers, scales, rotates, normals, albedos, roughnesses, metallics, opacities, SHs):
+        """The incident-radiance cache under `envmap` [N,S,3] (pbgi/renderer.py:743-746): [N,S,3], per (i,p) the irradiance the first hit
+        of ray p of surfel i reflects towards i, with per-corner roughness and the n.l cosine.  Reads `self.hemi_index_buffers`
+        ([N,S,1] int32) and `self.uv_buffers` ([N,S,2]).  centers, scales, rotates, metallics, opacities and SHs never reach the
+        reference's result and are ignored.  FORWARD ONLY: the result carries no autograd graph (nobody differentiates it in the
+        reference: calculate_radiance feeds update_radiance_with_calc)."""
+        dev, t = _irradiance_inputs("render_irradiance", N, S, self.hemi_index_buffers, self.uv_buffers, envmap, ray_directions, normals,
+                                    albedos, roughnesses)
+        N, S = int(N), int(S)
+        with torch.cuda.device(dev):
+            out = _native.out_tensor((N, S, 3), torch.float32, dev)
+            _native.check(_lib.svgir_pbgi_irradiance(N, S, *[_native.ptr(x) for x in t], _native.ptr(out), _native.stream_ptr(dev)),
+                          "pbgi_irradiance")
+        return out
+
+    def render_irradiance_sample(self, N, S, sample_indices, envmap, ray_directions, centers, scales, rotates, normals, albedos, roughnesses,
+                                 metallics, opacities, SHs):
+        """[N,3]: the same sum for ONE ray per surfel, p = sample_indices[i] ([N] or [N,1] integers), with the reference's two quirks
+        (corner 0's roughness for all corners, no cosine; pbgi/renderer.py:748-751).  Differentiable in envmap, albedos and roughnesses;
+        every other argument gets no gradient (None).  Reads `self.hemi_index_buffers` and `self.uv_buffers`."""
+        return _IrradianceSample.apply(N, S, sample_indices, envmap, albedos, roughnesses, ray_directions, normals, self.hemi_index_buffers,
+                                       self.uv_buffers)

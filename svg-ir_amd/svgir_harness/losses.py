@@ -1,6 +1,7 @@
 """L1 and SSIM of a rendered image against the ground truth, fused (csrc/loss.hip): the reference's
 `F.l1_loss(image, gt)` + `ssim(image, gt)` (gaussian_renderer/svgss.py:281-289, render.py:150-151;
-utils/loss_utils.py:21-64), one kernel forward, one backward."""
+utils/loss_utils.py:21-64), one kernel forward, one backward; and the radiance-consistency loss of stage 2 (`radiance_loss`: scene/gaussian_model.py:544-575)
+around the irradiance kernel of csrc/irradiance.hip."""
 import ctypes as C
 
 import torch
@@ -118,3 +119,25 @@ def ssim(img1, img2, window_size=11, size_average=True):
     if window_size != 11 or not size_average:
         raise NotImplementedError("only the reference's call form ssim(img1, img2) is implemented")
     return l1_ssim(img1, img2)[1]
+
+
+def radiance_loss(renderer, xyz, camera_center, geo_normal, incident_dirs, visibility, envmap, normals12, albedos, roughnesses, radiances,
+                  radiance_ratio):
+    """`GaussianModel.get_radiance_loss` (scene/gaussian_model.py:544-575) on explicit tensors: the view direction of every surfel
+    (xyz [N,3] - camera_center [3]) is reflected about its geometric normal, the incident sample that looks most along the reflection
+    and is occluded -- the largest (incident_dir . reflection) * (1 - visibility), the first index on ties -- is chosen, the irradiance
+    its first hit reflects back is evaluated by `renderer.render_irradiance_sample` (a pbgi.Renderer whose hemi_index_buffers /
+    uv_buffers are set) under `envmap` [N,S,3], and the L1 distance to the cached radiance of that sample,
+    nan_to_num(radiances.detach() * radiance_ratio) [N,S,3], is returned.  incident_dirs [N,S,3], visibility [N,S,1] or [N,S],
+    normals12 / albedos [N,12], roughnesses [N,4].  The selection and the L1 are plain torch ([N,S] work); gradients reach envmap,
+    albedos and roughnesses through the kernel's backward and radiance_ratio through autograd."""
+    N, S = int(incident_dirs.shape[0]), int(incident_dirs.shape[1])
+    view_dirs = torch.nn.functional.normalize(xyz - camera_center, dim=-1)
+    view_reflect = 2 * torch.sum(geo_normal * view_dirs, dim=-1, keepdim=True) * geo_normal + view_dirs
+    n_d_i = torch.sum(incident_dirs * view_reflect[:, None], dim=-1) * (1 - visibility.reshape(N, S))
+    max_idx = torch.argmax(n_d_i.detach(), dim=-1).unsqueeze(-1).int()
+    radiance = renderer.render_irradiance_sample(N, S, max_idx, envmap, incident_dirs, None, None, None, normals12, albedos, roughnesses,
+                                                 None, None, None)
+    target = torch.nan_to_num(radiances.detach() * radiance_ratio, nan=0.0)
+    target = target.gather(1, max_idx.long().unsqueeze(-1).expand(-1, -1, 3)).squeeze(-2)
+    return torch.nn.functional.l1_loss(radiance, target)
