@@ -91,18 +91,7 @@ __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __
         }
 #pragma unroll 8
         for (int b = g * GS; b < (int)blockIdx.x; b++) pre += table[(size_t)b * 256 + t];
-        uint32_t incl = tot;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();   // (also: the wave counters are zero)
-        uint32_t woff = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) woff += w < wave ? wtot[w] : 0u;
-        cursor = woff + incl - tot + pre;
+        cursor = block_excl_scan<4>(tot, wtot) + pre;   // (its barrier also: the wave counters are zero)
     }
     // rank of every key among the keys of its WAVE with the same digit: wave-level digit matching (ballots) against a
     // wave-private digit counter in LDS -- no workgroup barrier inside the ranking
@@ -110,11 +99,7 @@ __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __
     for (int c = 0; c < ITEMS; c++) {
         const bool valid = base + c * 64 + lane < n;
         const uint32_t d = (ks[c] >> bit_lo) & mask;
-        unsigned long long same = __ballot(valid);
-        for (int b = 0; b < nbits; b++) {
-            const unsigned long long m = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? m : ~m;
-        }
+        const unsigned long long same = wave_match(d, nbits, valid);
         const uint32_t in_round = (uint32_t)__popcll(same & lt_mask);
         const uint32_t prior = wcnt[wave][d];   // (the DS operations of a wave execute in order: every lane reads before the leader writes)
         rk[c] = prior + in_round;
@@ -129,19 +114,8 @@ __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __
         __shared__ uint32_t bstart[256], gcur[256];
         const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t], c3 = wcnt[3][t];
         const uint32_t bc = c0 + c1 + c2 + c3;            // keys of digit t in this block
-        uint32_t incl = bc;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        __syncthreads();                                   // (wtot was read by every thread above)
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        uint32_t woff = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) woff += w < wave ? wtot[w] : 0u;
-        const uint32_t bs = woff + incl - bc;              // first slot of digit t in the block's staging order
+        // first slot of digit t in the block's staging order (wtot was last read in front of the barrier above)
+        const uint32_t bs = block_excl_scan<4>(bc, wtot);
         bstart[t] = bs; gcur[t] = cursor;
         wcnt[0][t] = bs; wcnt[1][t] = bs + c0; wcnt[2][t] = bs + c0 + c1; wcnt[3][t] = bs + c0 + c1 + c2;   // the waves' staging cursors
         __syncthreads();
@@ -276,20 +250,10 @@ __global__ void __launch_bounds__(BLOCK) ts12_scatter_kernel(const uint32_t* __r
     uint32_t sum = 0;
 #pragma unroll
     for (int j = 0; j < PERMAX; j++) sum += tot[j];
-    uint32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wtot[wave] = incl;
 #pragma unroll
     for (int w = 0; w < 4; w++)
         for (int i = t; i < nbins / 2; i += BLOCK) reinterpret_cast<uint32_t*>(&wcnt[w][0])[i] = 0u;
-    __syncthreads();
-    uint32_t run = incl - sum;
-#pragma unroll
-    for (int w = 0; w < 4; w++) run += w < wave ? wtot[w] : 0u;
+    uint32_t run = block_excl_scan<4>(sum, wtot);   // (its barrier also: the wave counters are zero)
 #pragma unroll
     for (int j = 0; j < PERMAX; j++) {
         if (j < per) {
@@ -307,12 +271,7 @@ __global__ void __launch_bounds__(BLOCK) ts12_scatter_kernel(const uint32_t* __r
     for (int c = 0; c < ROUNDS; c++) {
         const bool valid = base + c * 64 + lane < n;
         const uint32_t d = ks[c] & (TS12_BINS - 1);
-        unsigned long long same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 12; b++) {
-            const unsigned long long m = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? m : ~m;
-        }
+        const unsigned long long same = wave_match(d, 12, valid);
         const uint32_t in_round = (uint32_t)__popcll(same & lt_mask);
         const uint32_t prior = wcnt[wave][d];   // (the DS operations of a wave execute in order: every lane reads before the leader writes)
         rk[c] = (uint16_t)(prior + in_round);
@@ -334,26 +293,8 @@ __global__ void __launch_bounds__(BLOCK) ts12_scatter_kernel(const uint32_t* __r
 }
 
 // ---- instance offsets: exclusive scan of tiles[order[i]] ---------------------------------------------------
-__device__ __forceinline__ uint32_t block_exclusive_scan_2048(uint32_t (&v)[8], uint32_t* wsum, uint32_t& total) {
-    // each thread owns 8 consecutive values; returns the exclusive prefix of the thread's first value
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t s = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) s += v[i];
-    uint32_t incl = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { const uint32_t x = wsum[w]; if (w < wave) woff += x; tot += x; }
-    total = tot;
-    return woff + incl - s;
-}
+// fold of two depth-key summaries {AND << 8 | OR} (identity 0xff00)
+__device__ __forceinline__ uint32_t key_top_fold(uint32_t a, uint32_t b) { return (a & b & 0xff00u) | ((a | b) & 0xffu); }
 
 // (the counts gathered here are parked, in depth order, in `offsets`: the write kernel reads them back with coalesced loads instead of
 // repeating the P random gathers, then overwrites them with the prefix)
@@ -367,8 +308,7 @@ __global__ void __launch_bounds__(BLOCK) offsets_reduce_kernel(const uint32_t* _
     if (threadIdx.x < 64) {   // this block's slice of the preprocess waves' depth-key summaries {AND << 8 | OR}: SCAN_BLOCK_ELEMS / 64 = 32 entries
         const int j = blockIdx.x * (SCAN_BLOCK_ELEMS / 64) + (int)threadIdx.x;
         uint32_t kv = (threadIdx.x < SCAN_BLOCK_ELEMS / 64 && j < n_key_top) ? key_top[j] : 0xff00u;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)kv, d); kv = (kv & o & 0xff00u) | ((kv | o) & 0xffu); }
+        kv = wave_reduce(kv, key_top_fold);
         if (threadIdx.x == 0) block_key[blockIdx.x] = kv;
     }
     uint32_t v[8];
@@ -387,8 +327,10 @@ __global__ void __launch_bounds__(BLOCK) offsets_reduce_kernel(const uint32_t* _
 #pragma unroll
         for (int i = 0; i < 8; i++) if (base + i < n) counts_out[base + i] = v[i];
     }
-    uint32_t total;
-    block_exclusive_scan_2048(v, wsum, total);
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) sum += v[i];
+    const uint32_t total = block_sum<4>(sum, wsum);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -411,23 +353,18 @@ __global__ void __launch_bounds__(BLOCK) offsets_write_kernel(int n,
 #pragma unroll
         for (int i = 0; i < 8; i++) v[i] = (base + i < n) ? offsets[base + i] : 0u;
     }
-    // sum of the preceding blocks' totals (the block sums are few: every block adds them up itself, no scan kernel)
     const bool last = blockIdx.x == (unsigned)(nblocks - 1);
-    uint32_t pre = 0, kv = 0xff00u;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += BLOCK) pre += block_sums[b];
-    if (last)   // the last block walks all the blocks anyway: it also folds their depth-key summaries {AND << 8 | OR}
-        for (int b = threadIdx.x; b < nblocks; b += BLOCK) { const uint32_t x = block_key[b]; kv = (kv & x & 0xff00u) | ((kv | x) & 0xffu); }
+    uint32_t kv = 0xff00u;
+    if (last)   // the last block also folds the blocks' depth-key summaries
+        for (int b = threadIdx.x; b < nblocks; b += BLOCK) kv = key_top_fold(kv, block_key[b]);
+    kv = wave_reduce(kv, key_top_fold);
+    if ((threadIdx.x & 63) == 0) ksum[threadIdx.x >> 6] = kv;
+    // sum of the preceding blocks' totals (the block sums are few: every block adds them up itself, no scan kernel)
+    const uint32_t before = blocks_before<4>(block_sums, (int)blockIdx.x, psum);   // (its barrier also publishes ksum)
+    uint32_t sum = 0, total;
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        pre += __shfl_xor(pre, d);
-        const uint32_t o = (uint32_t)__shfl_xor((int)kv, d);
-        kv = (kv & o & 0xff00u) | ((kv | o) & 0xffu);
-    }
-    if ((threadIdx.x & 63) == 0) { psum[threadIdx.x >> 6] = pre; ksum[threadIdx.x >> 6] = kv; }
-    uint32_t total;
-    uint32_t run = block_exclusive_scan_2048(v, wsum, total);   // contains a __syncthreads()
-    const uint32_t before = psum[0] + psum[1] + psum[2] + psum[3];
-    run += before;
+    for (int i = 0; i < 8; i++) sum += v[i];
+    uint32_t run = before + block_excl_scan<4>(sum, wsum, &total);
     uint32_t span = 0;   // 1 + position (in depth order) of this thread's last Gaussian that touches a tile
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -437,12 +374,11 @@ __global__ void __launch_bounds__(BLOCK) offsets_write_kernel(int n,
     }
     // total_out[3] = the visible span of the depth order: order[0 .. span) holds every Gaussian with tiles > 0 (they sort in front of
     // the culled ones) -- the working set of the fused shading (api.hip).  One atomic per wave that holds a visible Gaussian.
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) span = max(span, (uint32_t)__shfl_xor((int)span, d));
+    span = wave_reduce_max(span);
     if ((threadIdx.x & 63) == 0 && span != 0u) atomicMax(total_out + 3, span);
     if (last && threadIdx.x == 0) {
         const uint32_t R = before + total;
-        const uint32_t summary = (ksum[0] & ksum[1] & ksum[2] & ksum[3] & 0xff00u) | ((ksum[0] | ksum[1] | ksum[2] | ksum[3]) & 0xffu);
+        const uint32_t summary = key_top_fold(key_top_fold(ksum[0], ksum[1]), key_top_fold(ksum[2], ksum[3]));
         total_out[0] = R;
         total_out[2] = summary;
         // the host's copy: tagged 8-byte stores into pinned host memory -- no copy operation and no event on the stream; the host
@@ -493,12 +429,7 @@ __global__ void __launch_bounds__(BLOCK) emit_kernel(int P, const uint32_t* __re
         rec[(size_t)g * REC + R_RECT] = __builtin_bit_cast(float, rect);
     }
     // local exclusive offsets of the wave's Gaussians and the run's length
-    uint32_t incl = n;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += o;
-    }
+    const uint32_t incl = wave_incl_scan_u32(n);   // (every lane of the wave is here: the exit above is per wave)
     const uint32_t loc = incl - n;
     const uint32_t M = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)(off - loc));   // (lane 0 is valid; off = base + loc on every valid lane)
@@ -578,11 +509,8 @@ __global__ void __launch_bounds__(1024) order_xcd_kernel(const uint32_t* __restr
         if (i < p0) before += both(len);
         zeros += len == 0u ? 1u : 0u;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        before += (unsigned long long)__shfl_xor((long long)before, d);
-        zeros += (uint32_t)__shfl_xor((int)zeros, d);
-    }
+    before = wave_reduce_add(before);
+    zeros = wave_reduce_add(zeros);
     if (lane == 0) { wsum2[wave] = before; wzero[wave] = zeros; }
     __syncthreads();
     unsigned long long run = 0;
@@ -590,41 +518,19 @@ __global__ void __launch_bounds__(1024) order_xcd_kernel(const uint32_t* __restr
 #pragma unroll
     for (int w = 0; w < 16; w++) { run += wsum2[w]; n_empty += wzero[w]; }
     // ---- bucket cursors of this XCD
-    const uint32_t hv = hist[t];
-    uint32_t incl = hv;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0, n_mine = 0;
-    for (int w = 0; w < 16; w++) { woff += w < wave ? wsum[w] : 0u; n_mine += wsum[w]; }
-    hist[t] = woff + incl - hv;
+    uint32_t n_mine;
+    hist[t] = block_excl_scan<16>(hist[t], wsum, &n_mine);
     __syncthreads();
     // ---- prefixes of this workgroup's eighth, in index order: 1024 items per round (wave scans + a scan over the 16 wave totals)
-    auto scan32 = [](uint32_t v) {
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-        return v;
-    };
     for (int i0 = p0; i0 < p1; i0 += 1024) {
         const int i = i0 + t;
         const unsigned long long v = both(i < p1 ? counts[i] : 0u);
-        const unsigned long long inc = (unsigned long long)scan32((uint32_t)v) | ((unsigned long long)scan32((uint32_t)(v >> 32)) << 32);
+        // (the two halves are scanned on their own: no carry from the counts into the slots inside a wave)
+        const unsigned long long inc = (unsigned long long)wave_incl_scan_u32((uint32_t)v) | ((unsigned long long)wave_incl_scan_u32((uint32_t)(v >> 32)) << 32);
         __syncthreads();   // (wsum2 of the previous round has been read)
-        if (lane == 63) wsum2[wave] = inc;
-        __syncthreads();
-        unsigned long long wo = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) { const unsigned long long x = wsum2[w]; wo += w < wave ? x : 0ull; all += x; }
+        unsigned long long all;
+        const unsigned long long ex = run + block_excl_scan<16>(v, inc, wsum2, &all);
         if (i < p1) {
-            const unsigned long long ex = run + wo + inc - v;
             if (prefix) prefix[i] = (uint32_t)ex;
             if (slot_prefix) slot_prefix[i] = (uint32_t)(ex >> 32);
         }

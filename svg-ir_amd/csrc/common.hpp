@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "../../include/svgir_raster.h"
+#include "wave.hpp"
 
 namespace svgir {
 
@@ -63,8 +64,8 @@ inline size_t radix_table_words(int n) { return (size_t)256 * sort_blocks(n) + r
 // group totals of a sort over (up to) n elements; they must be ZERO when launch_radix_sort runs (the stage in front of each
 // sort clears them in passing: preprocess for the depth sort, emit for the tile sort)
 inline uint32_t* radix_gtot(uint32_t* table, int n) { return table + (size_t)256 * sort_blocks(n); }
-constexpr int SCAN_BLOCK_ELEMS = 2048;
-inline int scan_blocks(int n) { return n <= 0 ? 1 : (n + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS; }
+constexpr int SCAN_BLOCK_ELEMS = BLOCK * 8;   // elements per workgroup of every scan / compaction: 8 consecutive ones per thread
+SVGIR_HD inline int scan_blocks(int n) { return n <= 0 ? 1 : (n + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS; }
 
 struct GeomLayout {
     float* rec;            // [P*24]
@@ -106,7 +107,7 @@ inline GeomLayout geom_layout(char* base, int P) {
     g.key_top = (uint32_t*)take((p + 63) / 64 * 4);
     g.needed = (uint8_t*)take(p);
     g.shade_list = (uint32_t*)take(p * 4);
-    g.shade_work = (uint32_t*)take(((p + BLOCK * 8 - 1) / (BLOCK * 8) + 2) * 4);
+    g.shade_work = (uint32_t*)take(((size_t)scan_blocks(P) + 2) * 4);
     g.bytes = off;
     return g;
 }
@@ -525,14 +526,17 @@ void launch_image_ops(int W, int H, const float* view, float focal_x, float foca
                       const float* opacity, const float* depth, float* pseudo_normal, float* surface_xyz,
                       hipStream_t s);
 
-// ---- working set of a view (subset.hip): list[0 .. *count_dev) = the surfels with flags[i] != 0 (or, flags == nullptr, positive[i] > 0)
-// in index order, list[P-1-j] = the j-th other one; work: partition_work_words(P) uint32 of scratch
-constexpr int PART_ELEMS = BLOCK * 8;   // surfels per partition workgroup
-// the second half alone: `work` already holds the per-chunk counts of selected surfels (chunk = PART_ELEMS consecutive surfels), e.g.
-// counted in passing by the live-segment kernel of the backward
+// ---- stream compaction (subset.hip; two launches: per-chunk counts, then every workgroup sums the counts in front of it and scatters;
+// chunk = SCAN_BLOCK_ELEMS consecutive elements; work: scan_blocks(P) chunk counts (+ the callers' own words behind them)) ----
+// working set of a view: list[0 .. *count_dev) = the surfels with flags[i] != 0 (or, flags == nullptr, positive[i] > 0) in index order,
+// list[P-1-j] = the j-th other one; work: partition_work_words(P) uint32 of scratch
+// the second half alone: `work` already holds the per-chunk counts of selected surfels, e.g. counted in passing by the live-segment
+// kernel of the backward (select_count_chunk)
 void launch_partition_scatter(int P, const float* positive, uint32_t* list, const uint32_t* work, uint32_t* count_dev, hipStream_t s);
 size_t partition_work_words(int P);
 void launch_partition(int P, const uint8_t* flags, const float* positive, uint32_t* list, uint32_t* work, uint32_t* count_dev, hipStream_t s);
+// the front alone: list[0 .. *count_dev) = the i with flags[i] != 0 in index order; nothing is written beyond list[*count_dev)
+void launch_compact(int P, const uint8_t* flags, uint32_t* list, uint32_t* work, uint32_t* count_dev, hipStream_t s);
 // zeroes row list[P-1-j], j < P - *count_dev, of up to 6 row-major fp32 tensors (null tensors are skipped)
 void launch_zero_rows(int P, const uint32_t* list, const uint32_t* count_dev, float* const* tensors, const int* row_floats, int n, hipStream_t s);
 
@@ -548,42 +552,19 @@ int shade_backward_impl(const svgir_shade_params* p, const float* dL_dreduced, c
 
 #if defined(__HIPCC__)
 // ---- device helpers ----------------------------------------------------------------------------------------
-// Wave64 sum with DPP row shifts + row broadcasts (gfx9 family); the total lands in lane 63.  All 64 lanes must
-// be active.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {   // v of the lane DPP control CTRL names; 0 where it names none
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_scan_last(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xa, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, false));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {  // uniform result
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave_scan_last(v)), 63));
-}
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
-// Ordering point for LDS traffic that is private to ONE wave (single-wave workgroups, or per-wave LDS regions): the DS
-// operations of a wave execute in issue order, so only the compiler has to be kept from moving LDS accesses across it.
-// Unlike __syncthreads() it does not drain vmcnt, i.e. it never waits for outstanding global atomics / stores.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// inclusive wave64 scan on the VALU (DPP row shifts + row broadcasts); all 64 lanes must be active
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-    return v;
+
+// ---- stream compaction: the two predicates and the count half (the count kernel of subset.hip; seg_build_kernel piggy-backs it) ----
+struct SelNonZero { const uint8_t* p; __device__ bool operator()(int i) const { return p[i] != 0; } };
+struct SelPositive { const float* p; __device__ bool operator()(int i) const { return p[i] > 0.f; } };
+// number of selected elements of chunk `chunk` of 0..n-1, in every thread; called by all BLOCK threads; wsum[BLOCK / 64]: wave.hpp BARRIERS
+template <class Sel>
+__device__ __forceinline__ uint32_t select_count_chunk(Sel sel, int chunk, int n, uint32_t* wsum) {
+    const int base = chunk * SCAN_BLOCK_ELEMS + (int)threadIdx.x * 8;
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) c += (base + i < n && sel(base + i)) ? 1u : 0u;
+    return block_sum<BLOCK / 64>(c, wsum);
 }
 
 // ---- dispatch order of the composite waves (see DISP_NCLS) ----

@@ -99,9 +99,7 @@ __global__ void __launch_bounds__(BLOCK) knn_morton_kernel(int P, const float* _
 // wave reduce of a box; every lane ends with the result
 __device__ __forceinline__ void knn_wave_box(float lo[3], float hi[3]) {
 #pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], d)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], d)); }
+    for (int c = 0; c < 3; c++) { lo[c] = wave_reduce_min(lo[c]); hi[c] = wave_reduce_max(hi[c]); }
 }
 
 // ---- Morton-ordered copy of the points + one box per 64 of them (a wave = a group) ------------------------------------------------

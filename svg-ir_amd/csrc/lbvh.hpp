@@ -75,9 +75,7 @@ inline LbvhTree lbvh_tree_layout(BlobCursor& c, int P) {
 __device__ __forceinline__ void whole_box_add(const float lo[3], const float hi[3], uint32_t* __restrict__ whole) {
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        float mn = lo[c], mx = hi[c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn = fminf(mn, __shfl_xor(mn, d)); mx = fmaxf(mx, __shfl_xor(mx, d)); }
+        const float mn = wave_reduce_min(lo[c]), mx = wave_reduce_max(hi[c]);
         if ((threadIdx.x & 63) == 0) { atomicMin(&whole[c], f2ord(mn)); atomicMax(&whole[3 + c], f2ord(mx)); }
     }
 }

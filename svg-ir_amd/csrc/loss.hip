@@ -142,8 +142,7 @@ __global__ void __launch_bounds__(256) ssim_reduce_kernel(const float* __restric
     __shared__ double red[2][4];
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < nblk; i += 256) { a += (double)partial[2 * i]; b += (double)partial[2 * i + 1]; }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); }
+    a = wave_reduce_add(a); b = wave_reduce_add(b);
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
     __syncthreads();
     if (threadIdx.x == 0) {

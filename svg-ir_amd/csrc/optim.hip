@@ -7,7 +7,7 @@
 //   * `add_densification_stats`     (scene/gaussian_model.py:1270-1276) -> one kernel,
 //   * the boolean-mask indexing of `_prune_optimizer` / `prune_points` (scene/gaussian_model.py:1020-1062: `t[mask]` for every
 //     parameter, both Adam moments and five bookkeeping arrays, ~45 index kernels each with its own mask scan) -> one scan of the
-//     mask + one multi-tensor row gather.
+//     mask (the front-only compaction of csrc/subset.hip) + one multi-tensor row gather.
 // Arithmetic of the Adam step = torch.optim.Adam (amsgrad=False, weight_decay=0, maximize=False), single-tensor form:
 //   m <- m + (1 - b1) (g - m);  v <- v b2 + (1 - b2) g g;  p <- p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // with the bias corrections evaluated on the host in double precision like torch does.
@@ -80,59 +80,7 @@ __global__ void __launch_bounds__(BLOCK) densify_stats_kernel(int P, const float
     }
 }
 
-// ---- mask -> list of kept rows (order preserving) ----------------------------------------------------------------
-constexpr int SCAN_ELEMS = BLOCK * 8;
-__global__ void __launch_bounds__(BLOCK) mask_count_kernel(const uint8_t* __restrict__ keep, int P, uint32_t* __restrict__ block_sums) {
-    __shared__ uint32_t wsum[BLOCK / 64];
-    const int base = blockIdx.x * SCAN_ELEMS + threadIdx.x * 8;
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) c += (base + i < P && keep[base + i]) ? 1u : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (int w = 0; w < BLOCK / 64; w++) s += wsum[w];
-        block_sums[blockIdx.x] = s;
-    }
-}
-__global__ void __launch_bounds__(BLOCK) mask_scatter_kernel(const uint8_t* __restrict__ keep, int P, const uint32_t* __restrict__ block_sums,
-                                                             int nblocks, uint32_t* __restrict__ kept, uint32_t* __restrict__ count_out) {
-    __shared__ uint32_t wsum[BLOCK / 64];
-    __shared__ uint32_t before_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t pre = 0;
-    for (int b = t; b < (int)blockIdx.x; b += BLOCK) pre += block_sums[b];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) pre += (uint32_t)__shfl_xor((int)pre, d);
-    if (lane == 0) wsum[wave] = pre;
-    __syncthreads();
-    if (t == 0) { uint32_t s = 0; for (int w = 0; w < BLOCK / 64; w++) s += wsum[w]; before_s = s; }
-    __syncthreads();
-    const int base = blockIdx.x * SCAN_ELEMS + t * 8;
-    uint32_t k[8], c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) { k[i] = (base + i < P && keep[base + i]) ? 1u : 0u; c += k[i]; }
-    uint32_t incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += o;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wave; w++) woff += wsum[w];
-    uint32_t pos = before_s + woff + incl - c;
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (k[i]) kept[pos++] = (uint32_t)(base + i);
-    if ((int)blockIdx.x == nblocks - 1 && t == BLOCK - 1) count_out[0] = pos;
-}
-
+// ---- mask -> list of kept rows (order preserving): svgir_mask_scan = the front-only compaction of csrc/subset.hip; then the row gather ----
 struct GatherTable {
     const uint32_t* src[ADAM_MAX]; uint32_t* dst[ADAM_MAX];
     int words[ADAM_MAX];              // 4-byte words per row
@@ -324,15 +272,13 @@ int svgir_densify_stats(int32_t P, const float* viewspace_grad, int32_t grad_str
     return hipGetLastError() == hipSuccess ? SVGIR_OK : SVGIR_ERR_HIP;
 }
 
-size_t svgir_mask_scan_work_words(int32_t P) { return (size_t)((P > 0 ? P : 1) + svgir::SCAN_ELEMS - 1) / svgir::SCAN_ELEMS + 1; }
+size_t svgir_mask_scan_work_words(int32_t P) { return (size_t)svgir::scan_blocks(P) + 1; }
 
 int svgir_mask_scan(int32_t P, const uint8_t* keep, uint32_t* kept, uint32_t* work, uint32_t* count_dev, void* stream) {
     using namespace svgir;
     if (P < 0 || !count_dev || (P > 0 && (!keep || !kept || !work))) return SVGIR_ERR_INVALID;
     if (P == 0) return hipMemsetAsync(count_dev, 0, 4, (hipStream_t)stream) == hipSuccess ? SVGIR_OK : SVGIR_ERR_HIP;
-    const int nb = (P + SCAN_ELEMS - 1) / SCAN_ELEMS;
-    hipLaunchKernelGGL(mask_count_kernel, dim3(nb), dim3(BLOCK), 0, (hipStream_t)stream, keep, P, work);
-    hipLaunchKernelGGL(mask_scatter_kernel, dim3(nb), dim3(BLOCK), 0, (hipStream_t)stream, keep, P, work, nb, kept, count_dev);
+    launch_compact(P, keep, kept, work, count_dev, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? SVGIR_OK : SVGIR_ERR_HIP;
 }
 

@@ -567,9 +567,7 @@ __global__ void __launch_bounds__(PBGI_WAVE) __attribute__((amdgpu_waves_per_eu(
 #if defined(SVGIR_DEV)
 #pragma unroll
     for (int i = 0; i < 6; i++) {
-        unsigned v = st_[i];
-#pragma unroll
-        for (int dd = 32; dd >= 1; dd >>= 1) v += (unsigned)__shfl_xor((int)v, dd);
+        const unsigned v = wave_reduce_add(st_[i]);
         if (lane == 0) atomicAdd(&g_pbgi_stats[i], (unsigned long long)v);
     }
 #endif

@@ -198,8 +198,7 @@ render_bwd_kernel(const RenderBwdArgs a) {
 
     // deepest contributor of the wave
     uint32_t wmax = last_contributor;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, d));
+    wmax = wave_reduce_max(wmax);
     if (wmax == 0) continue;
 
     // entry of list position i (0 = deepest) from the lanes' registers: per-lane positions through the LDS crossbar (no LDS memory),

@@ -197,8 +197,7 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
 
     // deepest contributor of the wave
     uint32_t wmax = last_contributor;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, d));
+    wmax = wave_reduce_max(wmax);
     if (wmax == 0) continue;
 
     // Replay state: the per-channel recurrences of the reference collapse into ONE scalar recurrence on

@@ -584,22 +584,15 @@ __global__ void __launch_bounds__(256) seg_build_kernel(const RenderArgs a, int 
         for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < ne; i += (int)gridDim.x * 256) shade_table_entry(tabs, i);
         for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < tabs.nzero; i += (int)gridDim.x * 256) tabs.zero[i] = 0.f;
     }
-    // ... and the first half of the partition "surfels that received a blend weight" (subset.hip): per chunk of PART_ELEMS surfels the
-    // number with weights > 0 (the scatter half is one small launch behind this one instead of two)
+    // ... and the first half of the partition "surfels that received a blend weight" (subset.hip): per chunk of SCAN_BLOCK_ELEMS surfels
+    // the number with weights > 0 (the scatter half is one small launch behind this one instead of two)
     if (weights) {
         __shared__ uint32_t pw[4];
-        const int nch = (P + PART_ELEMS - 1) / PART_ELEMS;
+        const int nch = scan_blocks(P);
         for (int ch = (int)blockIdx.x; ch < nch; ch += (int)gridDim.x) {
-            const int base = ch * PART_ELEMS + (int)threadIdx.x * 8;
-            uint32_t c = 0;
-#pragma unroll
-            for (int i = 0; i < 8; i++) c += (base + i < P && weights[base + i] > 0.f) ? 1u : 0u;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
             __syncthreads();   // (pw of the previous chunk has been read)
-            if ((threadIdx.x & 63) == 0) pw[threadIdx.x >> 6] = c;
-            __syncthreads();
-            if (threadIdx.x == 0) part_sums[ch] = pw[0] + pw[1] + pw[2] + pw[3];
+            const uint32_t c = select_count_chunk(SelPositive{weights}, ch, P, pw);
+            if (threadIdx.x == 0) part_sums[ch] = c;
         }
     }
     if ((int)blockIdx.x >= nblk) return;   // (workgroups beyond the tile blocks only clear)
@@ -621,8 +614,7 @@ __global__ void __launch_bounds__(256) seg_build_kernel(const RenderArgs a, int 
     }
 #pragma unroll
     for (int c = 0; c < SEG_CLASSES; c++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { bef[c] += (uint32_t)__shfl_xor((int)bef[c], d); tot[c] += (uint32_t)__shfl_xor((int)tot[c], d); }
+        bef[c] = wave_reduce_add(bef[c]); tot[c] = wave_reduce_add(tot[c]);
         if (lane == 0) { red_b[c][wave] = bef[c]; red_t[c][wave] = tot[c]; }
     }
     uint32_t nseg[4] = {0u, 0u, 0u, 0u}, head[4] = {0u, 0u, 0u, 0u}, nd[4] = {0u, 0u, 0u, 0u}, pb[4] = {0u, 0u, 0u, 0u}, sb[4] = {0u, 0u, 0u, 0u}, r0 = 0, r1 = 0;
@@ -651,26 +643,15 @@ __global__ void __launch_bounds__(256) seg_build_kernel(const RenderArgs a, int 
         nfull += nseg[w] - (lcls[w] == 0 ? 0u : 1u);
         if (lcls[w] != 0) npart += 1ull << (16 * (lcls[w] - 1));
     }
-    uint32_t ifull = nfull;
-    unsigned long long ipart = npart;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t of = (uint32_t)__shfl_up((int)ifull, d);
-        const unsigned long long op = (unsigned long long)__shfl_up((long long)ipart, d);
-        if (lane >= d) { ifull += of; ipart += op; }
-    }
-    if (lane == 63) { wfull[wave] = ifull; wpart[wave] = ipart; }
-    __syncthreads();
+    // (every thread of the workgroups < nblk is here; the first barrier also publishes red_b / red_t.  npart: one 64-bit add per step)
+    const uint32_t xfull = block_excl_scan<4>(nfull, wfull);
+    const unsigned long long xpart = block_excl_scan<4>(npart, wpart);
     uint32_t base[SEG_CLASSES], n_all = 0;
 #pragma unroll
     for (int c = 0; c < SEG_CLASSES; c++) {
         base[c] = n_all + (red_b[c][0] + red_b[c][1]) + (red_b[c][2] + red_b[c][3]);   // classes before + workgroups before
         n_all += (red_t[c][0] + red_t[c][1]) + (red_t[c][2] + red_t[c][3]);
     }
-    uint32_t xfull = ifull - nfull;
-    unsigned long long xpart = ipart - npart;
-#pragma unroll
-    for (int v = 0; v < 4; v++) { xfull += v < wave ? wfull[v] : 0u; xpart += v < wave ? wpart[v] : 0ull; }
     if (blockIdx.x == 0 && t == 0) a.seg_count[0] = n_all;
     if (nfull == 0 && npart == 0ull) return;
     uint32_t at[SEG_CLASSES];
@@ -716,7 +697,7 @@ void launch_seg_build(const RenderArgs& a, void* clear, size_t clear_bytes, cons
     const int T = a.gx * a.gy, nblk = (T + 255) / 256;
     const size_t n16 = clear ? (clear_bytes + 15) / 16 : 0;   // (the scratch regions are 256-byte aligned and padded: common.hpp align_up)
     int grid = (int)std::max<size_t>((size_t)nblk, std::min<size_t>((n16 + 255) / 256, 2048));
-    if (weights) grid = std::max(grid, std::min((P + PART_ELEMS - 1) / PART_ELEMS, 2048));
+    if (weights) grid = std::max(grid, std::min(scan_blocks(P), 2048));
     hipLaunchKernelGGL(seg_build_kernel, dim3(grid), dim3(256), 0, s, a, T, nblk, (uint4*)clear, n16, tabs, weights, P, part_sums);
 }
 

@@ -8,7 +8,8 @@
 // output rows of the back, so every output is still written completely.
 //   forward : selected <=> the surfel is a candidate of at least one 8x8 sub-tile (flag byte set by cull_kernel);
 //   backward: selected <=> out_weights > 0 (every other surfel has exactly-zero dL_dfeatures / dL_dvfeatures rows).
-// Two launches, like the mask scan of csrc/optim.hip: per-block counts, then every block sums the counts in front of it and scatters.
+// The selection is the project's one stream compaction (two launches: per-chunk counts, then every workgroup sums the counts in front of
+// it and scatters); the mask scan of csrc/optim.hip is its front-only form.
 #include <algorithm>
 
 #include "common.hpp"
@@ -17,71 +18,43 @@ namespace svgir {
 
 namespace {
 
-
-template <bool FLAGS>
-__device__ __forceinline__ bool part_pred(const uint8_t* __restrict__ flags, const float* __restrict__ values, int i) {
-    return FLAGS ? flags[i] != 0 : values[i] > 0.f;
+// Sel: SelNonZero / SelPositive (common.hpp).  BACK: also list the unselected ids from the end, list[n-1-j] = the j-th of them; without
+// it nothing is written beyond list[count).
+template <class Sel>
+__global__ void __launch_bounds__(BLOCK) select_count_kernel(Sel sel, int n, uint32_t* __restrict__ block_sums) {
+    __shared__ uint32_t wsum[BLOCK / 64];
+    const uint32_t s = select_count_chunk(sel, (int)blockIdx.x, n, wsum);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = s;
 }
 
-template <bool FLAGS>
-__global__ void __launch_bounds__(BLOCK) part_count_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ values, int P,
-                                                           uint32_t* __restrict__ block_sums) {
-    __shared__ uint32_t wsum[BLOCK / 64];
-    const int base = blockIdx.x * PART_ELEMS + threadIdx.x * 8;
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) c += (base + i < P && part_pred<FLAGS>(flags, values, base + i)) ? 1u : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (int w = 0; w < BLOCK / 64; w++) s += wsum[w];
-        block_sums[blockIdx.x] = s;
-    }
-}
-
-template <bool FLAGS>
-__global__ void __launch_bounds__(BLOCK) part_scatter_kernel(const uint8_t* __restrict__ flags, const float* __restrict__ values, int P,
-                                                             const uint32_t* __restrict__ block_sums, int nblocks,
-                                                             uint32_t* __restrict__ list, uint32_t* __restrict__ count_out) {
-    __shared__ uint32_t wsum[BLOCK / 64];
-    __shared__ uint32_t before_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t pre = 0;
-    for (int b = t; b < (int)blockIdx.x; b += BLOCK) pre += block_sums[b];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) pre += (uint32_t)__shfl_xor((int)pre, d);
-    if (lane == 0) wsum[wave] = pre;
-    __syncthreads();
-    if (t == 0) { uint32_t s = 0; for (int w = 0; w < BLOCK / 64; w++) s += wsum[w]; before_s = s; }
-    __syncthreads();
-    const int base = blockIdx.x * PART_ELEMS + t * 8;
+template <class Sel, bool BACK>
+__global__ void __launch_bounds__(BLOCK) select_scatter_kernel(Sel sel, int n, const uint32_t* __restrict__ block_sums, int nblocks,
+                                                               uint32_t* __restrict__ list, uint32_t* __restrict__ count_out) {
+    __shared__ uint32_t psum[BLOCK / 64], wsum[BLOCK / 64];
+    const int t = threadIdx.x;
+    const uint32_t before = blocks_before<BLOCK / 64>(block_sums, (int)blockIdx.x, psum);
+    const int base = blockIdx.x * SCAN_BLOCK_ELEMS + t * 8;
     uint32_t k[8], c = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) { k[i] = (base + i < P && part_pred<FLAGS>(flags, values, base + i)) ? 1u : 0u; c += k[i]; }
-    uint32_t incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += o;
-    }
-    const uint32_t before = before_s;
-    __syncthreads();
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wave; w++) woff += wsum[w];
-    uint32_t pos = before + woff + incl - c;            // selected surfels in front of this thread's first
-    uint32_t npos = (uint32_t)base - pos;               // unselected ones in front of it
+    for (int i = 0; i < 8; i++) { k[i] = (base + i < n && sel(base + i)) ? 1u : 0u; c += k[i]; }
+    uint32_t pos = before + block_excl_scan<BLOCK / 64>(c, wsum);   // selected elements in front of this thread's first
+    uint32_t npos = (uint32_t)base - pos;                           // unselected ones in front of it
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        if (base + i >= P) break;
+        if (base + i >= n) break;
         if (k[i]) list[pos++] = (uint32_t)(base + i);
-        else list[(uint32_t)P - 1u - npos++] = (uint32_t)(base + i);
+        else if (BACK) list[(uint32_t)n - 1u - npos++] = (uint32_t)(base + i);
     }
     if ((int)blockIdx.x == nblocks - 1 && t == BLOCK - 1) count_out[0] = pos;
+}
+
+// work_out: the chunk counts are written first (the count launch); null: `work` already holds them
+template <class Sel, bool BACK>
+void launch_select(Sel sel, int n, uint32_t* list, uint32_t* work_out, const uint32_t* work, uint32_t* count_dev, hipStream_t s) {
+    if (n <= 0) return;
+    const int nb = scan_blocks(n);
+    if (work_out) hipLaunchKernelGGL(select_count_kernel<Sel>, dim3(nb), dim3(BLOCK), 0, s, sel, n, work_out);
+    hipLaunchKernelGGL((select_scatter_kernel<Sel, BACK>), dim3(nb), dim3(BLOCK), 0, s, sel, n, work, nb, list, count_dev);
 }
 
 struct ZeroRows {
@@ -105,24 +78,19 @@ __global__ void __launch_bounds__(BLOCK) zero_rows_kernel(const uint32_t* __rest
 
 }  // namespace
 
-size_t partition_work_words(int P) { return (size_t)((P > 0 ? P : 1) + PART_ELEMS - 1) / PART_ELEMS + 2; }
+size_t partition_work_words(int P) { return (size_t)scan_blocks(P) + 2; }
 
 void launch_partition(int P, const uint8_t* flags, const float* positive, uint32_t* list, uint32_t* work, uint32_t* count_dev, hipStream_t s) {
-    if (P <= 0) return;
-    const int nb = (P + PART_ELEMS - 1) / PART_ELEMS;
-    if (flags) {
-        hipLaunchKernelGGL(part_count_kernel<true>, dim3(nb), dim3(BLOCK), 0, s, flags, positive, P, work);
-        hipLaunchKernelGGL(part_scatter_kernel<true>, dim3(nb), dim3(BLOCK), 0, s, flags, positive, P, work, nb, list, count_dev);
-    } else {
-        hipLaunchKernelGGL(part_count_kernel<false>, dim3(nb), dim3(BLOCK), 0, s, flags, positive, P, work);
-        hipLaunchKernelGGL(part_scatter_kernel<false>, dim3(nb), dim3(BLOCK), 0, s, flags, positive, P, work, nb, list, count_dev);
-    }
+    if (flags) launch_select<SelNonZero, true>(SelNonZero{flags}, P, list, work, work, count_dev, s);
+    else launch_select<SelPositive, true>(SelPositive{positive}, P, list, work, work, count_dev, s);
 }
 
 void launch_partition_scatter(int P, const float* positive, uint32_t* list, const uint32_t* work, uint32_t* count_dev, hipStream_t s) {
-    if (P <= 0) return;
-    const int nb = (P + PART_ELEMS - 1) / PART_ELEMS;
-    hipLaunchKernelGGL(part_scatter_kernel<false>, dim3(nb), dim3(BLOCK), 0, s, (const uint8_t*)nullptr, positive, P, work, nb, list, count_dev);
+    launch_select<SelPositive, true>(SelPositive{positive}, P, list, nullptr, work, count_dev, s);
+}
+
+void launch_compact(int P, const uint8_t* flags, uint32_t* list, uint32_t* work, uint32_t* count_dev, hipStream_t s) {
+    launch_select<SelNonZero, false>(SelNonZero{flags}, P, list, work, work, count_dev, s);
 }
 
 void launch_zero_rows(int P, const uint32_t* list, const uint32_t* count_dev, float* const* tensors, const int* row_floats, int n, hipStream_t s) {

@@ -5,8 +5,9 @@ the edge it is named for, the oracle reproduces the reference's fixtures and tor
 Launch geometry the sizes are chosen around (csrc/optim.hip):
   adam_kernel          one workgroup per ADAM_CHUNK = 4096 elements of one tensor; the owning tensor is found by walking first_chunk[];
                        at most MAX_TENSORS = 32 tensors per launch (the harness splits longer lists)
-  mask_count / scatter SCAN_ELEMS = 2048 mask entries per workgroup; the scatter kernel sums the totals of the earlier blocks in a loop
-                       strided by SCAN_BLOCK = 256, so the loop's second trip needs more than 256 blocks (P > 524288)
+  mask count / scatter (the front-only compaction of csrc/subset.hip) SCAN_ELEMS = 2048 mask entries per workgroup; the scatter kernel
+                       sums the totals of the earlier blocks in a loop strided by SCAN_BLOCK = 256, so the loop's second trip needs more
+                       than 256 blocks (P > 524288)
   gather / append      grid.x sized by the widest tensor of the launch (narrower ones return early), grid.y = tensor
   stats / masks / split one thread per row, 256 per workgroup
 

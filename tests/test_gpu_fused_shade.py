@@ -167,6 +167,50 @@ def test_fused_view_is_bit_identical_small(built, training, lattice):
     assert 0.05 < frac < float((radii > 0).float().mean()) + 1e-6, frac
 
 
+@pytest.mark.parametrize("Ns,training", [(64, True), (200, False)])
+@pytest.mark.parametrize("P", [2047, 2048, 2049, 4097])
+def test_fused_view_is_bit_identical_at_the_chunk_edges(built, P, Ns, training):
+    """The view's working set is a partition of 0..P-1 built per chunk of 2048 surfels (csrc/subset.hip): one chunk less one, exactly
+    one, one more, two and one more.  Training widths: the backward's out_weights > 0 partition (counted in passing by the live-segment
+    kernel, scattered by launch_partition_scatter); Ns = 200: the contribution pre-pass and the flag-byte partition of the forward.
+    The suite poisons every output (SVGIR_POISON): a list entry written to the wrong place, or not written, is a NaN or a non-zero
+    row outside the subset, i.e. a difference to the unfused call."""
+    assert N.POISON
+    dev = torch.device(DEV)
+    S, VS = (4, 52) if training else (7, 64)
+    sc = scenes.surface_scene(P=P, W=176, H=144, seed=41, sh_degree=2, variant="svgss", S=S, VS=VS, scale_lo=0.01, scale_hi=0.06)
+    sct = runner.to_torch(sc, dev)
+    st = runner.settings(sct, "svgss")
+    d = _materials(sct, st, Ns, training, seed=3)
+    oa, _ = _compare(sct, st, d, scenes.upstream_grads(sc, "svgss", seed=6), training)
+    w = oa[7][:, 0]
+    assert 0 < int((w > 0).sum()) < P   # both sides of the partition are non-empty
+
+
+def test_fused_view_that_renders_nothing_writes_zero_gradients(built):
+    """Every surfel behind the camera: nothing is rendered, the backward partitions all-zero weights (launch_partition, every surfel on
+    the unselected side, P = one chunk and one more) -- every per-surfel gradient row is written and exactly zero."""
+    assert N.POISON
+    dev = torch.device(DEV)
+    P = 2049
+    sc = scenes.surface_scene(P=P, W=176, H=144, seed=41, sh_degree=2, variant="svgss", S=4, VS=52, scale_lo=0.01, scale_hi=0.06)
+    sct = runner.to_torch(sc, dev)
+    st = runner.settings(sct, "svgss")
+    axis = st.viewmatrix[:3, 2]   # view depth = means3D @ axis + viewmatrix[3, 2]
+    depth = sct["means3D"] @ axis + st.viewmatrix[3, 2]
+    sct["means3D"] = (sct["means3D"] - (depth.max() + 5.0) * axis / (axis @ axis)).contiguous()
+    d = _materials(sct, st, 64, True, seed=3)
+    gt = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in scenes.upstream_grads(sc, "svgss", seed=6).items()}
+    lv = _leaves(sct, d)
+    out, m2, _ = _fused(sct, st, d, lv, True)
+    assert out[0] == 0 and int((out[8] != 0).sum()) == 0
+    _loss(out, gt).backward()
+    torch.cuda.synchronize()
+    for k, g in list((k, v.grad) for k, v in lv.items()) + [("means2D", m2.grad)]:
+        assert g is not None and g.shape[0] == (lv[k].shape[0] if k != "means2D" else P), k
+        assert not torch.isnan(g).any() and float(g.abs().max()) == 0.0, k
+
+
 def test_fused_all_surfels_and_reduced_gradient(built):
     """all_surfels=True: the reference's semantics (every surfel shaded; `reduced` usable in a loss of its own, svgss.py:359-364)."""
     dev = torch.device(DEV)
