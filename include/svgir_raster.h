@@ -439,6 +439,36 @@ int svgir_l1_ssim_forward(const float* img1, const float* img2, int32_t C, int32
 int svgir_l1_ssim_backward(const float* img1, const float* img2, const float* dmaps, int32_t C, int32_t H, int32_t W,
                            float g_ssim_mean, float g_l1_mean, const float* g_dev, float* dL_dimg1, void* stream);
 
+/* The geometry terms both training stages add to the photometric loss (gaussian_renderer/render.py:157-188, svgss.py:297-313,
+ * 333-338), fused: one forward launch plus a small fixed-order reduction, one backward launch.  `terms` is a bit set:
+ *   1 surface  cos_loss(normal, depth2normal(depth, mask, camera)): normal [3,H,W], depth, mask [1,H,W], fovx / fovy / prcp as above;
+ *              the pseudo normal is never stored and is the one the depth2normal entry point above writes (one device function)
+ *   2 target   cos_loss(normal, target, weight=weight): target [3,H,W], weight [1,H,W] or NULL (= 1)  (the mono-normal term)
+ *   4 mask     mean(opacity * (1 - maxpool9(mask))): opacity, mask [1,H,W]; the 9 x 9 window is clipped to the image
+ *   8 entropy  -mean(m log o + (1 - m) log(1 - o)), o = clamp(opacity, float32(1e-6), float32(1 - 1e-6))
+ * The planes of a term that is not requested may be NULL.  W or H <= 0, no term, or a term without its planes: -1 and a message.
+ * cos_loss (utils/loss_utils.py:119-121): cos = sum_c (output_c * gt_c) * weight, evaluated in fp32 without contraction in the order
+ * ((o0 g0) w + (o1 g1) w) + (o2 g2) w; a pixel is selected iff cos < 1.f (a NaN cos is not selected and gets zero gradient; a
+ * background pixel, cos = 0, is selected and contributes 1); loss = sum_selected (1 - cos) / count; count == 0 gives NaN (torch's mean
+ * of an empty selection) and zero gradients.  The selection, the count and the gradients use that fp32 cos; the VALUE of a selected
+ * pixel is 1 - cos with cos in double (the surface form: on the pseudo normal restated in double from the same fp32 depth), so a loss
+ * carries no rounding beyond its final one to fp32.  The entropy gradient passes where lo <= opacity <= hi, bounds included.
+ *   forward : `partial` = 8 doubles per workgroup, as many workgroups as the partials function returns; `stats` [4][2] = {sum, count} per
+ *             term in bit order (count = H W for the two means), device doubles, and `losses` [4] = float32(sum / count), device
+ *             floats, both written for all four terms (zeros for the ones not requested).  No atomics: two runs give the same bits.
+ *   backward: `stats` as the forward wrote it; `g_dev` [4] = the upstream gradients of the four losses, device floats the host never
+ *             reads.  Each of dL_dnormal [3,H,W] (surface + target), dL_ddepth [1,H,W] (through the pseudo normal; a gather, no
+ *             atomics) and dL_dopacity [1,H,W] (mask + entropy) that is not NULL is written completely.  The mask, the target and the
+ *             weight get no gradient. */
+size_t svgir_geometry_loss_partials(int32_t W, int32_t H);
+int svgir_geometry_loss_forward(int32_t W, int32_t H, int32_t terms, const float* normal, const float* depth, const float* mask,
+                                const float* opacity, const float* target, const float* weight, float fovx, float fovy, float prcp_x,
+                                float prcp_y, double* partial, double* stats, float* losses, void* stream);
+int svgir_geometry_loss_backward(int32_t W, int32_t H, int32_t terms, const float* normal, const float* depth, const float* mask,
+                                 const float* opacity, const float* target, const float* weight, float fovx, float fovy, float prcp_x,
+                                 float prcp_y, const double* stats, const float* g_dev, float* dL_dnormal, float* dL_ddepth,
+                                 float* dL_dopacity, void* stream);
+
 /* The consumers of the rasterizer's gradients: Adam over the per-Gaussian parameter block, the
  * densification statistics, and the row compaction behind pruning (scene/gaussian_model.py:737-773, 1020-1062, 1270-1276).
  *

@@ -307,6 +307,15 @@ void stage_mark(StageMarks& t, const char* name) {
     }
     t.prev = e;
 }
+int report_error(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
 }  // namespace svgir
 
 namespace {

@@ -17,6 +17,7 @@
 //   pbr = srgb(x o + (1 - o) bg)      normal = x      direct, indirect = srgb(x)
 //   base_color, diffuse, lights, local_lights = srgb(x) o + (1 - o) bg      roughness, visibility = x o + (1 - o) bg
 #include "common.hpp"
+#include "d2n.hpp"
 
 namespace svgir {
 
@@ -126,36 +127,19 @@ __global__ void __launch_bounds__(BLOCK) unpack_kernel(const UnpackArgs a) {
 // depth2normal (utils/image_utils.py:61-125): back-project the pixel and its four neighbours (replicate padding) with
 // the reference's intrinsics -- K = diag(focal(FoVy, H), focal(FoVx, W)), i.e. x is divided by the y focal length and
 // vice versa, as in the reference --, mask, sum of the four cross products of neighbouring differences, normalise, mask.
+// The per-pixel arithmetic is d2n_normal / d2n_adjoint of d2n.hpp, which the fused geometry losses (geom_loss.hip) share.
 __global__ void __launch_bounds__(BLOCK) depth2normal_kernel(const float* __restrict__ depth, const float* __restrict__ mask,
                                                              int W, int H, float k00, float k11, float ppx, float ppy,
                                                              float* __restrict__ normal) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= W * H) return;
     const int x = i % W, y = i / W;
-    auto cam = [&](int xx, int yy, float* p, float& m) {
-        xx = min(max(xx, 0), W - 1); yy = min(max(yy, 0), H - 1);
-        const float d = depth[yy * W + xx];
-        m = mask[yy * W + xx] != 0.f ? 1.f : 0.f;
-        p[0] = ((float)xx - ppx) * d / k00; p[1] = ((float)yy - ppy) * d / k11; p[2] = d;
-    };
-    float pc[3], pu[3], pl[3], pb[3], pr[3], mc, mu, ml, mb, mr;
-    cam(x, y, pc, mc); cam(x, y - 1, pu, mu); cam(x - 1, y, pl, ml); cam(x, y + 1, pb, mb); cam(x + 1, y, pr, mr);
-    float c[3], u[3], l[3], b[3], r[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        c[j] = pc[j] * mc;
-        u[j] = (pu[j] - c[j]) * mu; l[j] = (pl[j] - c[j]) * ml; b[j] = (pb[j] - c[j]) * mb; r[j] = (pr[j] - c[j]) * mr;
-    }
-    auto cross = [](const float* a, const float* b_, float* o) {
-        o[0] = a[1] * b_[2] - a[2] * b_[1]; o[1] = a[2] * b_[0] - a[0] * b_[2]; o[2] = a[0] * b_[1] - a[1] * b_[0];
-    };
-    float n1[3], n2[3], n3[3], n4[3];
-    cross(u, l, n1); cross(r, u, n2); cross(b, r, n3); cross(l, b, n4);
-    float n[3] = {n1[0] + n2[0] + n3[0] + n4[0], n1[1] + n2[1] + n3[1] + n4[1], n1[2] + n2[2] + n3[2] + n4[2]};
-    const float len = fmaxf(sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]), 1e-12f);
+    const D2nCam k{W, H, k00, k11, ppx, ppy};
+    float n[3];
+    d2n_normal(k, x, y, [&](int xx, int yy, float& d, float& m) { d = depth[yy * W + xx]; m = mask[yy * W + xx]; }, n);
     const size_t N = (size_t)W * H;
 #pragma unroll
-    for (int j = 0; j < 3; j++) normal[(size_t)j * N + i] = n[j] / len * mc;
+    for (int j = 0; j < 3; j++) normal[(size_t)j * N + i] = n[j];
 }
 
 // adjoint of depth2normal: every pixel recomputes its five camera points and scatters d(loss)/d(depth) of its own normal to
@@ -167,77 +151,17 @@ __global__ void __launch_bounds__(BLOCK) depth2normal_bwd_kernel(const float* __
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= W * H) return;
     const int x = i % W, y = i / W;
-    float ray[5][3], m[5];
-    int at[5];
-    float p[5][3];
+    const D2nCam k{W, H, k00, k11, ppx, ppy};
+    const size_t N = (size_t)W * H;
+    const float g[3] = {g_normal[i], g_normal[N + i], g_normal[2 * N + i]};
+    float gd[5];
+    d2n_adjoint(k, x, y, [&](int xx, int yy, float& d, float& m) { d = depth[yy * W + xx]; m = mask[yy * W + xx]; }, g, gd);
     const int ox[5] = {0, 0, -1, 0, 1}, oy[5] = {0, -1, 0, 1, 0};   // centre, up, left, bottom, right
 #pragma unroll
     for (int q = 0; q < 5; q++) {
         const int xx = min(max(x + ox[q], 0), W - 1), yy = min(max(y + oy[q], 0), H - 1);
-        at[q] = yy * W + xx;
-        const float d = depth[at[q]];
-        m[q] = mask[at[q]] != 0.f ? 1.f : 0.f;
-        ray[q][0] = ((float)xx - ppx) / k00; ray[q][1] = ((float)yy - ppy) / k11; ray[q][2] = 1.f;
-        p[q][0] = ((float)xx - ppx) * d / k00; p[q][1] = ((float)yy - ppy) * d / k11; p[q][2] = d;
+        if (gd[q] != 0.f) atomic_add_f32(&dL_ddepth[yy * W + xx], gd[q]);
     }
-    float c[3], e[5][3];   // e[1..4] = u, l, b, r
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        c[j] = p[0][j] * m[0];
-#pragma unroll
-        for (int q = 1; q < 5; q++) e[q][j] = (p[q][j] - c[j]) * m[q];
-    }
-    auto cross = [](const float* a, const float* b_, float* o) {
-        o[0] = a[1] * b_[2] - a[2] * b_[1]; o[1] = a[2] * b_[0] - a[0] * b_[2]; o[2] = a[0] * b_[1] - a[1] * b_[0];
-    };
-    const float *u = e[1], *l = e[2], *b = e[3], *r = e[4];
-    float n1[3], n2[3], n3[3], n4[3], n[3];
-    cross(u, l, n1); cross(r, u, n2); cross(b, r, n3); cross(l, b, n4);
-#pragma unroll
-    for (int j = 0; j < 3; j++) n[j] = n1[j] + n2[j] + n3[j] + n4[j];
-    const size_t N = (size_t)W * H;
-    // normal = n / max(|n|, 1e-12) * mask_c
-    float g[3] = {g_normal[i] * m[0], g_normal[N + i] * m[0], g_normal[2 * N + i] * m[0]};
-    const float len = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-    float gn[3];
-    if (len > 1e-12f) {
-        const float dot = (n[0] * g[0] + n[1] * g[1] + n[2] * g[2]) / (len * len);
-#pragma unroll
-        for (int j = 0; j < 3; j++) gn[j] = (g[j] - n[j] * dot) / len;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 3; j++) gn[j] = g[j] / 1e-12f;
-    }
-    // n = u x l + r x u + b x r + l x b;  for a x b: d/da = b x g, d/db = g x a
-    float t1[3], t2[3], ge[5][3];
-    cross(l, gn, t1); cross(gn, r, t2);
-#pragma unroll
-    for (int j = 0; j < 3; j++) ge[1][j] = t1[j] + t2[j];   // u
-    cross(gn, u, t1); cross(b, gn, t2);
-#pragma unroll
-    for (int j = 0; j < 3; j++) ge[2][j] = t1[j] + t2[j];   // l
-    cross(r, gn, t1); cross(gn, l, t2);
-#pragma unroll
-    for (int j = 0; j < 3; j++) ge[3][j] = t1[j] + t2[j];   // b
-    cross(u, gn, t1); cross(gn, b, t2);
-#pragma unroll
-    for (int j = 0; j < 3; j++) ge[4][j] = t1[j] + t2[j];   // r
-    float gc[3] = {0.f, 0.f, 0.f};
-    float gd[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 1; q < 5; q++) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const float gp = ge[q][j] * m[q];       // e = (p_q - c) m_q
-            gd[q] += gp * ray[q][j];
-            gc[j] -= gp;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) gd[0] += gc[j] * m[0] * ray[0][j];   // c = p_c m_c
-#pragma unroll
-    for (int q = 0; q < 5; q++)
-        if (gd[q] != 0.f) atomic_add_f32(&dL_ddepth[at[q]], gd[q]);
 }
 
 // ---- stage 1 (rgss) feature packing and image-space tail (gaussian_renderer/render.py:83-91, 107-114) ----------

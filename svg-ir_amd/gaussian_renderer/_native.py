@@ -142,7 +142,8 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_split_transform", "svgir_bvh_bytes", "svgir_bvh_build",
            "svgir_bvh_trace_visibility", "svgir_pbgi_bvh_bytes", "svgir_pbgi_bvh_build", "svgir_pbgi_bvh_export",
            "svgir_pbgi_trace_radiance", "svgir_knn_bytes", "svgir_knn_mean_dist", "svgir_knn_topk", "svgir_pbgi_irradiance_sample",
-           "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance")
+           "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance", "svgir_geometry_loss_partials",
+           "svgir_geometry_loss_forward", "svgir_geometry_loss_backward")
 
 
 _scope = threading.local()

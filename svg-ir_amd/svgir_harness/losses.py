@@ -1,7 +1,8 @@
 """L1 and SSIM of a rendered image against the ground truth, fused (csrc/loss.hip): the reference's
 `F.l1_loss(image, gt)` + `ssim(image, gt)` (gaussian_renderer/svgss.py:281-289, render.py:150-151;
 utils/loss_utils.py:21-64), one kernel forward, one backward; and the radiance-consistency loss of stage 2 (`radiance_loss`: scene/gaussian_model.py:544-575)
-around the irradiance kernel of csrc/irradiance.hip."""
+around the irradiance kernel of csrc/irradiance.hip; and the geometry terms of both stages (`cos_loss`, `surface_loss`, `mask_loss`,
+`mask_entropy_loss`, `geometry_losses`: gaussian_renderer/render.py:157-188, svgss.py:297-313, 333-338), fused in csrc/geom_loss.hip."""
 import ctypes as C
 
 import torch
@@ -15,6 +16,13 @@ N.lib.svgir_l1_ssim_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_i
 N.lib.svgir_l1_ssim_backward.restype = C.c_int
 N.lib.svgir_l1_ssim_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
+
+N.lib.svgir_geometry_loss_partials.restype = C.c_size_t
+N.lib.svgir_geometry_loss_partials.argtypes = [C.c_int32] * 2
+N.lib.svgir_geometry_loss_forward.restype = C.c_int
+N.lib.svgir_geometry_loss_forward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_float] * 4 + [C.c_void_p] * 4
+N.lib.svgir_geometry_loss_backward.restype = C.c_int
+N.lib.svgir_geometry_loss_backward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_float] * 4 + [C.c_void_p] * 6
 
 
 def _need_maps(dmaps):
@@ -141,3 +149,135 @@ def radiance_loss(renderer, xyz, camera_center, geo_normal, incident_dirs, visib
     target = torch.nan_to_num(radiances.detach() * radiance_ratio, nan=0.0)
     target = target.gather(1, max_idx.long().unsqueeze(-1).expand(-1, -1, 3)).squeeze(-2)
     return torch.nn.functional.l1_loss(radiance, target)
+
+
+# ---- geometry terms (csrc/geom_loss.hip) ------------------------------------------------------------------------------------------
+GEOMETRY_TERMS = ("surface", "target", "mask", "entropy")   # bit k of the kernels' `terms`; the order of their stats / losses buffers
+
+
+def _plane(t, channels, H, W, name):
+    """[channels,H,W] view of a plane given as [channels,H,W] (or [H,W] for one channel)."""
+    if t is None:
+        return None
+    if channels == 1 and t.dim() == 2:
+        t = t[None]
+    if tuple(t.shape) != (channels, H, W):
+        raise ValueError(f"geometry_losses: {name} must be [{channels},{H},{W}], got {tuple(t.shape)}")
+    return t
+
+
+class _GeometryLoss(torch.autograd.Function):
+    """The requested terms as ONE node: one forward launch (+ its reduction), one backward launch.  Returns the [4] vector of losses in
+    GEOMETRY_TERMS order (zeros for the terms not requested) and the kernels' stats [4][2] = {sum, count} per term (doubles); the gradient of the
+    loss vector is the kernels' upstream buffer as it is."""
+
+    @staticmethod
+    def forward(ctx, terms, cam, normal, depth, opacity, mask, target, weight):
+        ref = normal if normal is not None else opacity
+        dev = ref.device
+        for t in (normal, depth, opacity, mask, target, weight):
+            if t is not None and t.device.type != "cuda":
+                raise RuntimeError("geometry_losses: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
+        H, W = int(ref.shape[-2]), int(ref.shape[-1])
+        shapes = tuple(None if t is None else tuple(t.shape) for t in (normal, depth, opacity))
+        planes = [N.f32c(_plane(None if t is None else t.detach(), c, H, W, n), dev)
+                  for t, c, n in ((normal, 3, "normal"), (depth, 1, "depth"), (mask, 1, "mask"), (opacity, 1, "opacity"), (target, 3, "target"),
+                                  (weight, 1, "weight"))]
+        with torch.cuda.device(dev):
+            partial = torch.empty((max(N.lib.svgir_geometry_loss_partials(W, H), 1), 8), dtype=torch.float64, device=dev)
+            stats = N.out_tensor((4, 2), torch.float64, dev)
+            losses = N.out_tensor((4,), torch.float32, dev)
+            N.check(N.lib.svgir_geometry_loss_forward(W, H, terms, *[N.ptr(p) for p in planes], *cam, partial.data_ptr(), stats.data_ptr(),
+                                                      losses.data_ptr(), N.stream_ptr(dev)), "geometry_loss forward")
+        ctx.save_for_backward(stats, *planes)
+        ctx.terms, ctx.cam, ctx.shapes, ctx.size = terms, cam, shapes, (H, W)
+        ctx.mark_non_differentiable(stats)
+        return losses, stats
+
+    @staticmethod
+    def backward(ctx, g, _g_stats):
+        stats, *planes = ctx.saved_tensors
+        H, W = ctx.size
+        dev = stats.device
+        need = ctx.needs_input_grad[2:5]   # normal, depth, opacity
+        outs = [N.out_tensor((c, H, W), torch.float32, dev) if n else None for n, c in zip(need, (3, 1, 1))]
+        if any(need):
+            gdev = g.to(torch.float32).contiguous()   # the four upstream scalars stay on the device
+            with torch.cuda.device(dev):
+                N.check(N.lib.svgir_geometry_loss_backward(W, H, ctx.terms, *[N.ptr(p) for p in planes], *ctx.cam, stats.data_ptr(),
+                                                           gdev.data_ptr(), *[N.ptr(o) for o in outs], N.stream_ptr(dev)),
+                        "geometry_loss backward")
+        grads = [None if o is None else o.reshape(sh) for o, sh in zip(outs, ctx.shapes)]
+        return (None, None, grads[0], grads[1], grads[2], None, None, None)
+
+
+def geometry_losses(normal=None, depth=None, mask=None, opacity=None, target=None, weight=None, fovx=None, fovy=None, prcppoint=(0.5, 0.5),
+                    terms=None, with_stats=False):
+    """The geometry terms of `calculate_loss` (gaussian_renderer/render.py:157-188, svgss.py:297-313, 333-338) from ONE forward launch and
+    one autograd node: a dict with
+      "surface": cos_loss(normal, depth2normal(depth, mask, camera))   -- normal [3,H,W], depth, mask [1,H,W], fovx, fovy, prcppoint
+      "target" : cos_loss(normal, target, weight=weight)                -- target [3,H,W], weight [1,H,W] / [H,W] or None (= 1)
+      "mask"   : (opacity * (1 - MaxPool2d(9, 1, 4)(mask))).mean()      -- opacity, mask [1,H,W]
+      "entropy": -(mask * log(o) + (1 - mask) * log(1 - o)).mean(), o = opacity.clamp(1e-6, 1 - 1e-6)
+    `terms`: the names wanted; None = every term whose inputs are given.  with_stats=True adds "stats": the device tensor [4,2] (float64) of {sum,
+    count} per term in GEOMETRY_TERMS order (the count of a cos_loss is its number of selected pixels; a loss is float32(sum / count)).  Differentiable in normal, depth and opacity; the mask, the target
+    and the weight get no gradient (a target that requires grad is refused)."""
+    have = {"surface": normal is not None and depth is not None and mask is not None and fovx is not None and fovy is not None,
+            "target": normal is not None and target is not None,
+            "mask": opacity is not None and mask is not None, "entropy": opacity is not None and mask is not None}
+    names = tuple(k for k in GEOMETRY_TERMS if have[k]) if terms is None else tuple(terms)
+    if not names:
+        raise ValueError("geometry_losses: no term requested (give the planes of at least one term)")
+    for k in names:
+        if k not in GEOMETRY_TERMS:
+            raise ValueError(f"geometry_losses: unknown term {k!r}")
+        if not have[k]:
+            raise ValueError(f"geometry_losses: the {k} term was requested without its planes")
+    for t, n in ((target, "target"), (weight, "weight"), (mask, "mask")):
+        if t is not None and t.requires_grad:
+            raise RuntimeError(f"geometry_losses: the {n} gets no gradient (detach it); the fused surface term differentiates through the "
+                               "pseudo normal")
+    bits = sum(1 << GEOMETRY_TERMS.index(k) for k in set(names))
+    surface = "surface" in names
+    cam = (float(fovx), float(fovy), float(prcppoint[0]), float(prcppoint[1])) if surface else (1.0, 1.0, 0.5, 0.5)
+    cos = surface or "target" in names
+    opac = "mask" in names or "entropy" in names
+    out, stats = _GeometryLoss.apply(bits, cam, normal if cos else None, depth if surface else None, opacity if opac else None,
+                              mask if surface or opac else None, target if "target" in names else None,
+                              weight if "target" in names else None)
+    res = {k: out[GEOMETRY_TERMS.index(k)] for k in GEOMETRY_TERMS if k in names}
+    if with_stats:
+        res["stats"] = stats
+    return res
+
+
+def cos_loss(output, gt, thrsh=0, weight=1):
+    """Drop-in for utils/loss_utils.py:119: cos = sum_c output_c * gt_c * weight, mean of 1 - cos over the pixels with cos < 1.
+    `thrsh` must be 0 (the only form the reference calls); `weight` is 1 or a [1,H,W] / [H,W] plane.  Differentiable in `output` only:
+    for the pseudo normal of the rendered depth use `surface_loss`, which differentiates through it."""
+    if thrsh != 0:
+        raise NotImplementedError("cos_loss: only thrsh = 0 is implemented (the reference's call form)")
+    if not torch.is_tensor(weight):
+        if weight != 1:
+            raise NotImplementedError("cos_loss: weight is 1 or a [1,H,W] / [H,W] plane")
+        weight = None
+    if gt.requires_grad:
+        raise RuntimeError("cos_loss: only `output` is differentiable; for gt = depth2normal(depth, ...) use surface_loss")
+    return geometry_losses(normal=output, target=gt, weight=weight, terms=("target",))["target"]
+
+
+def surface_loss(normal, depth, mask, fovx, fovy, prcppoint=(0.5, 0.5)):
+    """cos_loss(normal, depth2normal(depth, mask, camera)) fused (render.py:158-160, svgss.py:299-301): the pseudo normal is never
+    stored.  Differentiable in `normal` and `depth`."""
+    return geometry_losses(normal=normal, depth=depth, mask=mask, fovx=fovx, fovy=fovy, prcppoint=prcppoint, terms=("surface",))["surface"]
+
+
+def mask_loss(opacity, mask):
+    """(opacity * (1 - MaxPool2d(9, stride=1, padding=4)(mask))).mean() (render.py:157-159).  Differentiable in `opacity`."""
+    return geometry_losses(opacity=opacity, mask=mask, terms=("mask",))["mask"]
+
+
+def mask_entropy_loss(opacity, mask):
+    """-(mask * log(o) + (1 - mask) * log(1 - o)).mean() with o = opacity.clamp(1e-6, 1 - 1e-6) (render.py:184-186, svgss.py:333-336).
+    Differentiable in `opacity`."""
+    return geometry_losses(opacity=opacity, mask=mask, terms=("entropy",))["entropy"]
