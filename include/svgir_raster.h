@@ -469,6 +469,42 @@ int svgir_geometry_loss_backward(int32_t W, int32_t H, int32_t terms, const floa
                                  float prcp_y, const double* stats, const float* g_dev, float* dL_dnormal, float* dL_ddepth,
                                  float* dL_dopacity, void* stream);
 
+/* The edge-aware smoothness terms and the TV term of both training stages (utils/loss_utils.py:101-117 `second_order_edge_aware_loss`,
+ * `first_order_edge_aware_loss`, `tv_loss`; gaussian_renderer/svgss.py:366-399, render.py:192-196), fused: up to SVGIR_SMOOTH_MAX_TERMS
+ * terms of one image size in one forward launch plus a small fixed-order reduction, and one backward launch.  `terms` is a HOST array
+ * of descriptors, read during the call; every plane is fp32 [.,H,W], contiguous, on the device.
+ *   kind 1 first : sum_{cb,k,p} |d_k D[c,p]| exp(-|d_k I[ci,p]|) / (Cb H W)
+ *   kind 2 second: sum_{cb,k,p} |d_kk D[c,p]| exp(-10 |d_k I[ci,p]|) / (Cb H W)   (the FIRST derivative of I weights the second of D)
+ *   kind 3 tv    : mean((x[:,1:,:] - x[:,:-1,:])^2) + mean((x[:,:,1:] - x[:,:,:-1])^2), x = data; Ci = 0, no img, no masks
+ * D = data * data_mask and I = img * img_mask, one fp32 product each (a NULL mask is 1; masks are [1,H,W]); C == Ci or one of them is 1,
+ * Cb = max(C, Ci), c / ci = cb or 0 (torch broadcasting); k in {x, y}.  The derivatives are kornia's spatial_gradient(mode='sobel',
+ * normalized=True): the cross-correlation of the REPLICATE-padded plane with Kx = (1 2 1)^T (-1 0 1) / 8, Ky = Kx^T (order 1) and
+ * Kxx = (1 4 6 4 1)^T (-1 0 2 0 -1) / 64, Kyy = Kxx^T (order 2).  Every tap takes part, the zero ones included (0 * inf = NaN, as in
+ * F.conv2d).  The VALUE of an element (cb, k, p) is evaluated in double from the fp32 planes; signs and gradients are fp32, sign(0) = 0.
+ * An element whose value is NaN puts NaN into the loss and contributes to no gradient.
+ *   partials: the number of 2-double records `partial` must hold: n_terms per 32 x 8 pixel tile.
+ *   forward : `stats` [n_terms][4] = {sum_a, count_a, sum_b, count_b}, device doubles: first / second {sum, Cb H W, 0, 0}; tv {row sum,
+ *             C (H-1) W, column sum, C H (W-1)}.  `losses` [n_terms] = float32(sum_a / count_a), tv float32(sum_a / count_a + sum_b /
+ *             count_b), device floats; an empty tv mean (H or W = 1) is NaN as in torch.  No atomics: two runs give the same bits.
+ *   backward: `stats` as the forward wrote it; `g` [n_terms] = the upstream gradients of the losses, device floats the host never reads.
+ *             Each d_data [C,H,W] / d_img [Ci,H,W] that is not NULL is written completely, times its mask (a gather: the adjoint of the
+ *             replicate padding folds every out-of-image tap back onto the border pixel it was clamped to; no atomics).  Masks get no
+ *             gradient; an empty tv mean gives zero gradient.
+ * n_terms outside 1 ... SVGIR_SMOOTH_MAX_TERMS, an unknown kind, C / Ci outside 1 ... 4 or not broadcastable, a missing plane, or a
+ * backward that requests no gradient: -1 and a message, before any HIP call.  W * H == 0 launches nothing. */
+#define SVGIR_SMOOTH_MAX_TERMS 4
+typedef struct svgir_smooth_term {
+    int32_t kind;                    /* 1 first, 2 second, 3 tv */
+    int32_t C, Ci;                   /* 1..4; tv: Ci = 0 */
+    const float *data, *img, *data_mask, *img_mask;
+    float *d_data, *d_img;           /* backward only; NULL = not wanted */
+} svgir_smooth_term;
+size_t svgir_smooth_loss_partials(int32_t W, int32_t H, int32_t n_terms);
+int svgir_smooth_loss_forward(int32_t W, int32_t H, int32_t n_terms, const svgir_smooth_term* terms, double* partial, double* stats,
+                              float* losses, void* stream);
+int svgir_smooth_loss_backward(int32_t W, int32_t H, int32_t n_terms, const svgir_smooth_term* terms, const double* stats, const float* g,
+                               void* stream);
+
 /* The consumers of the rasterizer's gradients: Adam over the per-Gaussian parameter block, the
  * densification statistics, and the row compaction behind pruning (scene/gaussian_model.py:737-773, 1020-1062, 1270-1276).
  *

@@ -76,6 +76,12 @@ class FusedShade(C.Structure):
     _fields_ = [("sp", ShadeParams), ("reduced", C.c_void_p), ("all_surfels", C.c_int32)]
 
 
+class SmoothTerm(C.Structure):
+    """svgir_smooth_term: one term of svgir_smooth_loss_forward / svgir_smooth_loss_backward."""
+    _fields_ = [("kind", C.c_int32), ("C", C.c_int32), ("Ci", C.c_int32), ("data", C.c_void_p), ("img", C.c_void_p),
+                ("data_mask", C.c_void_p), ("img_mask", C.c_void_p), ("d_data", C.c_void_p), ("d_img", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -124,6 +130,13 @@ def _load():
     lib.svgir_pbgi_irradiance_sample_backward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 13
     lib.svgir_pbgi_irradiance.restype = C.c_int
     lib.svgir_pbgi_irradiance.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 9
+    # the edge-aware smoothness and TV terms (svgir_harness/losses.py): W, H, n_terms, host descriptors, device pointers, stream
+    lib.svgir_smooth_loss_partials.restype = C.c_size_t
+    lib.svgir_smooth_loss_partials.argtypes = [C.c_int32] * 3
+    lib.svgir_smooth_loss_forward.restype = C.c_int
+    lib.svgir_smooth_loss_forward.argtypes = [C.c_int32] * 3 + [C.POINTER(SmoothTerm)] + [C.c_void_p] * 4
+    lib.svgir_smooth_loss_backward.restype = C.c_int
+    lib.svgir_smooth_loss_backward.argtypes = [C.c_int32] * 3 + [C.POINTER(SmoothTerm)] + [C.c_void_p] * 3
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -143,7 +156,8 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_bvh_trace_visibility", "svgir_pbgi_bvh_bytes", "svgir_pbgi_bvh_build", "svgir_pbgi_bvh_export",
            "svgir_pbgi_trace_radiance", "svgir_knn_bytes", "svgir_knn_mean_dist", "svgir_knn_topk", "svgir_pbgi_irradiance_sample",
            "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance", "svgir_geometry_loss_partials",
-           "svgir_geometry_loss_forward", "svgir_geometry_loss_backward")
+           "svgir_geometry_loss_forward", "svgir_geometry_loss_backward", "svgir_smooth_loss_partials", "svgir_smooth_loss_forward",
+           "svgir_smooth_loss_backward")
 
 
 _scope = threading.local()

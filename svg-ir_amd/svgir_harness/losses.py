@@ -2,7 +2,9 @@
 `F.l1_loss(image, gt)` + `ssim(image, gt)` (gaussian_renderer/svgss.py:281-289, render.py:150-151;
 utils/loss_utils.py:21-64), one kernel forward, one backward; and the radiance-consistency loss of stage 2 (`radiance_loss`: scene/gaussian_model.py:544-575)
 around the irradiance kernel of csrc/irradiance.hip; and the geometry terms of both stages (`cos_loss`, `surface_loss`, `mask_loss`,
-`mask_entropy_loss`, `geometry_losses`: gaussian_renderer/render.py:157-188, svgss.py:297-313, 333-338), fused in csrc/geom_loss.hip."""
+`mask_entropy_loss`, `geometry_losses`: gaussian_renderer/render.py:157-188, svgss.py:297-313, 333-338), fused in csrc/geom_loss.hip; and the
+edge-aware smoothness and TV terms (`first_order_edge_aware_loss`, `second_order_edge_aware_loss`, `tv_loss`, `smoothness_losses`:
+utils/loss_utils.py:101-117; svgss.py:366-399, render.py:192-196), fused in csrc/smooth_loss.hip."""
 import ctypes as C
 
 import torch
@@ -281,3 +283,142 @@ def mask_entropy_loss(opacity, mask):
     """-(mask * log(o) + (1 - mask) * log(1 - o)).mean() with o = opacity.clamp(1e-6, 1 - 1e-6) (render.py:184-186, svgss.py:333-336).
     Differentiable in `opacity`."""
     return geometry_losses(opacity=opacity, mask=mask, terms=("entropy",))["entropy"]
+
+
+# ---- edge-aware smoothness and TV terms (csrc/smooth_loss.hip) ------------------------------------------------------------------------
+SMOOTH_KINDS = {"first": 1, "second": 2, "tv": 3}   # svgir_smooth_term.kind
+SMOOTH_MAX_TERMS = 4                                 # SVGIR_SMOOTH_MAX_TERMS
+
+
+def _descriptors(kinds, planes, grads=None):
+    """(svgir_smooth_term * n) over the planes [(data, img, data_mask, img_mask)]; grads [(d_data, d_img)] for the backward."""
+    arr = (N.SmoothTerm * len(kinds))()
+    for k, (kind, (data, img, dm, im)) in enumerate(zip(kinds, planes)):
+        t = arr[k]
+        t.kind, t.C, t.Ci = kind, int(data.shape[0]), 0 if img is None else int(img.shape[0])
+        t.data, t.img, t.data_mask, t.img_mask = (None if p is None else p.data_ptr() for p in (data, img, dm, im))
+        if grads is not None:
+            t.d_data, t.d_img = (None if g is None else g.data_ptr() for g in grads[k])
+    return arr
+
+
+class _SmoothLoss(torch.autograd.Function):
+    """Up to SMOOTH_MAX_TERMS terms of one image size as ONE node: one forward launch (+ its reduction), one backward launch.  `tensors` =
+    (data, img, data_mask, img_mask) per term, None where a term has none.  Returns the [n] vector of losses and the kernels' stats [n,4] =
+    {sum_a, count_a, sum_b, count_b} per term (doubles); the gradient of the loss vector is the kernels' upstream buffer as it is."""
+
+    @staticmethod
+    def forward(ctx, kinds, *tensors):
+        n = len(kinds)
+        dev = tensors[0].device
+        for t in tensors:
+            if t is not None and t.device.type != "cuda":
+                raise RuntimeError("smoothness_losses: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
+        H, W = int(tensors[0].shape[-2]), int(tensors[0].shape[-1])
+        flat = [None if t is None else N.f32c(t.detach(), dev) for t in tensors]
+        planes = [tuple(flat[4 * k:4 * k + 4]) for k in range(n)]
+        with torch.cuda.device(dev):
+            partial = torch.empty((max(N.lib.svgir_smooth_loss_partials(W, H, n), 1), 2), dtype=torch.float64, device=dev)
+            stats = N.out_tensor((n, 4), torch.float64, dev)
+            losses = N.out_tensor((n,), torch.float32, dev)
+            N.check(N.lib.svgir_smooth_loss_forward(W, H, n, _descriptors(kinds, planes), partial.data_ptr(), stats.data_ptr(), losses.data_ptr(),
+                                                    N.stream_ptr(dev)), "smooth_loss forward")
+        ctx.save_for_backward(stats, *[p for p in flat if p is not None])
+        ctx.kinds, ctx.present, ctx.size = kinds, tuple(p is not None for p in flat), (H, W)
+        ctx.mark_non_differentiable(stats)
+        return losses, stats
+
+    @staticmethod
+    def backward(ctx, g, _g_stats):
+        stats, *saved = ctx.saved_tensors
+        it = iter(saved)
+        flat = [next(it) if here else None for here in ctx.present]
+        n = len(ctx.kinds)
+        planes = [tuple(flat[4 * k:4 * k + 4]) for k in range(n)]
+        dev = stats.device
+        need = ctx.needs_input_grad[1:]
+        grads = [tuple(N.out_tensor(tuple(planes[k][j].shape), torch.float32, dev) if need[4 * k + j] else None for j in (0, 1)) for k in range(n)]
+        if any(o is not None for pair in grads for o in pair):
+            gdev = g.to(torch.float32).contiguous()   # the upstream scalars stay on the device
+            with torch.cuda.device(dev):
+                N.check(N.lib.svgir_smooth_loss_backward(ctx.size[1], ctx.size[0], n, _descriptors(ctx.kinds, planes, grads), stats.data_ptr(),
+                                                         gdev.data_ptr(), N.stream_ptr(dev)), "smooth_loss backward")
+        out = [None]
+        for pair in grads:
+            out += [pair[0], pair[1], None, None]
+        return tuple(out)
+
+
+def _smooth_plane(t, name, k, H=None, W=None, one=False):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dim() != 3 or not 1 <= t.shape[0] <= 4 or (one and t.shape[0] != 1):
+        raise ValueError(f"smoothness_losses: term {k}: {name} must be a " + ("[1,H,W]" if one else "[C,H,W] (C = 1 ... 4)") + " tensor, got "
+                         + (str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+    if H is not None and (int(t.shape[1]), int(t.shape[2])) != (H, W):
+        raise ValueError(f"smoothness_losses: term {k}: {name} is {tuple(t.shape)}; every plane of a launch must be [.,{H},{W}]")
+    return t
+
+
+def smoothness_losses(terms, with_stats=False):
+    """The smoothness terms of `calculate_loss` (gaussian_renderer/svgss.py:366-399, render.py:192-196) from ONE forward launch and one
+    autograd node.  `terms`: a list of up to 4 dicts {kind, data, img=None, data_mask=None, img_mask=None} over one image size,
+      kind "first" : first_order_edge_aware_loss(data * data_mask, img * img_mask)     -- data [C,H,W], img [Ci,H,W], C == Ci or one is 1
+      kind "second": second_order_edge_aware_loss(data * data_mask, img * img_mask)
+      kind "tv"    : tv_loss(data)                                                     -- data [C,H,W]; no img, no masks
+    (utils/loss_utils.py:101-117; a kind may also be given as 1, 2, 3).  The masks are [1,H,W] planes or None (= 1): the kernels form the
+    fp32 product the reference forms, and multiply the outgoing gradient by the mask.  Returns the [n] vector of losses in the order of
+    `terms`; with_stats=True returns (losses, stats), stats the device tensor [n,4] (float64) of {sum_a, count_a, sum_b, count_b} per term
+    (a loss is float32(sum_a / count_a), tv float32(sum_a / count_a + sum_b / count_b)).  Differentiable in every `data` and in every `img`
+    that requires grad; masks get no gradient (one that requires grad is refused)."""
+    terms = list(terms)
+    if not 1 <= len(terms) <= SMOOTH_MAX_TERMS:
+        raise ValueError(f"smoothness_losses: 1 ... {SMOOTH_MAX_TERMS} terms per launch, got {len(terms)}")
+    kinds, flat = [], []
+    H = W = None
+    for k, t in enumerate(terms):
+        unknown = set(t) - {"kind", "data", "img", "data_mask", "img_mask"}
+        if unknown:
+            raise ValueError(f"smoothness_losses: term {k}: unknown keys {sorted(unknown)}")
+        kind = SMOOTH_KINDS.get(t.get("kind"), t.get("kind"))
+        if kind not in (1, 2, 3):
+            raise ValueError(f"smoothness_losses: term {k}: unknown kind {t.get('kind')!r} (first, second, tv)")
+        data = _smooth_plane(t.get("data"), "data", k, H, W)
+        if data is None:
+            raise ValueError(f"smoothness_losses: term {k} has no data")
+        H, W = int(data.shape[1]), int(data.shape[2])
+        img, dm, im = (_smooth_plane(t.get(nm), nm, k, H, W, one) for nm, one in (("img", False), ("data_mask", True), ("img_mask", True)))
+        if kind == 3:
+            if img is not None or dm is not None or im is not None:
+                raise ValueError(f"smoothness_losses: term {k}: a tv term takes data only")
+        else:
+            if img is None:
+                raise ValueError(f"smoothness_losses: term {k} has no img")
+            if data.shape[0] != img.shape[0] and data.shape[0] != 1 and img.shape[0] != 1:
+                raise ValueError(f"smoothness_losses: term {k}: cannot broadcast data {tuple(data.shape)} against img {tuple(img.shape)}")
+        for m, nm in ((dm, "data_mask"), (im, "img_mask")):
+            if m is not None and m.requires_grad:
+                raise RuntimeError(f"smoothness_losses: term {k}: the {nm} gets no gradient (detach it)")
+        kinds.append(kind)
+        flat += [data, img, dm, im]
+    losses, stats = _SmoothLoss.apply(tuple(kinds), *flat)
+    return (losses, stats) if with_stats else losses
+
+
+def first_order_edge_aware_loss(data, img):
+    """Drop-in for utils/loss_utils.py:104: (|d data| * exp(-|d img|)).sum(1).mean() over kornia's normalized Sobel derivatives, data
+    [C,H,W], img [Ci,H,W].  Differentiable in `data`, and in `img` when it requires grad.  A caller that multiplies by a mask first can
+    hand the mask to `smoothness_losses` instead and save the product."""
+    return smoothness_losses([dict(kind="first", data=data, img=img)])[0]
+
+
+def second_order_edge_aware_loss(data, img):
+    """Drop-in for utils/loss_utils.py:101: (|d2 data| * exp(-10 |d img|)).sum(1).mean(), the xx / yy second derivatives of `data` weighted
+    by the x / y first derivatives of `img`."""
+    return smoothness_losses([dict(kind="second", data=data, img=img)])[0]
+
+
+def tv_loss(x):
+    """Drop-in for utils/loss_utils.py:113: mean of the squared row differences + mean of the squared column differences, x [C,H,W] or
+    [H,W].  H == 1 or W == 1: NaN (the empty mean, as in torch) and zero gradient."""
+    return smoothness_losses([dict(kind="tv", data=x[None] if x.dim() == 2 else x)])[0]
