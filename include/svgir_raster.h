@@ -423,6 +423,25 @@ int svgir_depth2normal(int32_t W, int32_t H, const float* depth, const float* ma
 int svgir_depth2normal_backward(int32_t W, int32_t H, const float* depth, const float* mask, const float* dL_dnormal, float fovx,
                                 float fovy, float prcp_x, float prcp_y, float* dL_ddepth, void* stream);
 
+/* The environment backdrop that ends every eval view (gaussian_renderer/svgss.py:255-260; forward only, the reference runs it
+ * under no_grad): per pixel (u, v) the camera direction ((u - cx) / fx, (v - cy) / fy, 1), normalised and rotated by c2w[:3,:3]
+ * (Camera.get_world_directions, scene/cameras.py:96-108), then by the light's lookup transform if one is given (EnvLight's
+ * `dirs @ transform.T`), is looked up in the lat-long map exactly as the shading kernels do it (grid_sample, align_corners=True, zero
+ * padding; env = env_scale * bilinear(f(env)), f = softplus when env_softplus != 0 -- DirectLightMap: softplus, scale 2; EnvLight's
+ * 32 x 64 resample: identity, scale 1).  d.z is clamped to [-1, 1] before the acos: where the reference's rounded unit vector has
+ * |z| = 1 + ulp and turns the pixel NaN, this looks up the pole.
+ *   intr         HOST  {fx, fy, cx, cy} in pixels (Camera.intrinsics); fx, fy finite and non-zero
+ *   c2w_rot      HOST  c2w[:3,:3], row-major 9 floats
+ *   env_transform HOST 9 floats row-major, or NULL
+ *   env          [env_h, env_w, 3] raw map; env_work: env_h * env_w * 4 floats of scratch, 16-byte aligned (the f(env) table)
+ *   image [3,H,W], opacity [1,H,W], vfeature [>= 3,H,W] (planes 0..2 = the rasterized pbr): the rasterizer's raw outputs
+ *   out [9,H,W], every element written: env_only = srgb(env) | render_env = image + (1 - o) srgb(env) |
+ *                pbr_env = srgb(pbr o + (1 - o) env), pbr = vfeature[0:3] / max(o, 1e-5)
+ * Invalid arguments are rejected with SVGIR_ERR_INVALID and a message before any HIP call. */
+int svgir_env_backdrop(int32_t W, int32_t H, const float* intr, const float* c2w_rot, const float* env_transform, const float* env,
+                       int32_t env_h, int32_t env_w, int32_t env_softplus, float env_scale, float* env_work, const float* image,
+                       const float* opacity, const float* vfeature, float* out, void* stream);
+
 /* Image losses behind render_view: L1 and SSIM with the reference's 11 x 11 Gaussian window
  * (`F.l1_loss(image, gt)` and `ssim(image, gt)`, gaussian_renderer/svgss.py:281-289, render.py:150-151;
  * utils/loss_utils.py:21-64), img1 / img2 = [C,H,W] planes.

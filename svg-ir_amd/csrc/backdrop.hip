@@ -1,0 +1,137 @@
+// svg-ir_amd/csrc/backdrop.hip -- the environment backdrop that ends every eval view.
+//
+// Replaces the PyTorch tail of `render_view`'s eval branch (gaussian_renderer/svgss.py:255-260): the camera's world-space pixel
+// directions (`Camera.get_world_directions`, scene/cameras.py:96-108: meshgrid, (u - cx) / fx, (v - cy) / fy, F.normalize, c2w[:3,:3] @ .),
+// the light's lookup along them (`DirectLightMap.direct_light`, scene/direct_light_map.py:70-83: 2 * bilinear(softplus(env));
+// `EnvLight.direct_light`, scene/envmap.py:54-73: bilinear of the 32 x 64 resample, directions through `.transform` first) and the three
+// images built from it.  The reference runs ~30 elementwise torch kernels over full-resolution planes; here one thread per pixel reads
+// image [3], opacity [1] and the pbr planes of vfeature [3] once and writes the nine result planes -- 28 B in, 36 B out per pixel:
+//   env_only   = srgb(env)                               planes 0..2
+//   render_env = image + (1 - o) * srgb(env)             planes 3..5
+//   pbr_env    = srgb(pbr * o + (1 - o) * env)           planes 6..8,   pbr = vfeature[0:3] / max(o, 1e-5)
+// Forward only: the reference runs this tail under no_grad.  All fp32, in the reference's operation order; the division and the square
+// root of the normalisation are the correctly rounded ones, as torch's.
+//
+// The lookup is the shading kernels' (env_lookup.hpp: env_taps on the f(env) float4 table that one tiny prologue launch builds), with
+// grid_sample's two corner rules spelled out: a tap outside the map contributes exactly 0 whatever the map holds, a tap inside it is
+// multiplied even when its weight is 0 (inf * 0 = NaN, as in grid_sample).
+//
+// ONE DELIBERATE DEPARTURE from the reference: d.z is clamped to [-1, 1] before the acos.  The rotation of a unit vector can round to
+// |z| = 1 + ulp, where the reference's arccos returns NaN and the pixel turns NaN; that NaN is not reproduced, the pixel looks up the
+// pole.  (A NaN direction -- from a NaN camera -- stays NaN.)
+#include <cmath>
+
+#include "common.hpp"
+#include "env_lookup.hpp"
+#include "srgb.hpp"
+
+namespace svgir {
+
+int report_error(int code, const char* fmt, ...);   // api.hip (it owns the per-thread message behind svgir_last_error)
+
+namespace {
+
+struct BackdropArgs {
+    int W, H;
+    float fx, fy, cx, cy;
+    float R[9];            // c2w[:3,:3], row-major
+    float T[9];            // the light's lookup transform (direction = T d), row-major; unused unless has_T
+    int has_T;
+    int env_h, env_w;
+    float env_scale;
+    const float4* env_tab;
+    const float *image, *opacity, *pbr;
+    float* out;
+};
+
+__global__ void __launch_bounds__(BLOCK) backdrop_table_kernel(const ShadeTables t) {
+    shade_table_entry(t, blockIdx.x * BLOCK + threadIdx.x);
+}
+
+__global__ void __launch_bounds__(BLOCK) backdrop_kernel(const BackdropArgs a) {
+    const size_t N = (size_t)a.W * a.H;
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= N) return;
+    const int u = (int)(i % (size_t)a.W), v = (int)(i / (size_t)a.W);
+    // scene/cameras.py:102-106
+    const float x = ((float)u - a.cx) / a.fx, y = ((float)v - a.cy) / a.fy;
+    const float nrm = fmaxf(sqrtf(x * x + y * y + 1.f), 1e-12f);
+    const float c[3] = {x / nrm, y / nrm, 1.f / nrm};
+    float d[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) d[j] = a.R[3 * j] * c[0] + a.R[3 * j + 1] * c[1] + a.R[3 * j + 2] * c[2];
+    if (a.has_T) {   // EnvLight: dirs @ transform.T
+        const float e[3] = {d[0], d[1], d[2]};
+#pragma unroll
+        for (int j = 0; j < 3; j++) d[j] = a.T[3 * j] * e[0] + a.T[3 * j + 1] * e[1] + a.T[3 * j + 2] * e[2];
+    }
+    d[2] = d[2] < -1.f ? -1.f : (d[2] > 1.f ? 1.f : d[2]);   // (the departure described in the header; NaN passes)
+    EnvTap t;
+    env_taps(d, a.env_h, a.env_w, t);
+    float E[3] = {0.f, 0.f, 0.f};
+    {
+        float4 tex[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) tex[j] = a.env_tab[t.idx[j] >= 0 ? t.idx[j] : 0];   // four gathers in flight
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const bool ok = t.idx[j] >= 0;
+            E[0] += ok ? t.w[j] * tex[j].x : 0.f;
+            E[1] += ok ? t.w[j] * tex[j].y : 0.f;
+            E[2] += ok ? t.w[j] * tex[j].z : 0.f;
+        }
+    }
+    const float o = a.opacity[i];
+    const float om = 1.f - o;
+    const float oc = clamp_min_nan(o, 1e-5f);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const float env = E[ch] * a.env_scale;
+        const float s = srgb(env);
+        const float pbr = a.pbr[(size_t)ch * N + i] / oc;
+        a.out[(size_t)ch * N + i] = s;
+        a.out[(size_t)(3 + ch) * N + i] = a.image[(size_t)ch * N + i] + om * s;
+        a.out[(size_t)(6 + ch) * N + i] = srgb(pbr * o + om * env);
+    }
+}
+
+}  // namespace
+
+}  // namespace svgir
+
+using namespace svgir;
+
+extern "C" int svgir_env_backdrop(int32_t W, int32_t H, const float* intr, const float* c2w_rot, const float* env_transform,
+                                  const float* env, int32_t env_h, int32_t env_w, int32_t env_softplus, float env_scale,
+                                  float* env_work, const float* image, const float* opacity, const float* vfeature, float* out,
+                                  void* stream) {
+    if (W < 1 || H < 1) return report_error(SVGIR_ERR_INVALID, "env_backdrop: bad image size W=%d H=%d", W, H);
+    if (env_h < 1 || env_w < 1 || (int64_t)env_h * env_w > (int64_t)1 << 26)
+        return report_error(SVGIR_ERR_INVALID, "env_backdrop: bad environment map size %d x %d", env_h, env_w);
+    if (!intr || !c2w_rot) return report_error(SVGIR_ERR_INVALID, "env_backdrop: the intrinsics and the camera rotation must be provided");
+    if (!env || !env_work) return report_error(SVGIR_ERR_INVALID, "env_backdrop: the environment map and its table must be provided");
+    if (!image || !opacity || !vfeature || !out)
+        return report_error(SVGIR_ERR_INVALID, "env_backdrop: image, opacity, vfeature and out must be provided");
+    if (!std::isfinite(intr[0]) || !std::isfinite(intr[1]) || intr[0] == 0.f || intr[1] == 0.f)
+        return report_error(SVGIR_ERR_INVALID, "env_backdrop: the focal lengths must be finite and non-zero (fx=%g fy=%g)", (double)intr[0],
+                            (double)intr[1]);
+    if ((uintptr_t)env_work & 15) return report_error(SVGIR_ERR_INVALID, "env_backdrop: env_work must be 16-byte aligned (it is read as float4)");
+    const size_t N = (size_t)W * H, blocks = (N + BLOCK - 1) / BLOCK;
+    if (blocks > 0x7fffffffu) return report_error(SVGIR_ERR_INVALID, "env_backdrop: image %d x %d exceeds the supported size", W, H);
+    BackdropArgs a{};
+    a.W = W; a.H = H; a.fx = intr[0]; a.fy = intr[1]; a.cx = intr[2]; a.cy = intr[3];
+    for (int j = 0; j < 9; j++) { a.R[j] = c2w_rot[j]; a.T[j] = env_transform ? env_transform[j] : 0.f; }
+    a.has_T = env_transform != nullptr;
+    a.env_h = env_h; a.env_w = env_w; a.env_scale = env_scale; a.env_tab = (const float4*)env_work;
+    a.image = image; a.opacity = opacity; a.pbr = vfeature; a.out = out;
+    ShadeTables t;
+    t.env = env; t.env_tab = (float4*)env_work; t.ntexel = env_h * env_w; t.softplus = env_softplus;
+    hipStream_t s = (hipStream_t)stream;
+    StageMarks tm = stage_begin(s);
+    hipLaunchKernelGGL(backdrop_table_kernel, dim3((t.ntexel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, t);
+    stage_mark(tm, "backdrop_env_table");
+    hipLaunchKernelGGL(backdrop_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    stage_mark(tm, "backdrop");
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SVGIR_OK : report_error(SVGIR_ERR_HIP, "env_backdrop launch failed: %s", hipGetErrorString(e));
+}

@@ -18,6 +18,7 @@
 //   base_color, diffuse, lights, local_lights = srgb(x) o + (1 - o) bg      roughness, visibility = x o + (1 - o) bg
 #include "common.hpp"
 #include "d2n.hpp"
+#include "srgb.hpp"
 
 namespace svgir {
 
@@ -26,22 +27,7 @@ namespace {
 enum PlaneKind { K_SRGB_OF_OVER = 0, K_PLAIN = 1, K_OVER_SRGB = 2, K_OVER_LIN = 3, K_SRGB = 4 };
 struct PlaneGroup { int kind, src, vf, n; };   // src: first source channel; vf: source is vfeature; n: source channels (1 or 3)
 
-// torch.clamp / clamp_min propagate NaN (fminf / fmaxf return the other operand): a NaN plane or opacity stays NaN in every result
-// it reaches, as in the reference, instead of turning into a valid-looking pixel.  Plain compares: false on NaN, so x passes through.
-__device__ __forceinline__ float clamp_min_nan(float x, float lo) { return x < lo ? lo : x; }
-__device__ __forceinline__ float clamp01_nan(float y) { return y < 0.f ? 0.f : (y > 1.f ? 1.f : y); }
-
-__device__ __forceinline__ float srgb(float x) {
-    const float y = x > 0.0031308f ? powf(x, 1.0f / 2.4f) * 1.055f - 0.055f : 12.92f * x;   // (NaN takes the linear branch: NaN)
-    return clamp01_nan(y);
-}
-// d srgb / dx: 0 where the final clip to [0,1] is active -- and for a NaN argument, as torch.clamp's backward (its mask
-// min <= y <= max is false): the gradients of a NaN pixel stay confined to that pixel either way, the kernel being per-pixel
-__device__ __forceinline__ float dsrgb(float x) {
-    const float y = x > 0.0031308f ? powf(x, 1.0f / 2.4f) * 1.055f - 0.055f : 12.92f * x;
-    if (!(y >= 0.f && y <= 1.f)) return 0.f;
-    return x > 0.0031308f ? (1.055f / 2.4f) * powf(x, 1.0f / 2.4f - 1.0f) : 12.92f;
-}
+// (clamp_min_nan, clamp01_nan, srgb, dsrgb: srgb.hpp, shared with the environment backdrop, csrc/backdrop.hip)
 
 template <bool TRAINING> struct Groups;
 template <> struct Groups<true> {

@@ -137,6 +137,9 @@ def _load():
     lib.svgir_smooth_loss_forward.argtypes = [C.c_int32] * 3 + [C.POINTER(SmoothTerm)] + [C.c_void_p] * 4
     lib.svgir_smooth_loss_backward.restype = C.c_int
     lib.svgir_smooth_loss_backward.argtypes = [C.c_int32] * 3 + [C.POINTER(SmoothTerm)] + [C.c_void_p] * 3
+    # the eval view's environment backdrop (svgir_harness/render_view.py): W, H, three host arrays, env + its shape / flags, device pointers, stream
+    lib.svgir_env_backdrop.restype = C.c_int
+    lib.svgir_env_backdrop.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 6
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -157,7 +160,7 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_pbgi_trace_radiance", "svgir_knn_bytes", "svgir_knn_mean_dist", "svgir_knn_topk", "svgir_pbgi_irradiance_sample",
            "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance", "svgir_geometry_loss_partials",
            "svgir_geometry_loss_forward", "svgir_geometry_loss_backward", "svgir_smooth_loss_partials", "svgir_smooth_loss_forward",
-           "svgir_smooth_loss_backward")
+           "svgir_smooth_loss_backward", "svgir_env_backdrop")
 
 
 _scope = threading.local()

@@ -3,11 +3,12 @@
 
 Only the parts that belong to the hot path and its immediate callers are reproduced: the SV-BRDF shading and packing
 (svgss.py:125-166, fused: gaussian_renderer/shading.py), the rasterizer call (:170-182) and the image-space unpacking
-(:188-246: division by the rendered opacity, channel split, sRGB, compositing over the background).  The
-`depth2normal` pseudo normal and the environment backdrop of the eval branch need the reference's camera class and
-are left to the caller."""
+(:188-246: division by the rendered opacity, channel split, sRGB, compositing over the background) and the environment
+backdrop that ends every eval view (:255-260: `environment_backdrop`, from the camera's intrinsics and rotation).  The
+`depth2normal` pseudo normal needs the reference's camera class and is left to the caller."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from gaussian_renderer import _native as N
@@ -187,22 +188,91 @@ def unpack(rendered, bg_color, is_training):
     return res
 
 
-def render_svgss_view(sc, mat, light, is_training, fused=False):
+def _host_f32(x, shape, what):
+    """A small camera / transform matrix as a contiguous fp32 numpy array (tensors on the GPU are copied to the host)."""
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+    if a.shape not in shape:
+        raise RuntimeError(f"environment_backdrop: {what} must have shape {' or '.join(str(s) for s in shape)}, got {a.shape}")
+    return a
+
+
+def environment_backdrop(light, intrinsics, c2w, image, opacity, vfeature):
+    """svgss.py:255-260 as one HIP kernel (csrc/backdrop.hip): the light looked up along the camera's world-space pixel directions
+    (`Camera.get_world_directions`) and the three images the eval branch builds from it.
+    light: DirectLightMap-like (.env) or EnvLight-like (.envmap [, .transform]), as for the shading (shading._env_of);
+    intrinsics [3,3] (`Camera.intrinsics`: fx, fy, cx, cy in pixels), c2w [4,4] or [3,3] (`Camera.c2w`): tensors or arrays, read on
+    the host; image [3,H,W], opacity [1,H,W], vfeature [>= 3,H,W]: the rasterizer's raw outputs (its first three vfeature planes are
+    the pbr).  Returns {env_only, render_env, pbr_env}: [3,H,W] views of one buffer; they never require grad (the reference runs
+    this tail under no_grad)."""
+    dev = image.device
+    if dev.type != "cuda" or opacity.device.type != "cuda" or vfeature.device.type != "cuda":
+        raise RuntimeError("environment_backdrop: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
+    K = _host_f32(intrinsics, ((3, 3),), "intrinsics")
+    R = _host_f32(c2w, ((4, 4), (3, 3)), "c2w")[:3, :3]
+    intr = (C.c_float * 4)(K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+    rot = (C.c_float * 9)(*R.reshape(-1))
+    src = getattr(light, "env", getattr(light, "envmap", None))
+    if torch.is_tensor(src) and src.device.type != "cuda":
+        raise RuntimeError("environment_backdrop: the light must live on the GPU (libsvgir_raster.so has no CPU path)")
+    with torch.no_grad(), torch.cuda.device(dev):
+        env, softplus, scale, transform = shading._env_of(light)
+        tr = None if transform is None else (C.c_float * 9)(*_host_f32(transform, ((3, 3),), "the light's transform").reshape(-1))
+        env = N.f32c(env.detach(), dev)
+        env = env.reshape((-1,) + tuple(env.shape[-3:]))[0]
+        if env.shape[-1] != 3:
+            raise RuntimeError(f"environment_backdrop: the environment map must have 3 channels, got {tuple(env.shape)}")
+        im, op, vf = (N.f32c(t.detach(), dev) for t in (image, opacity, vfeature))
+        H, W = im.shape[-2], im.shape[-1]
+        if im.numel() != 3 * H * W or op.numel() != H * W or vf.dim() != 3 or vf.shape[0] < 3 or tuple(vf.shape[1:]) != (H, W):
+            raise RuntimeError(f"environment_backdrop: expected image [3,H,W], opacity [1,H,W], vfeature [>=3,H,W], got "
+                               f"{tuple(image.shape)}, {tuple(opacity.shape)}, {tuple(vfeature.shape)}")
+        work = torch.empty((env.shape[0] * env.shape[1], 4), dtype=torch.float32, device=dev)
+        out = N.out_tensor((9, H, W), torch.float32, dev)
+        N.check(N.lib.svgir_env_backdrop(W, H, intr, rot, tr, env.data_ptr(), env.shape[0], env.shape[1], int(softplus), float(scale),
+                                         work.data_ptr(), im.data_ptr(), op.data_ptr(), vf.data_ptr(), out.data_ptr(),
+                                         N.stream_ptr(dev)), "env_backdrop")
+    return dict(env_only=out[0:3], render_env=out[3:6], pbr_env=out[6:9])
+
+
+def camera_of(sc):
+    """The `camera` argument of render_svgss_view for a runner.to_torch() (or numpy) scene, by the reference's formulas:
+    `Camera.get_intrinsics` (scene/cameras.py:116-130, fx is None: focal = size / (2 tan(FoV / 2)), principal point at the image
+    centre) and `Camera.c2w` = the inverse of the view matrix (:81; sc["viewmatrix"] is the transposed world_view_transform)."""
+    W, H = int(sc["W"]), int(sc["H"])
+    K = np.array([[W / (2.0 * float(sc["tanfovx"])), 0.0, W / 2.0], [0.0, H / (2.0 * float(sc["tanfovy"])), H / 2.0], [0.0, 0.0, 1.0]])
+    vm = sc["viewmatrix"]
+    vm = vm.detach().cpu().numpy() if torch.is_tensor(vm) else np.asarray(vm)
+    c2w = np.linalg.inv(vm.astype(np.float64).T)
+    return dict(intrinsics=torch.from_numpy(K.astype(np.float32)), c2w=torch.from_numpy(c2w.astype(np.float32)))
+
+
+def _with_backdrop(res, rendered, light, is_training, camera):
+    if camera is not None and not is_training:
+        res.update(environment_backdrop(light, camera["intrinsics"], camera["c2w"], rendered[1], rendered[3], rendered[6]))
+    return res
+
+
+def render_svgss_view(sc, mat, light, is_training, fused=False, camera=None):
     """sc: runner.to_torch() scene (geometry + camera); mat: dict with base_color [P,12], roughness [P,4], normals
     [P,4,3], viewdirs [P,3], radiance / dirs [P,Ns,3], visibility / areas [P,Ns,1]; light: DirectLightMap-like (.env).
     Returns (results dict, means2D gradient carrier).  fused=True: the shading runs inside the rasterizer calls, for the surfels
-    the view reads only (shading.render_shaded); same results."""
+    the view reads only (shading.render_shaded); same results.
+    camera: dict(intrinsics=[3,3], c2w=[4,4] or [3,3]) (camera_of(sc) derives it from the scene); with is_training=False the results
+    gain the eval branch's env_only, render_env and pbr_env (environment_backdrop, from the rasterizer's raw image, opacity and
+    vfeature).  None: no backdrop, the results are what they are without this argument."""
     means2D = torch.zeros_like(sc["means3D"], requires_grad=torch.is_grad_enabled())
     if fused:
         rendered, _ = shading.render_shaded(runner.settings(sc, "svgss"), sc["means3D"], means2D, sc["opacities"], sc["shs"],
                                             sc["scales"], sc["rotations"], mat["base_color"], mat["roughness"], mat["normals"],
                                             mat["viewdirs"], mat["radiance"], light, mat["visibility"], mat["dirs"], mat["areas"],
                                             is_training)
-        return unpack(rendered, sc["bg"], is_training), means2D
+        return _with_backdrop(unpack(rendered, sc["bg"], is_training), rendered, light, is_training, camera), means2D
     feats, vfeats, _ = shading.shade_and_pack(mat["base_color"], mat["roughness"], mat["normals"], mat["viewdirs"],
                                               mat["radiance"], light, mat["visibility"], mat["dirs"], mat["areas"],
                                               sc["viewmatrix"], is_training)
     rast = GaussianRasterizer(runner.settings(sc, "svgss"))
     rendered = rast(means3D=sc["means3D"], means2D=means2D, opacities=sc["opacities"], shs=sc["shs"],
                     scales=sc["scales"], rotations=sc["rotations"], features=feats, vfeatures=vfeats)
-    return unpack(rendered, sc["bg"], is_training), means2D
+    return _with_backdrop(unpack(rendered, sc["bg"], is_training), rendered, light, is_training, camera), means2D
