@@ -666,6 +666,74 @@ int svgir_pbgi_irradiance_sample_backward(int32_t N, int32_t S, const int32_t* s
 int svgir_pbgi_irradiance(int32_t N, int32_t S, const float* ray_d, const float* envmap, const float* normals, const float* albedos,
                           const float* roughnesses, const int32_t* hit_indices, const float* uvs, float* out, void* stream);
 
+/* The whole radiance-consistency loss of GaussianModel.get_radiance_loss (scene/gaussian_model.py:544-575) as one forward and one backward
+ * call: the selection of the sample, the light of the hit surfel looked up inside the kernel, the irradiance sum above and the L1 against
+ * the cached radiance.  L = mean over [N,3] of |R - T|.  No [N,S,3] light tensor and no [N,S,3] gradient exist on this path.
+ *   Inputs (svgir_radiance_loss_params; all device pointers, fp32 / int32, contiguous): xyz [N,3], camera_center [3], geo_normal [N,3],
+ *   ray_d [N,S,3] (the incident directions: both the selection's and the kernels' ray_d), areas [N,S], visibility [N,S], normals /
+ *   albedos [N,12], roughnesses [N,4], hit_indices [N,S], uvs [N,S,2] as above; radiances [N,S,3] (the raw cache), radiance_ratio [1];
+ *   the light: env [env_h,env_w,3] with env_softplus / env_scale (f = softplus, scale 2: DirectLightMap; f = identity, scale 1: EnvLight's
+ *   32 x 64 resample) and env_transform (device [9], row-major, or null: the lookup direction is transform * d, EnvLight.transform).
+ *   work: svgir_radiance_loss_work_bytes(N, env_h, env_w) bytes of scratch, 16-byte aligned (the f(env) table, the env-gradient table, the
+ *   partial sums); written by each call and free again when its kernels have run; the backward needs no content from the forward.
+ *   Selection, per row i: v = (xyz_i - c) / max(|xyz_i - c|, 1e-12), r = (2 (g_i . v)) g_i + v, score_s = dot(ray_d[i,s], r) *
+ *   (1 - visibility[i,s]); every operation a separate fp32 one (no contraction; dot = (x*x + y*y) + z*z; correctly rounded sqrt and
+ *   divide).  p = sample_indices[i] follows torch.argmax: the first index of the maximum; a NaN score beats every number and the first
+ *   NaN wins; +0 and -0 tie.  (A surfel at the camera centre has v = 0, every score +-0, p = 0.)
+ *   R [N,3] = svgir_pbgi_irradiance_sample's sum for (i, p) -- both quirks and all four decisions above hold -- with
+ *   envmap[h,s,c] = (env_scale * bilinear(f(env))(ray_d[h,s]))_c * areas[h,s]: the lat-long lookup of the shading kernels on the RAW
+ *   direction d (phi = acos(d.z) - 1e-6, theta = atan2(d.y, d.x); grid_sample with align_corners, zero padding: a tap outside the map
+ *   adds exactly 0, a tap inside is multiplied even at weight 0) on the same f(env) table, with the transform, the angles and the grid
+ *   coordinates in fp64 and the four weights rounded to fp32 at the end: a texel's gradient is a sum of (upstream * weight) terms, and
+ *   an fp32 coordinate, off by about env_w * 2^-24 texels absolutely, would leave a small weight few digits.  |d.z| > 1 has no
+ *   latitude: the acos is NaN, the sample's light is NaN (as the reference's arccos makes it) and so is R of every row that sums it.
+ *   T[i,c] = radiances[i,p,c] * radiance_ratio with NaN replaced by 0 (get_radiances' nan_to_num(nan = 0)); +-inf stays -- torch's
+ *   nan_to_num would also clamp an infinite product to the largest finite number; here it stays infinite and falls under the non-finite
+ *   rule below.
+ *   svgir_radiance_loss_forward writes sample_indices [N], radiance = R [N,3], *loss_sum = sum |R - T| (each difference fp32, summed in
+ *       double: per row, per workgroup, then a fixed tree) and *loss = fp32(loss_sum / 3N).  The same input gives the same bits.
+ *   svgir_radiance_loss_backward, from the forward's sample_indices and radiance and the upstream scalar *d_loss (device): d_R[i,c] =
+ *       d_loss * sign(R - T) / 3N, d_albedos [N,12] and d_roughnesses [N,4] as svgir_pbgi_irradiance_sample_backward gives for d_out = d_R;
+ *       d_env [env_h,env_w,3] (may be null: not wanted) = f'(env) * sum over contributing (i, s, c) and the four taps j of
+ *       d_R[i,c] irr_c / S * areas[h,s] * env_scale * w_j; *d_radiance_ratio (may be null) = sum -d_R[i,c] radiances[i,p,c] over the
+ *       elements whose product radiances * ratio is finite.  Every element of every output is written; the call clears what it
+ *       accumulates into.  Rows that share a hit surfel and samples that share a texel add with float atomics: the backward is
+ *       repeatable only up to the order of those adds (d_radiance_ratio is a fixed tree and is repeatable).
+ *   One more decision of this project's own:
+ *     - A non-finite value gives no gradient.  Where R[i,c] or T[i,c] is not finite the loss is NaN, as in torch, but d_R[i,c] = 0: the
+ *       element contributes to no gradient.  The rule is per element: a light that is NaN or infinite in one channel only is left
+ *       out of that channel's sums (skipped, not multiplied by 0) and the other channels of the row contribute as usual.  (Torch propagates sign(NaN) = NaN into every gradient the row touches and from there into
+ *       the whole env map.)  An element of d_env nothing was added to is exactly 0 whatever env holds there.
+ *   N = 0 launches nothing and writes nothing; the loss of no rows is NaN (torch's mean of an empty tensor), which is the caller's to
+ *   return.  Everything is launched on `stream`; nothing waits on the host. */
+typedef struct svgir_radiance_loss_params {
+    int32_t N, S;
+    const float* xyz;
+    const float* camera_center;
+    const float* geo_normal;
+    const float* ray_d;
+    const float* areas;
+    const float* visibility;
+    const float* normals;
+    const float* albedos;
+    const float* roughnesses;
+    const int32_t* hit_indices;
+    const float* uvs;
+    const float* radiances;
+    const float* radiance_ratio;
+    const float* env;
+    int32_t env_h, env_w, env_softplus;
+    float env_scale;
+    const float* env_transform;
+    void* work;
+} svgir_radiance_loss_params;
+size_t svgir_radiance_loss_work_bytes(int32_t N, int32_t env_h, int32_t env_w);
+int svgir_radiance_loss_forward(const svgir_radiance_loss_params* p, int32_t* sample_indices, float* radiance, double* loss_sum, float* loss,
+                                void* stream);
+int svgir_radiance_loss_backward(const svgir_radiance_loss_params* p, const int32_t* sample_indices, const float* radiance,
+                                 const float* d_loss, float* d_env, float* d_albedos, float* d_roughnesses, float* d_radiance_ratio,
+                                 void* stream);
+
 /* Exact k-nearest-neighbour search over a point cloud: simple_knn's `distCUDA2` (submodules/simple-knn/simple_knn.cu:147-221; the initial
  * scales of GaussianModel.create_from_pcd) and custom_knn's `topKdistCUDA2` (no source upstream; get_knn_loss,
  * scene/gaussian_model.py:577-592).  points [P,3]; `work` is svgir_knn_bytes bytes of scratch, written by the call and free again when the

@@ -20,9 +20,16 @@
 //
 // A term is evaluated without contraction to fused multiply-adds, with correctly rounded divides and square roots, in the order the
 // header gives: the numpy fp32 restatement of tests/radiance_cases.py then differs from a term only by exp2's rounding.
+//
+// The second half of the file is the whole radiance-consistency loss around that sum as one forward and one backward kernel
+// (svgir_radiance_loss_forward / _backward; GaussianModel.get_radiance_loss, scene/gaussian_model.py:544-575): the selection of the
+// sample, the light of the hit surfel's escaped samples looked up in the kernel (env_lookup.hpp, the f(env) table of the shading
+// kernels) and the L1 against the cached radiance.  It shares irr_load_corners / irr_light / irr_spec with the kernels above; no
+// [N,S,3] light tensor and no [N,S,3] gradient exist on that path.  See the comment in front of radiance_loss_fwd_kernel.
 #include <cmath>
 
 #include "common.hpp"
+#include "env_lookup.hpp"
 
 namespace svgir {
 
@@ -268,11 +275,473 @@ bool irr_args_ok(int32_t N, int32_t S, const void* a, const void* b, const void*
     return N == 0 || (a && b && c && d && e2 && f && g);
 }
 
+
+// ---- the fused radiance-consistency loss -----------------------------------------------------------------------------------------------
+// Forward, one wave per row i (IRR_WAVES rows per workgroup), lanes over samples in passes of 64:
+//   1. selection: score_s = dot(d[i,s], r) * (1 - vis[i,s]) with v = (xyz_i - c) / max(|xyz_i - c|, 1e-12), r = (2 (g_i.v)) g_i + v, every
+//      operation a separate fp32 one in the reference's order; p = torch.argmax's index: the first NaN if there is one, else the first index
+//      of the maximum (+0 == -0).  Every lane keeps its best (value, index) over the passes -- a later equal value never displaces an earlier
+//      index -- and a butterfly over the wave takes the best of the 64 under the same order.
+//   2. the irradiance of h = hit[i,p] as in irradiance_kernel<false>, the light of a sample being (scale * bilinear(f(env))(d[h,s])) *
+//      area[h,s] from the taps of the raw direction (env_taps<double>) and the f(env) float4 table.
+//   3. T = nan_to_num(radiances[i,p] * ratio, nan = 0); the row's |R - T| (fp32 differences) is summed in double: wave, then workgroup
+//      partials in wave order, then radiance_loss_final_kernel's fixed tree.  Same bits on every run.
+// Backward, one wave per row in persistent workgroups of RLB_WAVES waves: d_R = g sign(R - T) / 3N from the saved p and R (zero where R or
+// T is not finite), d_albedos / d_roughnesses as irradiance_sample_bwd_kernel, the env gradient scattered to the four taps of every
+// contributing sample -- into a workgroup-private double table in LDS when it fits (flushed once per workgroup with float atomics), with
+// global float atomics otherwise -- and d_ratio through per-workgroup partials.  radiance_loss_env_grad_kernel applies f'(env).
+constexpr int RLB_WAVES = 8;                      // rows per pass of a backward workgroup
+constexpr int RLB_MAX_BLOCKS = 1024;              // backward workgroups (= d_ratio partials) at most
+constexpr size_t RL_LDS_BYTES = 160 * 1024;       // as shade_backward_impl: the double table must fit beside the kernel's other LDS
+
+struct RadLossArgs {
+    int N, S;
+    const float *xyz, *cam, *geo, *ray_d, *area, *vis, *normals, *albedos, *roughnesses, *uvs, *radiances, *ratio;
+    const int32_t* hit;
+    const float4* env_tab;
+    int env_h, env_w;
+    float env_scale;
+    const float* transform;   // device [9], row-major: the lookup direction is T d (EnvLight); null: none
+    // forward
+    int32_t* sample_out;
+    float* R_out;
+    double* partial;          // [ceil(N / IRR_WAVES)]
+    // backward
+    const int32_t* sample_in;
+    const float *R_in, *g;
+    float *d_albedos, *d_roughnesses, *d_envtab;   // d_envtab [He*We*3] (null: the env gets no gradient)
+    double* ratio_part;       // [gridDim.x]
+    int env_in_lds, ntex3;
+};
+
+struct RlTransform { float t[9]; bool on; };
+__device__ __forceinline__ RlTransform rl_transform(const RadLossArgs& a) {
+    RlTransform T;
+    T.on = a.transform != nullptr;
+#pragma unroll
+    for (int j = 0; j < 9; j++) T.t[j] = T.on ? a.transform[j] : 0.f;
+    return T;
+}
+
+// The coordinate type of the loss's lookup (env_taps<T>, env_lookup.hpp).  double: the gradient of a texel is a sum of (upstream *
+// weight) terms and is held to a bound relative to those terms, so a weight must be good relative to ITSELF, and an fp32 coordinate --
+// about We eps32 texels off, absolutely -- gives a weight of 0.01 only three digits.  (The forward value alone would not need it.)  The
+// direction goes through the light's transform in the same type for the same reason.
+using RlCoord = double;
+
+// the light of one sample: taps of the (transformed) raw direction, env[c] = (scale * sum_j w_j f(env)[tap_j, c]) * area.  grid_sample's two
+// corner rules as in backdrop.hip: a tap outside the map adds exactly 0, a tap inside is multiplied even at weight 0.  A direction with
+// |d.z| > 1 has no latitude: acos is NaN, and the light is NaN as the reference's arccos makes it (`nan` says so whatever index the
+// taps of a NaN coordinate got: env_taps range-checks them); a NaN light makes the row's R NaN, see the non-finite rule.
+__device__ __forceinline__ void rl_light(const RadLossArgs& a, const RlTransform& T, const float* ld, float area, EnvTap& t, float* env) {
+    RlCoord d[3] = {(RlCoord)ld[0], (RlCoord)ld[1], (RlCoord)ld[2]};
+    if (T.on) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) d[j] = ((RlCoord)T.t[3 * j] * ld[0] + (RlCoord)T.t[3 * j + 1] * ld[1]) + (RlCoord)T.t[3 * j + 2] * ld[2];
+    }
+    env_taps<RlCoord>(d, a.env_h, a.env_w, t);
+    const bool nan = !(d[2] >= (RlCoord)-1 && d[2] <= (RlCoord)1) || d[0] != d[0] || d[1] != d[1];
+    float4 tex[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) tex[j] = a.env_tab[t.idx[j] >= 0 ? t.idx[j] : 0];
+    float E[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const bool ok = t.idx[j] >= 0;
+        E[0] += ok ? t.w[j] * tex[j].x : 0.f;
+        E[1] += ok ? t.w[j] * tex[j].y : 0.f;
+        E[2] += ok ? t.w[j] * tex[j].z : 0.f;
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) env[ch] = nan ? NAN : (E[ch] * a.env_scale) * area;
+}
+
+// torch.argmax's order on (value, index) pairs: does (nv, ni) come before (bv, bi)?  An index < 0 is "no element".
+__device__ __forceinline__ bool rl_before(float nv, int ni, float bv, int bi) {
+    if (ni < 0) return false;
+    if (bi < 0) return true;
+    const bool nn = nv != nv, bn = bv != bv;
+    if (nn || bn) return nn && (!bn || ni < bi);
+    return nv > bv || (nv == bv && ni < bi);
+}
+
+__device__ __forceinline__ int rl_hit_of(const RadLossArgs& a, size_t i, int p) {
+    if (p < 0 || p >= a.S) return -1;
+    const int h = a.hit[i * (size_t)a.S + p];
+    return (h < 0 || h >= a.N) ? -1 : h;
+}
+
+__global__ void __launch_bounds__(BLOCK) radiance_loss_table_kernel(const ShadeTables t, float* z0, size_t n0, float* z1, size_t n1) {
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < (size_t)t.entries()) shade_table_entry(t, (int)i);
+    if (i < (size_t)t.nzero) t.zero[i] = 0.f;   // backward: the env-gradient table and the two per-surfel gradients
+    if (i < n0) z0[i] = 0.f;
+    if (i < n1) z1[i] = 0.f;
+}
+
+__global__ void __launch_bounds__(BLOCK) radiance_loss_fwd_kernel(const RadLossArgs a) {
+    __shared__ double wsum[IRR_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t i = (size_t)blockIdx.x * IRR_WAVES + wave;
+    const int S = a.S;
+    double rowsum = 0.0;
+    if (i < (size_t)a.N) {   // (wave-uniform)
+        // 1. selection
+        float v[3] = {a.xyz[i * 3] - a.cam[0], a.xyz[i * 3 + 1] - a.cam[1], a.xyz[i * 3 + 2] - a.cam[2]};
+        const float len = fmaxf(sqrtf(irr_dot(v, v)), 1e-12f);
+        v[0] = v[0] / len; v[1] = v[1] / len; v[2] = v[2] / len;
+        const float gn[3] = {a.geo[i * 3], a.geo[i * 3 + 1], a.geo[i * 3 + 2]};
+        const float two = 2.0f * irr_dot(gn, v);
+        const float r[3] = {two * gn[0] + v[0], two * gn[1] + v[1], two * gn[2] + v[2]};
+        float bv = 0.f;
+        int bi = -1;
+        for (int s = lane; s < S; s += IRR_WAVE) {
+            const size_t is = i * (size_t)S + s;
+            const float d[3] = {a.ray_d[is * 3], a.ray_d[is * 3 + 1], a.ray_d[is * 3 + 2]};
+            const float sc = irr_dot(d, r) * (1.0f - a.vis[is]);
+            if (rl_before(sc, s, bv, bi)) { bv = sc; bi = s; }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const float ov = __shfl_xor(bv, m);
+            const int oi = __shfl_xor(bi, m);
+            if (rl_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        const int p = __builtin_amdgcn_readfirstlane(bi);   // (S >= 1: a valid index)
+        // 2. the irradiance of the hit surfel under the looked-up light
+        const int hh = __builtin_amdgcn_readfirstlane(rl_hit_of(a, i, p));
+        float acc[3] = {0.f, 0.f, 0.f};
+        if (hh >= 0) {
+            const size_t h = (size_t)hh;
+            const float* vd = a.ray_d + (i * (size_t)S + p) * 3;
+            const float vdir[3] = {vd[0], vd[1], vd[2]};
+            IrrCorners c;
+            irr_load_corners<false>(c, vdir, h, a.normals, a.albedos, a.roughnesses);
+            const RlTransform T = rl_transform(a);
+            const float fs = (float)S;
+            for (int s = lane; s < S; s += IRR_WAVE) {
+                const size_t hs = h * (size_t)S + s;
+                if (a.hit[hs] != -1) continue;   // occluded secondary
+                const float ld[3] = {a.ray_d[hs * 3], a.ray_d[hs * 3 + 1], a.ray_d[hs * 3 + 2]};
+                IrrLight q;
+                irr_light(q, c, ld, a.uvs[hs * 2], a.uvs[hs * 2 + 1]);
+                EnvTap tp;
+                float env[3];
+                rl_light(a, T, ld, a.area[hs], tp, env);
+                float b[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) b[k] = irr_spec<false>(c, q, k, nullptr);
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) {
+                    float t[4];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) t[k] = b[k] + c.alb[ch][k] * IRR_1_PI;
+                    const float irr = ((q.w[0] * t[0] + q.w[1] * t[1]) + q.w[2] * t[2]) + q.w[3] * t[3];
+                    acc[ch] += (irr * env[ch]) / fs;
+                }
+            }
+        }
+        // 3. target and L1
+        const float ratio = a.ratio[0];
+        float diff[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            acc[ch] = wave_sum(acc[ch]);
+            float t = a.radiances[(i * (size_t)S + p) * 3 + ch] * ratio;
+            t = t != t ? 0.f : t;   // nan_to_num(nan = 0): +-inf stays
+            diff[ch] = fabsf(acc[ch] - t);
+        }
+        rowsum = ((double)diff[0] + (double)diff[1]) + (double)diff[2];
+        if (lane == 0) a.sample_out[i] = p;
+        if (lane < 3) a.R_out[i * 3 + lane] = lane == 0 ? acc[0] : lane == 1 ? acc[1] : acc[2];
+    }
+    if (lane == 0) wsum[wave] = rowsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < IRR_WAVES; w++) t += wsum[w];
+        a.partial[blockIdx.x] = t;
+    }
+}
+
+constexpr int RL_FINAL = 1024;
+// one workgroup: thread t adds partial[t], partial[t + 1024], ... in order, then a fixed tree.  sum_out = the sum, loss = fp32(sum / count)
+__global__ void __launch_bounds__(RL_FINAL) radiance_loss_final_kernel(const double* __restrict__ partial, size_t n, double count,
+                                                                       double* __restrict__ sum_out, float* __restrict__ loss) {
+    __shared__ double part[RL_FINAL];
+    double t = 0.0;
+    for (size_t k = threadIdx.x; k < n; k += RL_FINAL) t += partial[k];
+    part[threadIdx.x] = t;
+    __syncthreads();
+    for (int h = RL_FINAL / 2; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        *sum_out = part[0];
+        *loss = (float)(part[0] / count);
+    }
+}
+
+__global__ void __launch_bounds__(RLB_WAVES * 64) radiance_loss_bwd_kernel(const RadLossArgs a) {
+    extern __shared__ double rl_smem[];   // [RLB_WAVES] the waves' d_ratio sums, then the env-gradient table [ntex3] (env_in_lds)
+    double* sEnv = rl_smem + RLB_WAVES;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int S = a.S, N = a.N;
+    if (a.env_in_lds) {
+        for (int k = threadIdx.x; k < a.ntex3; k += RLB_WAVES * 64) sEnv[k] = 0.0;
+        __syncthreads();
+    }
+    const float gscale = a.g[0] / (float)(3.0 * (double)N);
+    const float ratio = a.ratio[0];
+    const RlTransform T = rl_transform(a);
+    const float fs = (float)S;
+    double ratio_acc = 0.0;   // (wave-uniform)
+    for (size_t row0 = (size_t)blockIdx.x * RLB_WAVES; row0 < (size_t)N; row0 += (size_t)gridDim.x * RLB_WAVES) {
+        const size_t i = row0 + wave;
+        if (i >= (size_t)N) continue;   // (wave-uniform; no barrier inside the loop)
+        const int p = __builtin_amdgcn_readfirstlane(a.sample_in[i]);
+        if (p < 0 || p >= S) continue;
+        float g[3];
+        bool any = false;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const float R = a.R_in[i * 3 + ch];
+            const float raw = a.radiances[(i * (size_t)S + p) * 3 + ch];
+            const float tr = raw * ratio;
+            const float t = tr != tr ? 0.f : tr;
+            // the non-finite rule: a non-finite R or T makes the loss NaN and gives no gradient
+            const bool ok = fabsf(R) < INFINITY && fabsf(t) < INFINITY;
+            const float df = R - t;
+            const float sg = !ok ? 0.f : df > 0.f ? 1.f : df < 0.f ? -1.f : 0.f;
+            g[ch] = sg * gscale;
+            if (sg != 0.f && fabsf(tr) < INFINITY) ratio_acc += (double)(-(g[ch] * raw));   // nan_to_num passes the gradient of finite products only
+            any = any || g[ch] != 0.f;
+        }
+        const int hh = __builtin_amdgcn_readfirstlane(rl_hit_of(a, i, p));
+        if (hh < 0 || !any) continue;
+        const size_t h = (size_t)hh;
+        const float* vd = a.ray_d + (i * (size_t)S + p) * 3;
+        const float vdir[3] = {vd[0], vd[1], vd[2]};
+        IrrCorners c;
+        irr_load_corners<false>(c, vdir, h, a.normals, a.albedos, a.roughnesses);
+        float dalb[3][4] = {}, drough = 0.f;
+        for (int s = lane; s < S; s += IRR_WAVE) {
+            const size_t hs = h * (size_t)S + s;
+            if (a.hit[hs] != -1) continue;
+            const float ld[3] = {a.ray_d[hs * 3], a.ray_d[hs * 3 + 1], a.ray_d[hs * 3 + 2]};
+            IrrLight q;
+            irr_light(q, c, ld, a.uvs[hs * 2], a.uvs[hs * 2 + 1]);
+            const float area = a.area[hs];
+            EnvTap tp;
+            float env[3];
+            rl_light(a, T, ld, area, tp, env);
+            float b[4], ds[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) b[k] = irr_spec<true>(c, q, k, &ds[k]);
+            const float dq = ((q.w[0] * ds[0] + q.w[1] * ds[1]) + q.w[2] * ds[2]) + q.w[3] * ds[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                float t[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    t[k] = b[k] + c.alb[ch][k] * IRR_1_PI;
+                    // (a channel without upstream is SKIPPED, not multiplied by 0: its light may be the NaN / inf that made R[i,ch] non-finite)
+                    if (g[ch] != 0.f) dalb[ch][k] += (((g[ch] * q.w[k]) * env[ch]) * IRR_1_PI) / fs;
+                }
+                const float irr = ((q.w[0] * t[0] + q.w[1] * t[1]) + q.w[2] * t[2]) + q.w[3] * t[3];
+                if (a.d_envtab && g[ch] != 0.f) {
+                    const float de = (((g[ch] * irr) / fs) * area) * a.env_scale;   // d L / d (the bilinear value of channel ch)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const float dv = de * tp.w[j];
+                        if (tp.idx[j] >= 0 && dv != 0.f) {
+                            if (a.env_in_lds) atomicAdd(&sEnv[tp.idx[j] * 3 + ch], (double)dv);   // ds_add_f64
+                            else atomic_add_f32(a.d_envtab + (size_t)tp.idx[j] * 3 + ch, dv);
+                        }
+                    }
+                }
+            }
+            const float ge[3] = {g[0] != 0.f ? (g[0] * env[0]) / fs : 0.f, g[1] != 0.f ? (g[1] * env[1]) / fs : 0.f,
+                                 g[2] != 0.f ? (g[2] * env[2]) / fs : 0.f};
+            drough += ((ge[0] + ge[1]) + ge[2]) * dq;
+        }
+        float mine = 0.f;   // lane 4 * ch + k: d_albedos[h, 4 ch + k]; lane 12: d_roughnesses[h, 0]
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float t = wave_sum(dalb[ch][k]);
+                if (lane == ch * 4 + k) mine = t;
+            }
+        const float tr = wave_sum(drough);
+        if (lane == 12) mine = tr;
+        if (lane < 12) atomicAdd(a.d_albedos + h * 12 + lane, mine);
+        else if (lane == 12) atomicAdd(a.d_roughnesses + h * 4, mine);
+    }
+    if (lane == 0) rl_smem[wave] = ratio_acc;
+    __syncthreads();   // (also: every wave's LDS adds are done)
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < RLB_WAVES; w++) t += rl_smem[w];
+        a.ratio_part[blockIdx.x] = t;
+    }
+    if (a.env_in_lds) {
+        for (int k = threadIdx.x; k < a.ntex3; k += RLB_WAVES * 64) {
+            const float v = (float)sEnv[k];
+            if (v != 0.f) atomic_add_f32(&a.d_envtab[k], v);
+        }
+    }
+}
+
+// d_env = d f(env) * f'(env) (softplus' = sigmoid; an element nothing was added to is exactly 0, whatever env holds there) and, in
+// workgroup 0, d_ratio = the workgroups' partial sums in a fixed tree
+__global__ void __launch_bounds__(BLOCK) radiance_loss_env_grad_kernel(const float* __restrict__ env, const float* __restrict__ dtab,
+                                                                       float* __restrict__ denv, int n, int softplus,
+                                                                       const double* __restrict__ ratio_part, int nparts,
+                                                                       float* __restrict__ d_ratio) {
+    if (d_ratio && blockIdx.x == 0) {
+        __shared__ double part[BLOCK];
+        double t = 0.0;
+        for (int k = threadIdx.x; k < nparts; k += BLOCK) t += ratio_part[k];
+        part[threadIdx.x] = t;
+        __syncthreads();
+        for (int h = BLOCK / 2; h >= 1; h >>= 1) {
+            if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) *d_ratio = (float)part[0];
+    }
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (!denv || i >= n) return;
+    const float d = dtab[i], x = env[i];
+    denv[i] = d == 0.f ? 0.f : softplus ? d * (x > 20.f ? 1.f : 1.f / (1.f + expf(-x))) : d;
+}
+
+// the work buffer: [f(env) float4 table | env-gradient table, floats | partial sums, doubles]
+struct RlWork { size_t tab, dtab, part, bytes, nparts; };
+RlWork rl_work(int32_t N, int32_t env_h, int32_t env_w) {
+    RlWork w;
+    const size_t ntexel = (size_t)env_h * env_w;
+    w.tab = 0;
+    w.dtab = ntexel * 16;
+    w.part = w.dtab + ((ntexel * 3 * 4 + 15) & ~(size_t)15);
+    w.nparts = std::max(((size_t)N + IRR_WAVES - 1) / IRR_WAVES, (size_t)RLB_MAX_BLOCKS);
+    w.bytes = w.part + w.nparts * 8;
+    return w;
+}
+
+bool rl_args_ok(const svgir_radiance_loss_params* p) {
+    if (!p || p->N < 0 || p->S < 1 || p->env_h < 1 || p->env_w < 1) return false;
+    if ((size_t)p->N * (size_t)p->S > ((size_t)1 << 31) - 1 || (int64_t)p->env_h * p->env_w > (int64_t)1 << 26) return false;
+    if (p->N == 0) return true;
+    return p->xyz && p->camera_center && p->geo_normal && p->ray_d && p->areas && p->visibility && p->normals && p->albedos && p->roughnesses &&
+           p->hit_indices && p->uvs && p->radiances && p->radiance_ratio && p->env && p->work && !((uintptr_t)p->work & 15);
+}
+
+RadLossArgs rl_args(const svgir_radiance_loss_params* p, const RlWork& w) {
+    RadLossArgs a{};
+    a.N = p->N; a.S = p->S;
+    a.xyz = p->xyz; a.cam = p->camera_center; a.geo = p->geo_normal; a.ray_d = p->ray_d; a.area = p->areas; a.vis = p->visibility;
+    a.normals = p->normals; a.albedos = p->albedos; a.roughnesses = p->roughnesses; a.uvs = p->uvs; a.radiances = p->radiances;
+    a.ratio = p->radiance_ratio; a.hit = p->hit_indices;
+    a.env_tab = (const float4*)((char*)p->work + w.tab);
+    a.env_h = p->env_h; a.env_w = p->env_w; a.env_scale = p->env_scale; a.transform = p->env_transform;
+    a.ntex3 = p->env_h * p->env_w * 3;
+    return a;
+}
+
+ShadeTables rl_tables(const svgir_radiance_loss_params* p, const RlWork& w) {
+    ShadeTables t;
+    t.env = p->env; t.env_tab = (float4*)((char*)p->work + w.tab); t.ntexel = p->env_h * p->env_w; t.softplus = p->env_softplus;
+    return t;
+}
+
 }  // namespace
 
 }  // namespace svgir
 
 extern "C" {
+
+size_t svgir_radiance_loss_work_bytes(int32_t N, int32_t env_h, int32_t env_w) {
+    if (N < 0 || env_h < 1 || env_w < 1 || (int64_t)env_h * env_w > (int64_t)1 << 26) return 0;
+    return svgir::rl_work(N, env_h, env_w).bytes;
+}
+
+int svgir_radiance_loss_forward(const svgir_radiance_loss_params* p, int32_t* sample_indices, float* radiance, double* loss_sum, float* loss,
+                                void* stream) {
+    using namespace svgir;
+    if (!rl_args_ok(p) || (p->N > 0 && (!sample_indices || !radiance || !loss_sum || !loss))) return SVGIR_ERR_INVALID;
+    if (p->N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const RlWork w = rl_work(p->N, p->env_h, p->env_w);
+    RadLossArgs a = rl_args(p, w);
+    a.sample_out = sample_indices; a.R_out = radiance; a.partial = (double*)((char*)p->work + w.part);
+    const ShadeTables t = rl_tables(p, w);
+    const size_t blocks = ((size_t)p->N + IRR_WAVES - 1) / IRR_WAVES;
+    hipLaunchKernelGGL(radiance_loss_table_kernel, dim3((t.ntexel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, t, (float*)nullptr, (size_t)0,
+                       (float*)nullptr, (size_t)0);
+    hipLaunchKernelGGL(radiance_loss_fwd_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(radiance_loss_final_kernel, dim3(1), dim3(RL_FINAL), 0, s, (const double*)a.partial, blocks, 3.0 * (double)p->N, loss_sum,
+                       loss);
+    return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+}
+
+int svgir_radiance_loss_backward(const svgir_radiance_loss_params* p, const int32_t* sample_indices, const float* radiance, const float* d_loss,
+                                 float* d_env, float* d_albedos, float* d_roughnesses, float* d_radiance_ratio, void* stream) {
+    using namespace svgir;
+    if (!rl_args_ok(p) || (p->N > 0 && (!sample_indices || !radiance || !d_loss || !d_albedos || !d_roughnesses))) return SVGIR_ERR_INVALID;
+    if (p->N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const RlWork w = rl_work(p->N, p->env_h, p->env_w);
+    RadLossArgs a = rl_args(p, w);
+    a.sample_in = sample_indices; a.R_in = radiance; a.g = d_loss; a.d_albedos = d_albedos; a.d_roughnesses = d_roughnesses;
+    a.d_envtab = d_env ? (float*)((char*)p->work + w.dtab) : nullptr;
+    a.ratio_part = (double*)((char*)p->work + w.part);
+    size_t lds = (size_t)RLB_WAVES * 8;
+    if (d_env && lds + (size_t)a.ntex3 * 8 <= RL_LDS_BYTES) { a.env_in_lds = 1; lds += (size_t)a.ntex3 * 8; }
+    // persistent workgroups: as many as are resident at once (registers and the LDS table both bound the workgroups per CU: one at
+    // ~230 VGPRs whatever the table), RLB_MAX_BLOCKS at most -- every further workgroup would zero and flush a table of its own for nothing.
+    // Per device: the opt-in for > 64 KB of dynamic LDS, set once, and the resident count of the last LDS size asked for (a training run
+    // has one map size; both are idempotent, so races are harmless).
+    size_t resident = 0;
+    {
+        struct DevState { bool attr_set; size_t lds, resident; };
+        static DevState state[64] = {};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return SVGIR_ERR_HIP;
+        const bool slot = dev >= 0 && dev < 64;
+        if (!slot || !state[dev].attr_set) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(radiance_loss_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)RL_LDS_BYTES) != hipSuccess)
+                return SVGIR_ERR_HIP;
+            if (slot) state[dev].attr_set = true;
+        }
+        if (slot && state[dev].resident != 0 && state[dev].lds == lds) resident = state[dev].resident;
+        else {
+            int per_cu = 0, cus = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(radiance_loss_bwd_kernel), RLB_WAVES * 64, lds) != hipSuccess ||
+                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+                return SVGIR_ERR_HIP;
+            resident = (size_t)std::max(per_cu, 1) * (size_t)std::max(cus, 1);
+            if (slot) { state[dev].resident = 0; state[dev].lds = lds; state[dev].resident = resident; }
+        }
+    }
+    const int blocks = (int)std::min<size_t>(((size_t)p->N + RLB_WAVES - 1) / RLB_WAVES, std::min<size_t>(resident, RLB_MAX_BLOCKS));
+    ShadeTables t = rl_tables(p, w);
+    t.zero = a.d_envtab; t.nzero = a.d_envtab ? a.ntex3 : 0;
+    const size_t n_alb = (size_t)p->N * 12, n_rough = (size_t)p->N * 4;
+    const size_t items = std::max(std::max((size_t)t.ntexel, (size_t)t.nzero), n_alb);
+    hipLaunchKernelGGL(radiance_loss_table_kernel, dim3((unsigned)((items + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, t, d_albedos, n_alb,
+                       d_roughnesses, n_rough);
+    hipLaunchKernelGGL(radiance_loss_bwd_kernel, dim3(blocks), dim3(RLB_WAVES * 64), lds, s, a);
+    if (d_env || d_radiance_ratio)
+        hipLaunchKernelGGL(radiance_loss_env_grad_kernel, dim3(d_env ? (a.ntex3 + BLOCK - 1) / BLOCK : 1), dim3(BLOCK), 0, s, p->env,
+                           (const float*)a.d_envtab, d_env, a.ntex3, p->env_softplus, (const double*)a.ratio_part, blocks, d_radiance_ratio);
+    return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+}
 
 int svgir_pbgi_irradiance_sample(int32_t N, int32_t S, const int32_t* sample_indices, const float* ray_d, const float* envmap,
                                  const float* normals, const float* albedos, const float* roughnesses, const int32_t* hit_indices,

@@ -82,6 +82,16 @@ class SmoothTerm(C.Structure):
                 ("data_mask", C.c_void_p), ("img_mask", C.c_void_p), ("d_data", C.c_void_p), ("d_img", C.c_void_p)]
 
 
+class RadianceLossParams(C.Structure):
+    """svgir_radiance_loss_params: the inputs of svgir_radiance_loss_forward / svgir_radiance_loss_backward."""
+    _fields_ = [("N", C.c_int32), ("S", C.c_int32), ("xyz", C.c_void_p), ("camera_center", C.c_void_p), ("geo_normal", C.c_void_p),
+                ("ray_d", C.c_void_p), ("areas", C.c_void_p), ("visibility", C.c_void_p), ("normals", C.c_void_p),
+                ("albedos", C.c_void_p), ("roughnesses", C.c_void_p), ("hit_indices", C.c_void_p), ("uvs", C.c_void_p),
+                ("radiances", C.c_void_p), ("radiance_ratio", C.c_void_p), ("env", C.c_void_p), ("env_h", C.c_int32),
+                ("env_w", C.c_int32), ("env_softplus", C.c_int32), ("env_scale", C.c_float), ("env_transform", C.c_void_p),
+                ("work", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -140,6 +150,13 @@ def _load():
     # the eval view's environment backdrop (svgir_harness/render_view.py): W, H, three host arrays, env + its shape / flags, device pointers, stream
     lib.svgir_env_backdrop.restype = C.c_int
     lib.svgir_env_backdrop.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 6
+    # the fused radiance-consistency loss (pbgi/renderer.py): the parameter block, device pointers, stream
+    lib.svgir_radiance_loss_work_bytes.restype = C.c_size_t
+    lib.svgir_radiance_loss_work_bytes.argtypes = [C.c_int32] * 3
+    lib.svgir_radiance_loss_forward.restype = C.c_int
+    lib.svgir_radiance_loss_forward.argtypes = [C.POINTER(RadianceLossParams)] + [C.c_void_p] * 5
+    lib.svgir_radiance_loss_backward.restype = C.c_int
+    lib.svgir_radiance_loss_backward.argtypes = [C.POINTER(RadianceLossParams)] + [C.c_void_p] * 8
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -160,7 +177,8 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_pbgi_trace_radiance", "svgir_knn_bytes", "svgir_knn_mean_dist", "svgir_knn_topk", "svgir_pbgi_irradiance_sample",
            "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance", "svgir_geometry_loss_partials",
            "svgir_geometry_loss_forward", "svgir_geometry_loss_backward", "svgir_smooth_loss_partials", "svgir_smooth_loss_forward",
-           "svgir_smooth_loss_backward", "svgir_env_backdrop")
+           "svgir_smooth_loss_backward", "svgir_env_backdrop", "svgir_radiance_loss_work_bytes", "svgir_radiance_loss_forward",
+           "svgir_radiance_loss_backward")
 
 
 _scope = threading.local()

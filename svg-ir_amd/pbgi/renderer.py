@@ -16,13 +16,14 @@ from .bvhhelpers import GsBvh, _lib
 
 
 def _irradiance_inputs(what, N, S, hit, uvs, envmap, ray_directions, normals, albedos, roughnesses):
-    """Contiguous fp32 / int32 views of the kernels' arguments on the caches' device, shapes checked."""
+    """Contiguous fp32 / int32 views of the kernels' arguments on the caches' device, shapes checked.  (envmap None: the fused loss, which
+    has no [N,S,3] light; its slot of the result is None.)"""
     if hit is None or uvs is None:
         raise RuntimeError(f"{what}: hemi_index_buffers / uv_buffers are not set (GaussianModel.update_radiace sets them after "
                            "render_radiance_with_sampling_SH)")
     N, S = int(N), int(S)
     for t in (hit, uvs, envmap, ray_directions, normals, albedos, roughnesses):
-        if not t.is_cuda:
+        if t is not None and not t.is_cuda:
             raise RuntimeError(f"{what} needs CUDA/HIP tensors (there is no CPU path)")
     if hit.numel() != N * S or uvs.numel() != N * S * 2 or int(hit.shape[0]) != N:
         raise ValueError(f"{what}: hemi_index_buffers {tuple(hit.shape)} / uv_buffers {tuple(uvs.shape)} do not hold N = {N} rows of S = {S} samples")
@@ -33,7 +34,7 @@ def _irradiance_inputs(what, N, S, hit, uvs, envmap, ray_directions, normals, al
     hit_i = hit.detach().reshape(N, S)
     if hit_i.dtype != torch.int32:
         hit_i = hit_i.to(torch.int32)
-    return dev, (f(ray_directions, (N, S, 3)), f(envmap, (N, S, 3)), f(normals, (N, 12)), f(albedos, (N, 12)), f(roughnesses, (N, 4)),
+    return dev, (f(ray_directions, (N, S, 3)), None if envmap is None else f(envmap, (N, S, 3)), f(normals, (N, 12)), f(albedos, (N, 12)), f(roughnesses, (N, 4)),
                  hit_i.contiguous(), f(uvs, (N, S, 2)))
 
 
@@ -70,6 +71,92 @@ class _IrradianceSample(torch.autograd.Function):
                                                                      _native.ptr(d_env), _native.ptr(d_alb), _native.ptr(d_rough),
                                                                      _native.stream_ptr(dev)), "pbgi_irradiance_sample_backward")
         return (None, None, None, d_env.reshape(env_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape), None, None, None, None)
+
+
+class _RadianceConsistency(torch.autograd.Function):
+    """svgir_radiance_loss_forward / _backward: the whole radiance-consistency loss as one node.  Differentiable in env, albedos,
+    roughnesses and radiance_ratio; everything else gets None.  Returns (loss, sample_indices [N] int32, radiance [N,3], loss_sum
+    (float64 scalar)); only the loss carries a graph."""
+
+    @staticmethod
+    def forward(ctx, env, albedos, roughnesses, radiance_ratio, light, xyz, camera_center, geo_normal, ray_directions, areas, visibility,
+                normals, radiances, hit, uvs):
+        what = "radiance_consistency"
+        softplus, scale, transform = light
+        N, S = int(ray_directions.shape[0]), int(ray_directions.shape[1])
+        for t in (env, xyz, camera_center, geo_normal, areas, visibility, radiances, radiance_ratio) + (() if transform is None else (transform,)):
+            if not t.is_cuda:
+                raise RuntimeError(f"{what} needs CUDA/HIP tensors (there is no CPU path)")
+        dev, t = _irradiance_inputs(what, N, S, hit, uvs, None, ray_directions, normals, albedos, roughnesses)
+        f = lambda x, shape, name: _rows(what, _native.f32c(x.detach(), dev), shape, name)
+        e = _native.f32c(env.detach(), dev)
+        if e.dim() < 3 or e.shape[-1] != 3 or e.shape[-3] < 1 or e.shape[-2] < 1 or e.numel() != e.shape[-3] * e.shape[-2] * 3:
+            raise ValueError(f"{what}: the light's map must be ONE [He,We,3] map (leading dimensions of 1 are fine), got {tuple(env.shape)}")
+        e = e.reshape(e.shape[-3:])
+        e = e.contiguous()
+        p = _native.RadianceLossParams()
+        keep = dict(xyz=f(xyz, (N, 3), "xyz"), camera_center=f(camera_center, (3,), "camera_center"), geo_normal=f(geo_normal, (N, 3), "geo_normal"),
+                    ray_d=t[0], areas=f(areas, (N, S), "incident_areas"), visibility=f(visibility, (N, S), "visibility"), normals=t[2],
+                    albedos=t[3], roughnesses=t[4], hit_indices=t[5], uvs=t[6], radiances=f(radiances, (N, S, 3), "radiances"),
+                    radiance_ratio=f(radiance_ratio, (1,), "radiance_ratio"), env=e,
+                    env_transform=None if transform is None else f(transform, (3, 3), "the light's transform"))
+        with torch.cuda.device(dev):
+            work = torch.empty(max(_lib.svgir_radiance_loss_work_bytes(N, e.shape[0], e.shape[1]), 16), dtype=torch.uint8, device=dev)
+            keep["work"] = work
+            p.N, p.S, p.env_h, p.env_w, p.env_softplus, p.env_scale = N, S, int(e.shape[0]), int(e.shape[1]), int(bool(softplus)), float(scale)
+            for k, v in keep.items():
+                setattr(p, k, _native.ptr(v))
+            idx = _native.out_tensor((N,), torch.int32, dev)
+            R = _native.out_tensor((N, 3), torch.float32, dev)
+            total = _native.out_tensor((), torch.float64, dev)
+            loss = _native.out_tensor((), torch.float32, dev)
+            if N == 0:   # nothing is launched: the mean of no rows is NaN, as torch's
+                total.zero_()
+                loss.fill_(float("nan"))
+            _native.check(_lib.svgir_radiance_loss_forward(p, _native.ptr(idx), _native.ptr(R), total.data_ptr(), loss.data_ptr(),
+                                                           _native.stream_ptr(dev)), "radiance_loss_forward")
+        # The backward reads the inputs through the parameter block's raw pointers; `keep` holds the tensors behind them (the fp32 /
+        # contiguous copies where one was made, and the work buffer).  Unlike save_for_backward this does not notice an in-place change
+        # of an input between forward and backward: the backward then differentiates the changed values.
+        ctx.p, ctx.keep = p, keep
+        ctx.save_for_backward(idx, R)
+        ctx.shapes = (env.shape, albedos.shape, roughnesses.shape, radiance_ratio.shape)
+        ctx.mark_non_differentiable(idx, R, total)
+        return loss, idx, R, total
+
+    @staticmethod
+    def backward(ctx, g, _gi, _gr, _gt):
+        idx, R = ctx.saved_tensors
+        p, keep = ctx.p, ctx.keep
+        N = p.N
+        dev = idx.device
+        need_env, _, _, need_ratio = ctx.needs_input_grad[:4]
+        he, we = p.env_h, p.env_w
+        with torch.cuda.device(dev):
+            d_env = _native.out_tensor((he, we, 3), torch.float32, dev) if need_env else None
+            d_alb = _native.out_tensor((N, 12), torch.float32, dev)
+            d_rough = _native.out_tensor((N, 4), torch.float32, dev)
+            d_ratio = _native.out_tensor((1,), torch.float32, dev) if need_ratio else None
+            if N == 0:
+                for t in (d_env, d_ratio):
+                    if t is not None:
+                        t.zero_()
+            gdev = _native.f32c(g.detach(), dev).reshape(1).contiguous()   # the upstream scalar stays on the device
+            _native.check(_lib.svgir_radiance_loss_backward(p, _native.ptr(idx), _native.ptr(R), gdev.data_ptr(), _native.ptr(d_env),
+                                                            _native.ptr(d_alb), _native.ptr(d_rough), _native.ptr(d_ratio),
+                                                            _native.stream_ptr(dev)), "radiance_loss_backward")
+        env_shape, alb_shape, rough_shape, ratio_shape = ctx.shapes
+        return (None if d_env is None else d_env.reshape(env_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape),
+                None if d_ratio is None else d_ratio.reshape(ratio_shape)) + (None,) * 11
+
+
+def _rows(what, t, shape, name):
+    n = 1
+    for d in shape:
+        n *= d
+    if t.numel() != n or (len(shape) > 1 and t.numel() and int(t.shape[0]) != shape[0]):
+        raise ValueError(f"{what}: {name} {tuple(t.shape)} does not hold {shape}")
+    return t.reshape(shape).contiguous()
 
 
 class Renderer:
@@ -147,3 +234,18 @@ class Renderer:
         every other argument gets no gradient (None).  Reads `self.hemi_index_buffers` and `self.uv_buffers`."""
         return _IrradianceSample.apply(N, S, sample_indices, envmap, albedos, roughnesses, ray_directions, normals, self.hemi_index_buffers,
                                        self.uv_buffers)
+
+    def radiance_consistency(self, xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, env, env_softplus, env_scale,
+                             env_transform, normals, albedos, roughnesses, radiances, radiance_ratio, with_sum=False):
+        """`GaussianModel.get_radiance_loss` (scene/gaussian_model.py:544-575) as ONE autograd node (svgir_radiance_loss_forward /
+        _backward, csrc/irradiance.hip): the selection of the sample, the light `env_scale * bilinear(f(env))(incident_dirs) *
+        incident_areas` of the hit surfel (f = softplus when `env_softplus`; `env_transform` [3,3] or None rotates the lookup direction),
+        the irradiance sum of `render_irradiance_sample` and the L1 against nan_to_num(radiances * radiance_ratio).  Reads
+        `self.hemi_index_buffers` and `self.uv_buffers`.  Returns (loss, sample_indices [N] int32, radiance [N,3]) -- with_sum: and the
+        float64 sum of |radiance - target| the loss is the rounding of.  Gradients reach env (when it requires grad), albedos,
+        roughnesses and radiance_ratio; a row whose radiance or target is not finite makes the loss NaN and gets no gradient
+        (include/svgir_raster.h)."""
+        out = _RadianceConsistency.apply(env, albedos, roughnesses, radiance_ratio, (env_softplus, env_scale, env_transform), xyz,
+                                         camera_center, geo_normal, incident_dirs, incident_areas, visibility, normals, radiances,
+                                         self.hemi_index_buffers, self.uv_buffers)
+        return out if with_sum else out[:3]

@@ -1,7 +1,7 @@
 """L1 and SSIM of a rendered image against the ground truth, fused (csrc/loss.hip): the reference's
 `F.l1_loss(image, gt)` + `ssim(image, gt)` (gaussian_renderer/svgss.py:281-289, render.py:150-151;
 utils/loss_utils.py:21-64), one kernel forward, one backward; and the radiance-consistency loss of stage 2 (`radiance_loss`: scene/gaussian_model.py:544-575)
-around the irradiance kernel of csrc/irradiance.hip; and the geometry terms of both stages (`cos_loss`, `surface_loss`, `mask_loss`,
+around the irradiance kernel of csrc/irradiance.hip, and the same loss fused end to end (`fused_radiance_loss`); and the geometry terms of both stages (`cos_loss`, `surface_loss`, `mask_loss`,
 `mask_entropy_loss`, `geometry_losses`: gaussian_renderer/render.py:157-188, svgss.py:297-313, 333-338), fused in csrc/geom_loss.hip; and the
 edge-aware smoothness and TV terms (`first_order_edge_aware_loss`, `second_order_edge_aware_loss`, `tv_loss`, `smoothness_losses`:
 utils/loss_utils.py:101-117; svgss.py:366-399, render.py:192-196), fused in csrc/smooth_loss.hip."""
@@ -151,6 +151,23 @@ def radiance_loss(renderer, xyz, camera_center, geo_normal, incident_dirs, visib
     target = torch.nan_to_num(radiances.detach() * radiance_ratio, nan=0.0)
     target = target.gather(1, max_idx.long().unsqueeze(-1).expand(-1, -1, 3)).squeeze(-2)
     return torch.nn.functional.l1_loss(radiance, target)
+
+
+def fused_radiance_loss(renderer, xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, light, normals12, albedos,
+                        roughnesses, radiances, radiance_ratio, with_rows=False):
+    """`GaussianModel.get_radiance_loss` (scene/gaussian_model.py:544-575) as one fused forward and one fused backward
+    (`Renderer.radiance_consistency`, csrc/irradiance.hip): what `radiance_loss` computes when it is fed
+    envmap = light.direct_light(incident_dirs) * incident_areas, without that [N,S,3] tensor, its gradient, or any [N,S] temporary of the
+    selection.  `light` is the reference's DirectLightMap (.env) or EnvLight (.envmap [, .transform]), as for the shading
+    (gaussian_renderer.shading._env_of); visibility and incident_areas are [N,S,1] or [N,S].  Gradients reach light.env (when it requires
+    grad), albedos, roughnesses and radiance_ratio.  with_rows=True returns (loss, sample_indices [N] int32, radiance [N,3]).
+    A row whose radiance or target is not finite makes the loss NaN, as in torch, but contributes to no gradient
+    (include/svgir_raster.h)."""
+    from gaussian_renderer import shading
+    env, softplus, scale, transform = shading._env_of(light)
+    out = renderer.radiance_consistency(xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, env, softplus, scale,
+                                        transform, normals12, albedos, roughnesses, radiances, radiance_ratio)
+    return out if with_rows else out[0]
 
 
 # ---- geometry terms (csrc/geom_loss.hip) ------------------------------------------------------------------------------------------

@@ -1,0 +1,573 @@
+"""The case table of the fused radiance-consistency loss (svg-ir_amd/csrc/irradiance.hip: svgir_radiance_loss_forward / _backward behind
+`pbgi.Renderer.radiance_consistency` and `svgir_harness.losses.fused_radiance_loss`) and its fp64 oracle: one table for
+tests/test_radiance_loss_edge_inputs.py (CPU: the oracle is pinned and every case holds what it is named for) and
+tests/test_gpu_radiance_loss.py (the kernels).
+
+The oracle is composed from what exists:
+    envmap  = shading_oracle.env_lookup(env, dirs, softplus, scale) * areas                (fp64; dirs through `transform` first)
+    loss    = the construction of radiance_cases.loss_oracle: selection (with its margin), radiance_cases.oracle_of under that selection,
+              target, L1, the sign as the kernel's upstream gradient, d_ratio
+    d_env   = d_envmap * areas pushed back through the lookup's adjoint (np.add.at over the four taps, times scale and f'(env))
+and adds the one rule of the contract that torch does not have: an ELEMENT [i,c] whose R or T is not finite makes the loss NaN and gives
+no gradient -- its upstream is 0 and the non-finite light values behind it are taken as 0 (kernel_case(clean=True)); the other elements
+of its row contribute as usual; an element of d_env that receives nothing but zeros is 0 whatever env holds there.
+
+Next to it the reference's operation order in torch fp32 on the CPU -- `direct_light`'s lines (shading_oracle.env_lookup is those lines with
+grid_sample spelled out), the selection's lines and l1_loss -- from which the two constants of the tolerances are measured:
+    E_SEL  the largest |score32 - score64| of a case (finite scores): a row whose fp64 best-minus-runner-up margin is below 4 E_SEL, without
+           being an exact tie, is a THRESHOLD row: fp32 may choose either; the GPU test holds it to the margin instead of the index.
+    E_ENV  the largest |light32 - light64| / (scale * sum_j |w_j f(env)_j|) of a case: the relative deviation of one looked-up light value.
+           It enlarges E_TERM of radiance_cases.bound: a term is (brdf term) * light.
+The constants below cover every case (test_radiance_loss_edge_inputs.py measures them again).
+
+`case(name)`, `oracle(name)` cache per process; the arrays are read-only."""
+import functools
+import math
+
+import numpy as np
+import torch
+
+from oracle import shading_oracle as so
+from tests import radiance_cases as rc
+
+F32, F64 = np.float32, np.float64
+WAVE = 64                 # csrc/irradiance.hip IRR_WAVE: samples per pass
+ROWS = 4                  # csrc/irradiance.hip IRR_WAVES: rows per forward workgroup
+BWD_ROWS = 8              # csrc/irradiance.hip RLB_WAVES: rows per pass of a backward workgroup
+LDS_BYTES = 160 * 1024    # csrc/irradiance.hip RL_LDS_BYTES
+LDS_TEXELS = (LDS_BYTES - BWD_ROWS * 8) // 24   # svgir_radiance_loss_backward: RLB_WAVES * 8 + texels * 3 * 8 <= RL_LDS_BYTES -> 6824
+# Measured 2026-10-18 over the whole table (test_the_measured_constants_cover_every_case prints them): E_SEL 7.2e-7 (`contention`; scores up to
+# 3: |r| <= 3, |d| = 1), E_ENV 5.3e-5 (`physical`, 32 000 lookups into a 32 x 64 map of unit-variance noise: a grid coordinate carries ~We eps32
+# texels of error, times the contrast of neighbouring texels; 1e-5 - 3e-5 in the small cases).
+E_SEL = 1.0e-6
+E_ENV = 6.0e-5
+
+CASES = {}
+
+
+# ---- the lookup: taps, value, adjoint ----------------------------------------------------------------------------------------------------
+def lookup_dirs(c, T=F64):
+    d = c["ray_d"].astype(T)
+    return d if c["transform"] is None else d @ c["transform"].astype(T).T
+
+
+def taps(dirs, He, We):
+    """fp64 taps of direct_light's grid (align_corners, zero padding): idx [n,4] (texel, clamped), w [n,4], ok [n,4]; tap j = (dx = j & 1,
+    dy = j >> 1) as csrc/env_lookup.hpp."""
+    d = np.asarray(dirs, F64).reshape(-1, 3)
+    with np.errstate(invalid="ignore"):
+        phi = np.arccos(d[:, 2]) - 1e-6
+        theta = np.arctan2(d[:, 1], d[:, 0])
+        x = ((-theta / math.pi) + 1) * 0.5 * (We - 1)
+        y = ((phi / math.pi * 2 - 1) + 1) * 0.5 * (He - 1)
+        x0, y0 = np.floor(x), np.floor(y)
+        fx, fy = x - x0, y - y0
+        idx, w, ok = [], [], []
+        for j in range(4):
+            xi, yi = x0 + (j & 1), y0 + (j >> 1)
+            good = (xi >= 0) & (xi < We) & (yi >= 0) & (yi < He)
+            ok.append(good)
+            idx.append(np.where(good, yi * We + xi, 0))
+            w.append((fx if j & 1 else 1 - fx) * (fy if j >> 1 else 1 - fy))
+    return np.stack(idx, 1).astype(np.int64), np.stack(w, 1), np.stack(ok, 1)
+
+
+def f_env(c, T=F64):
+    e = c["env"].astype(T)
+    return np.where(e > 20, e, np.logaddexp(0, np.minimum(e, 20))) if c["softplus"] else e
+
+
+def df_env(c):
+    e = c["env"].astype(F64)
+    with np.errstate(over="ignore"):
+        return np.where(e > 20, 1.0, 1 / (1 + np.exp(-e))) if c["softplus"] else np.ones_like(e)
+
+
+def light64(c):
+    """(light [N,S,3] = scale * bilinear(f(env)) at the case's lookup directions, its magnitude scale * sum_j |w_j f_j|)"""
+    He, We = c["env"].shape[:2]
+    idx, w, ok = taps(lookup_dirs(c), He, We)
+    f = f_env(c).reshape(-1, 3)
+    with np.errstate(invalid="ignore"):
+        t = np.where(ok[..., None], w[..., None] * f[idx], 0.0)      # [n,4,3]
+    shape = c["ray_d"].shape
+    return (t.sum(1) * c["scale"]).reshape(shape), (np.abs(t).sum(1) * c["scale"]).reshape(shape)
+
+
+def lookup_adjoint(c, d_light):
+    """d_light [N,S,3] (any number of stacked arrays) -> d_env [He,We,3]: the adjoint of light64 in env, f' included"""
+    He, We = c["env"].shape[:2]
+    idx, w, ok = taps(lookup_dirs(c), He, We)
+    out = np.zeros((He * We, 3))
+    for j in range(4):
+        m = ok[:, j]
+        np.add.at(out, idx[m, j], (w[m, j, None] * c["scale"]) * d_light.reshape(-1, 3)[m])
+    return out.reshape(He, We, 3)
+
+
+def composed_adjoint_slack(c, d_light_abs):
+    """What the fp32 lookup of the reference adds to an element of d_env when the light is composed in torch (the path the fused loss
+    replaces): a bilinear weight is 1-Lipschitz in each grid coordinate, so a tap's weight is off by at most |x32 - x64| + |y32 - y64|
+    =: E_W (the largest over the case's lookups, direct_light's lines in torch fp32 on the CPU against fp64), ABSOLUTELY -- whatever the
+    weight.  Returns E_W * (the sum of |d_light| * scale over every sample that has the texel among its four taps) * f'."""
+    He, We = c["env"].shape[:2]
+
+    def xy(dtype):
+        d = torch.from_numpy(np.ascontiguousarray(c["ray_d"]).copy()).to(dtype).reshape(-1, 3)
+        if c["transform"] is not None:
+            d = d @ torch.from_numpy(np.ascontiguousarray(c["transform"]).copy()).to(dtype).T
+        phi = torch.arccos(d[:, 2]) - 1e-6
+        theta = torch.atan2(d[:, 1], d[:, 0])
+        return ((-theta / math.pi + 1) * 0.5 * (We - 1)).double().numpy(), (((phi / math.pi) * 2 - 1 + 1) * 0.5 * (He - 1)).double().numpy()
+    (x32, y32), (x64, y64) = xy(torch.float32), xy(torch.float64)
+    e_w = float(np.nanmax(np.abs(x32 - x64) + np.abs(y32 - y64)))
+    idx, w, ok = taps(lookup_dirs(c), He, We)
+    out = np.zeros((He * We, 3))
+    flat = np.asarray(d_light_abs, F64).reshape(-1, 3) * c["scale"]
+    for j in range(4):
+        m = ok[:, j]
+        np.add.at(out, idx[m, j], flat[m])
+    return e_w * out.reshape(He, We, 3) * df_env(c), e_w
+
+
+def light32_torch(c):
+    """the reference's lines in torch fp32 on the CPU: dirs @ transform.T, direct_light (shading_oracle.env_lookup)"""
+    d = torch.from_numpy(np.ascontiguousarray(c["ray_d"]))
+    if c["transform"] is not None:
+        d = d.reshape(-1, 3) @ torch.from_numpy(np.ascontiguousarray(c["transform"])).T
+    return so.env_lookup(torch.from_numpy(np.ascontiguousarray(c["env"])), d.reshape(c["ray_d"].shape), softplus=c["softplus"],
+                         scale=c["scale"]).numpy()
+
+
+def scores_torch(c, dtype):
+    """the selection's lines of get_radiance_loss (scene/gaussian_model.py:555-564) in torch on the CPU"""
+    t = lambda k: torch.from_numpy(np.ascontiguousarray(c[k])).to(dtype)
+    view_dirs = torch.nn.functional.normalize(t("xyz") - t("camera_center"), dim=-1)
+    geo_normal = t("geo_normal")
+    view_reflect = 2 * torch.sum(geo_normal * view_dirs, dim=-1, keepdim=True) * geo_normal + view_dirs
+    n_d_i = torch.sum(t("ray_d") * view_reflect[:, None], dim=-1)
+    return n_d_i * (1 - t("visibility"))
+
+
+def selection(c):
+    """(sel [N], margin [N], score [N,S]) in fp64: torch.argmax's index (the first NaN, else the first maximum); margin = best minus runner-up
+    (0: an exact tie; inf: S = 1 or a NaN row, where nothing is close)"""
+    score = scores_torch(c, torch.float64).numpy()
+    sel = score.argmax(-1)                       # (numpy's argmax treats NaN as torch does)
+    N, S = score.shape
+    margin = np.full(N, np.inf)
+    if S > 1:
+        srt = np.sort(score, -1)                 # NaN sorts last
+        m = srt[:, -1] - srt[:, -2]
+        margin = np.where(np.isnan(m), np.inf, m)
+    return sel, margin, score
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------------------
+def _unit(v):
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def smooth_env(He, We, seed):
+    """a map without texel-to-texel contrast (wide maps: the lookup's fp32 coordinate error is ~We eps32 texels)"""
+    rng = np.random.default_rng(seed)
+    y, x = np.meshgrid(np.linspace(0, 1, He), np.linspace(0, 1, We), indexing="ij")
+    ph = rng.uniform(0, 6.28, size=(3, 2))
+    return np.stack([0.3 + 0.8 * np.sin(3 * x + ph[k, 0]) * np.cos(2 * y + ph[k, 1]) for k in range(3)], -1)
+
+
+def _base(N, S, seed, He=32, We=64, p_free=0.4, smooth=False):
+    """radiance_cases._random (two populations, so no half vector comes near zero) with UNIT directions -- the light is looked up along the
+    raw direction, as in the reference, whose incident directions are unit vectors -- and what the loss needs on top."""
+    c = rc._random(N, S, seed, p_free=p_free)
+    rng = np.random.default_rng(seed + 77777)
+    d = _unit(c["ray_d"]).astype(F32)
+    d[..., 2] = np.clip(d[..., 2], -1.0, 1.0)
+    c.pop("envmap"), c.pop("sample"), c.pop("grad_out")
+    c.update(ray_d=d, xyz=rng.normal(size=(N, 3)), camera_center=np.array([0.3, -2.5, 0.4]), geo_normal=_unit(rng.normal(size=(N, 3))),
+             visibility=np.where(rng.uniform(size=(N, S)) < 0.3, 0.0, rng.uniform(0.0, 1.0, size=(N, S))),
+             areas=rng.uniform(0.5, 1.5, size=(N, S)) * (2 * math.pi / S), radiances=rng.uniform(0.0, 1.5, size=(N, S, 3)),
+             radiance_ratio=np.array(1.25), env=smooth_env(He, We, seed) if smooth else rng.normal(size=(He, We, 3)), softplus=True,
+             scale=2.0, transform=None)
+    return c
+
+
+def _f32(c):
+    for k in ("xyz", "camera_center", "geo_normal", "visibility", "areas", "radiances", "radiance_ratio", "env", "ray_d", "normals", "albedos",
+              "roughnesses", "uvs", "transform"):
+        if c.get(k) is not None:
+            c[k] = np.ascontiguousarray(c[k], dtype=F32)
+    c["hit"] = np.ascontiguousarray(c["hit"], dtype=np.int32)
+    return c
+
+
+def _aim(c, i, t):
+    """makes sample t the strict maximum of row i: v is set perpendicular to the geometric normal and along d[i,t], so r = v = d[i,t]
+    and score_t = 1 with the sample fully occluded; every other score is (1 - vis) cos < 1."""
+    d = c["ray_d"][i, t].astype(F64)
+    a = np.cross(d, [1.0, 0.0, 0.0] if abs(d[0]) < 0.9 else [0.0, 1.0, 0.0])
+    c["geo_normal"][i] = _unit(a)
+    c["xyz"][i] = c["camera_center"] + 2.0 * d
+    c["visibility"][i, t] = 0.0
+
+
+def _register(fn):
+    CASES[fn.__name__] = fn
+    return fn
+
+
+for _S in (63, 64, 65, 129, 300):
+    CASES["random_5x%d" % _S] = functools.partial(_base, 5, _S, 500 + _S)      # N = 5: one row past a forward workgroup's 4
+CASES["random_9x65"] = functools.partial(_base, 9, 65, 965)                    # one row past a backward pass of 8
+CASES["random_70x64"] = functools.partial(_base, 70, 64, 7064)
+
+
+@_register
+def self_hit_1x1():
+    c = _base(1, 1, 1)
+    c["hit"][:] = 0
+    return c
+
+
+@_register
+def max_positions():
+    """S = 129: the maximum at lane 63 (row 0), at index 64 (row 1, the first sample of the second pass) and at S - 1 (row 2, the only
+    sample of the third pass); rows 3 and 4 as they fall"""
+    c = _base(5, 129, 11)
+    for i, t in ((0, 63), (1, 64), (2, 128)):
+        _aim(c, i, t)
+    return c
+
+
+@_register
+def tie_3_70():
+    """rows 0-2: samples 3 and 70 are the same direction with the same visibility and hold the maximum: an exact tie in any precision,
+    across the passes; 3 must win"""
+    c = _base(5, 129, 12)
+    for i in range(3):
+        _aim(c, i, 3)
+        c["ray_d"][i, 70] = c["ray_d"][i, 3]
+        c["visibility"][i, 70] = c["visibility"][i, 3]
+    return c
+
+
+@_register
+def all_visible():
+    """visibility 1 everywhere: every score is +0 or -0, which tie: index 0"""
+    c = _base(5, 65, 13)
+    c["visibility"][:] = 1.0
+    return c
+
+
+@_register
+def all_negative():
+    """r = v = -(the pole of the row's population), perpendicular to the geometric normal: every score is -|d.z| (1 - vis) < 0"""
+    c = _base(6, 65, 14)
+    sign = np.where(np.arange(6) & 1, -1.0, 1.0)
+    c["geo_normal"][:] = [1.0, 0.0, 0.0]
+    c["xyz"] = c["camera_center"] + np.stack([np.zeros(6), np.zeros(6), -2.0 * sign], -1)
+    c["visibility"] = np.clip(c["visibility"], 0.0, 0.9)
+    return c
+
+
+@_register
+def at_camera():
+    """rows 0 and 3 sit at the camera centre: a zero view vector (0 / 1e-12), r = 0, scores +-0: index 0"""
+    c = _base(5, 65, 15)
+    c["xyz"][0] = c["camera_center"]
+    c["xyz"][3] = c["camera_center"]
+    return c
+
+
+@_register
+def nan_scores():
+    """row 0: one NaN score (index 17, through its visibility); row 1: two (40 and 100: the first wins, across the passes), next to an
+    aimed finite maximum at index 5"""
+    c = _base(5, 129, 16)
+    c["visibility"][0, 17] = np.nan
+    _aim(c, 1, 5)
+    c["visibility"][1, 40] = np.nan
+    c["visibility"][1, 100] = np.nan
+    return c
+
+
+@_register
+def dyadic():
+    """inputs for which every fp32 operation of the selection is exact: v along an axis (|xyz - c| = 2), axis-aligned normals, directions
+    in eighths (|d.z| <= 1; not unit: the brdf normalises), visibility in quarters"""
+    N, S = 6, 65
+    c = _base(N, S, 17)
+    rng = np.random.default_rng(1717)
+    sign = np.where(np.arange(N) & 1, -1.0, 1.0)
+    d = rng.integers(-8, 9, size=(N, S, 3)) / 8.0
+    d[..., 2] = rng.integers(1, 9, size=(N, S)) / 8.0 * sign[:, None]      # (the populations' half spaces, |z| >= 1/8)
+    c["ray_d"] = d
+    c["camera_center"] = np.array([0.5, -2.0, 0.25])
+    ax = np.eye(3)[np.arange(N) % 3]
+    c["xyz"] = c["camera_center"] + 2.0 * ax * np.where(np.arange(N) % 2, -1.0, 1.0)[:, None]
+    c["geo_normal"] = np.eye(3)[(np.arange(N) + (np.arange(N) // 3)) % 3]
+    c["visibility"] = rng.integers(0, 4, size=(N, S)) / 4.0
+    return c
+
+
+def _map_case(He, We, seed, smooth=False, N=20, S=64):
+    return functools.partial(_base, N, S, seed, He, We, 0.4, smooth)
+
+
+CASES["map_1x2"] = _map_case(1, 2, 21)
+CASES["map_2x4"] = _map_case(2, 4, 22)
+CASES["map_32x64"] = _map_case(32, 64, 23)                       # the LDS table
+CASES["map_lds_last"] = _map_case(8, 853, 24, smooth=True)       # 6 824 texels: the largest map that fits the LDS rule
+CASES["map_lds_first_global"] = _map_case(5, 1365, 25, smooth=True)   # 6 825 texels: the first that does not
+CASES["map_128x256"] = _map_case(128, 256, 26, smooth=True)      # global atomics: the reference's default size
+
+
+@_register
+def poles_and_seam():
+    """surfel 1's escaped samples look at the south pole (0,0,-1), surfel 0's at the north pole (0,0,1: phi = -1e-6, the taps of row -1
+    lie outside the map) and both along the seam: theta = +pi (x = 0) and theta = -pi (x = We - 1: the tap at We lies outside)"""
+    c = _base(20, 64, 27)
+    for h, z in ((0, 1.0), (1, -1.0)):
+        c["ray_d"][h, 0] = [0.0, 0.0, z]
+        c["ray_d"][h, 1] = [-1.0, 0.0, 0.0]
+        c["ray_d"][h, 2] = [-1.0, -0.0, 0.0]
+        c["hit"][h, 0:3] = -1
+    return c
+
+
+@_register
+def envlight():
+    """EnvLight: f = identity, scale 1, the 32 x 64 map (already at the resample's size, so that the resample is the identity)"""
+    c = _base(20, 64, 28)
+    c.update(env=np.random.default_rng(2828).uniform(0.0, 3.0, size=(32, 64, 3)), softplus=False, scale=1.0)
+    return c
+
+
+@_register
+def envlight_transform():
+    c = envlight()
+    a, b = 0.7, 0.4
+    rz = np.array([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1]])
+    rx = np.array([[1, 0, 0], [0, math.cos(b), -math.sin(b)], [0, math.sin(b), math.cos(b)]])
+    c["transform"] = rz @ rx
+    return c
+
+
+@_register
+def flat_map():
+    c = _base(20, 64, 29)
+    c["env"][:] = 0.25
+    return c
+
+
+@_register
+def softplus_linear():
+    """env beyond softplus's switch to the identity (x > 20) in the whole red channel (f = x, f' = 1 there; a whole channel, so that
+    the map gains no texel-to-texel contrast of 24, which only the lookup's coordinate error would feel)"""
+    c = _base(20, 64, 30)
+    c["env"][..., 0] += 24.0
+    return c
+
+
+@_register
+def contention():
+    """300 rows that all hit surfel 0, whose samples all escape"""
+    c = _base(300, 64, 31)
+    c["hit"][:] = 0
+    c["hit"][0, :] = -1
+    return c
+
+
+@_register
+def all_primaries_miss():
+    c = _base(20, 64, 32)
+    c["hit"][:] = -1
+    return c
+
+
+@_register
+def hits_out_of_range():
+    """the chosen primaries of rows 0-3 hit -2, N, N + 5 and -100 (misses); row 4's hit surfel has secondaries -2 and N (occluded)"""
+    c = _f32(_base(20, 64, 33))
+    sel = selection(c)[0]
+    for i, h in ((0, -2), (1, 20), (2, 25), (3, -100)):
+        c["hit"][i, sel[i]] = h
+    c["hit"][4, sel[4]] = 5
+    c["hit"][5, :] = -1
+    c["hit"][5, 0::4] = -2
+    c["hit"][5, 1::4] = 20
+    return c
+
+
+@_register
+def non_finite():
+    """row 0 hits surfel 1, one of whose escaped samples looks at a NaN texel (all three channels): R[0] is NaN, and so is R of every other
+    row that sums such a sample; row 2's target is +inf.  The loss is NaN; those rows give no gradient."""
+    c = _f32(_base(40, 64, 34))
+    sel = selection(c)[0]
+    c["hit"][0, sel[0]] = 1
+    c["hit"][1, 7] = -1
+    idx, w, ok = taps(lookup_dirs(c)[1, 7], 32, 64)
+    j = int(np.argmax(np.where(ok[0], w[0], -1)))
+    c["env"].reshape(-1, 3)[idx[0, j]] = np.nan
+    c["radiances"][2, sel[2]] = np.inf
+    return c
+
+
+@_register
+def non_finite_channels():
+    """the rule per ELEMENT: row 0 hits surfel 1, one of whose escaped samples looks at a texel that is NaN in the green channel only;
+    row 2 hits surfel 3, one of whose samples looks at a texel that is +inf in the blue channel only (texels none of the other two surfels
+    looks at); row 4 (which hits surfel 7) has
+    T = +inf in the red channel only.  Those elements are non-finite; the other channels of the same rows keep their gradients."""
+    c = _f32(_base(40, 64, 37))
+    sel = selection(c)[0]
+    c["hit"][4, sel[4]] = 7
+    d = lookup_dirs(c)
+
+    def texels(h):      # every texel an escaped sample of surfel h has among its taps
+        idx, w, ok = taps(d[h][c["hit"][h] == -1], 32, 64)
+        return set(idx[ok].tolist())
+    for i, h, ch, v in ((0, 1, 1, np.nan), (2, 3, 2, np.inf)):
+        c["hit"][i, sel[i]] = h
+        others = set().union(*(texels(o) for o in (1, 3, 7) if o != h))
+        for s in np.flatnonzero(c["hit"][h] == -1):      # a sample whose strongest tap no other of the three surfels looks at
+            idx, w, ok = taps(d[h, s], 32, 64)
+            t = int(idx[0, int(np.argmax(np.where(ok[0], w[0], -1)))])
+            if t not in others:
+                break
+        c["env"].reshape(-1, 3)[t, ch] = v
+    c["radiances"][4, sel[4], 0] = np.inf
+    return c
+
+
+@_register
+def ratio_zero():
+    c = _base(20, 64, 35)
+    c["radiance_ratio"] = np.array(0.0)
+    return c
+
+
+@_register
+def physical():
+    """the 2 000 x 16 case of radiance_cases (the traced scene of tests/pbgi_scene.py) with the areas of the Fibonacci lattice (2 pi) and
+    a learnable 32 x 64 map"""
+    p = rc.case("physical")
+    c = {k: np.array(p[k]) for k in ("ray_d", "normals", "albedos", "roughnesses", "hit", "uvs", "xyz", "camera_center", "geo_normal", "radiances",
+                                     "radiance_ratio")}
+    c.update(N=p["N"], S=p["S"], visibility=np.array(p["visibility"]).reshape(p["N"], p["S"]), areas=np.full((p["N"], p["S"]), 2 * math.pi),
+             env=np.random.default_rng(36).normal(size=(32, 64, 3)), softplus=True, scale=2.0, transform=None)
+    c["ray_d"][..., 2] = np.clip(c["ray_d"][..., 2], -1.0, 1.0)
+    return c
+
+
+SELECTION_CASES = ("max_positions", "tie_3_70", "all_visible", "all_negative", "at_camera", "nan_scores", "dyadic")
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    c = _f32(CASES[name]())
+    for v in c.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return c
+
+
+# ---- the oracle -----------------------------------------------------------------------------------------------------------------------
+def bound(kind, cnt, abs_sum):
+    """radiance_cases.bound with E_TERM enlarged by E_ENV: (contributions * 2^-24 + 4 (E_TERM[kind] + E_ENV)) * sum |t|"""
+    return (cnt * 2.0 ** -24 + 4.0 * (rc.E_TERM[kind] + E_ENV)) * abs_sum
+
+
+def kernel_case(c, sel, grad_out=None, clean=False):
+    """the case in the form radiance_cases.oracle_of takes, under the selection `sel`.  clean: a non-finite light value is replaced by 0 --
+    every row that sums it is non-finite in that channel and has no upstream there, so the value reaches no gradient (the contract's
+    per-element rule); only 0 * NaN would."""
+    light, _ = light64(c)
+    N = c["N"]
+    envmap = light * c["areas"].astype(F64)[..., None]
+    if clean:
+        envmap = np.where(np.isfinite(envmap), envmap, 0.0)
+    return dict(c, sample=np.asarray(sel, np.int32), envmap=envmap, grad_out=np.zeros((N, 3)) if grad_out is None else grad_out)
+
+
+def oracle_at(c, sel):
+    """fp64 reference of the fused loss under the selection `sel` [N] (the oracle's own, or the kernel's on threshold rows):
+    out / out_abs [N,3], target, bad [N,3] (R or T not finite), loss (NaN when anything is bad), loss_sum / loss_sum_bound over the
+    finite elements, d_albedos, d_roughnesses (+ _abs, _cnt, thr) from radiance_cases.oracle_of, d_env (+ _abs, _cnt), d_ratio (+ _abs),
+    and `unsafe` [N] / `unsafe_env` [He,We,3] / unsafe_ratio_abs: what is fed by rows whose |R - T| lies within 10 bounds of zero (the
+    L1's sign depends on rounding there: finiteness only)."""
+    N, S = c["N"], c["S"]
+    rows = np.arange(N)
+    sel = np.asarray(sel, np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        k1 = rc.oracle_of(kernel_case(c, sel))
+        out, out_abs = k1["out"], k1["out_abs"]
+        raw = c["radiances"].astype(F64)[rows, sel]
+        prod = raw * float(c["radiance_ratio"].reshape(-1)[0])
+        target = np.where(np.isnan(prod), 0.0, prod)
+        bad = ~np.isfinite(out) | ~np.isfinite(target)
+        gap = np.abs(out - target)
+        sign = np.where(bad, 0.0, np.sign(out - target))
+    g = sign / (3 * N)          # (0 in every non-finite element: the element gives no gradient, its row's other elements do)
+    dead = bad.all(1)
+    k2 = rc.oracle_of(kernel_case(c, sel, g, clean=True))
+    row_bound = bound("out", S, out_abs)
+    hit_of = np.full(N, -1)
+    hit_of[k2["rows"]] = k2["hits"]
+    risky = (~bad & (gap <= 10 * row_bound) & (out_abs > 0)).any(1)
+    unsafe = np.zeros(N, bool)
+    unsafe[hit_of[risky & (hit_of >= 0)]] = True
+    areas = c["areas"].astype(F64)[..., None]
+    with np.errstate(invalid="ignore"):
+        d_tab, d_tab_abs = lookup_adjoint(c, k2["d_envmap"] * areas), lookup_adjoint(c, k2["d_envmap_abs"] * areas)
+        # (an element nothing but zeros was added to is 0 whatever env holds there -- f' of a NaN texel does not reach it)
+        d_env = np.where(d_tab_abs > 0, d_tab * df_env(c), 0.0)
+        d_env_abs = np.where(d_tab_abs > 0, d_tab_abs * df_env(c), 0.0)
+    cnt = _tap_count(c, k2["d_envmap_cnt"])
+    unsafe_env = _tap_count(c, np.repeat(unsafe[:, None, None], S, 1) * k2["d_envmap_cnt"]) > 0
+    fin = np.isfinite(prod) & ~bad
+    t_ratio = np.where(fin, -g * np.where(fin, raw, 0.0), 0.0)
+    ok = ~bad
+    return rc._readonly(dict(
+        sel=sel, out=out, out_abs=out_abs, target=target, bad=bad, dead=dead, gap=gap,
+        loss=float("nan") if bad.any() else gap.sum() / (3 * N), loss_sum=gap[ok].sum(),
+        # (each |R - T| is an fp32 difference of R and the fp32 product T: one rounding of T, one of the difference)
+        loss_sum_bound=row_bound[ok].sum() + 2.0 ** -23 * (np.abs(out[ok]).sum() + np.abs(target[ok]).sum()),
+        kernel=k2, d_env=d_env, d_env_abs=d_env_abs, d_env_cnt=cnt, d_ratio=t_ratio.sum(), d_ratio_abs=np.abs(t_ratio).sum(),
+        unsafe=unsafe, unsafe_env=unsafe_env, unsafe_ratio_abs=np.abs(t_ratio)[risky].sum()))
+
+
+def _tap_count(c, cnt_envmap):
+    """number of contributions per element of d_env: every contributing (h, s, c) adds to its in-range taps"""
+    He, We = c["env"].shape[:2]
+    idx, w, ok = taps(lookup_dirs(c), He, We)
+    out = np.zeros((He * We, 3))
+    flat = np.asarray(cnt_envmap, F64).reshape(-1, 3)
+    for j in range(4):
+        m = ok[:, j]
+        np.add.at(out, idx[m, j], flat[m])
+    return out.reshape(He, We, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle(name):
+    """oracle_at under the fp64 selection, with the selection's `margin`, `score` and `threshold` rows"""
+    c = case(name)
+    sel, margin, score = selection(c)
+    o = dict(oracle_at(c, sel))
+    o.update(margin=margin, score=score, threshold=(margin > 0) & (margin < 4 * E_SEL))
+    return rc._readonly(o)
+
+
+def measure(name):
+    """(E_SEL, E_ENV) of one case, from the reference's fp32 lines on the CPU"""
+    c = case(name)
+    s32, s64 = scores_torch(c, torch.float32).numpy().astype(F64), scores_torch(c, torch.float64).numpy()
+    ok = np.isfinite(s32) & np.isfinite(s64)
+    e_sel = float(np.abs(s32 - s64)[ok].max()) if ok.any() else 0.0
+    l64, mag = light64(c)
+    l32 = light32_torch(c).astype(F64)
+    ok = np.isfinite(l32) & np.isfinite(l64) & (mag > 0)
+    e_env = float((np.abs(l32 - l64)[ok] / mag[ok]).max()) if ok.any() else 0.0
+    return e_sel, e_env
