@@ -778,7 +778,7 @@ int svgir_split_transform(int64_t n_new, int32_t N, const float* z, float* xyz_n
 /* Per-stage GPU timing.  While enabled, forward/backward record HIP events on the launch stream at every stage
  * boundary (no extra synchronisation); svgir_last_timings() waits for the recorded events and returns, per stage,
  * the AVERAGE duration in milliseconds and the number of samples since profiling was (re-)enabled.
- * Stage names: "preprocess","sort_depth","scan","emit","sort_tile","ranges","render","image",
+ * Stage names: "preprocess","sort_depth","emit","sort_tile","ranges","render","image",
  *              "render_bwd","geom_bwd".  Returns the number of entries written (<= cap); `counts` may be NULL. */
 void svgir_set_profiling(int enabled);
 int svgir_last_timings(const char** names, float* avg_ms, int* counts, int cap);

@@ -516,7 +516,7 @@ struct ForwardCall {
         return e != hipSuccess ? fail(SVGIR_ERR_HIP, p->debug ? "%s failed: %s" : "%s launch failed: %s", what, hipGetErrorString(e)) : 0;
     }
 
-    // Everything behind the offsets scan depends on the instance count R that the GPU is still computing.  The stages are launched for an
+    // Everything behind the depth sort depends on the instance count R that the GPU is still computing.  The stages are launched for an
     // instance CAPACITY `cap` and read R on the device (min(cap, R)); the binning blob is laid out for `cap`.  `timed`: stage marks are
     // only recorded for the launch sequence that counts.
     int run_binning_and_render(char* bblob, int cap, long long cap_slots, bool timed, bool cull_only = false) {
@@ -646,7 +646,7 @@ struct ForwardCall {
         // pass of the composite (the alpha / transmittance chain of the very same arithmetic: no channels, no outputs) first finds the surfels
         // that actually receive a blend weight -- 29 % at cfg3, 13 % at cfg5 -- for ~40 % of the full composite's time.  Otherwise the
         // working set is every surfel that touches a tile (44 % on the BASELINE scenes: the preprocess culls), which costs nothing to find:
-        // the depth order holds them in front, and the offsets scan reports where they end.
+        // the depth order holds them in front, and the depth sort's last pass reports where they end.
         prepass = shade_subset && shade_prepass(p->shade->sp.Ns);
         pa.needed = prepass ? G.needed : nullptr;
         pa.span = G.counters + 3;
@@ -668,14 +668,11 @@ struct ForwardCall {
         // depth sort of the P Gaussians: 4 x 8-bit stable passes (ends in slot 0), or 3 when the top byte is speculated to be common (slot 1)
         const int depth_bits = spec_top >= 0 ? 24 : 32;
         depth_order = G.idx[(depth_bits / 8) & 1];
-        launch_radix_sort(G.key, G.idx, P, nullptr, depth_bits, 8, G.radix_tbl, s);
+        // (its last pass sums the tile counts next to the keys: G.offsets, the instance count R and what the host reads with it -- no scan stage)
+        const RadixWeights rw{G.tiles, G.radix_wtbl, G.offsets, G.counters, G.key_top, (P + 63) / 64, pa.prefilter_violation, R_pin.at, R_pin.tag};
+        launch_radix_sort(G.key, G.idx, P, nullptr, depth_bits, 8, G.radix_tbl, s, &rw);
         if (int rc = check("depth sort")) return rc;
         stage_mark(tm, "sort_depth");
-
-        launch_offsets_scan(G.tiles, depth_order, G.offsets, G.scan_tmp, P, G.counters, G.key_top, (P + 63) / 64, pa.prefilter_violation,
-                            R_pin.at, R_pin.tag, s);
-        if (int rc = check("offsets scan")) return rc;
-        stage_mark(tm, "scan");
 
         nstate = seg_nstate(p->S, svgss ? p->VS : 0);
         plan = tile_sort_plan(v.T);

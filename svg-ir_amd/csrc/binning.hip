@@ -1,4 +1,4 @@
-// svg-ir_amd/csrc/binning.hip -- tile binning: depth sort, instance offsets, key emit, tile sort, tile ranges.
+// svg-ir_amd/csrc/binning.hip -- tile binning: depth sort (its last pass also yields the instance offsets), key emit, tile sort, tile ranges.
 //
 // Replaces cub::DeviceScan::InclusiveSum (rasterizer_impl.cu:307), duplicateWithKeys (:70-111),
 // cub::DeviceRadixSort::SortPairs on 64-bit (tile|depth) keys (:333-338) and identifyTileRanges (:116-138).
@@ -15,6 +15,7 @@
 // <= 31 histogram rows of the preceding blocks of its group (a two-level prefix, ~50 coalesced 1 KB row reads per
 // block), so no separate scan kernel sits between the two; the in-wave rank uses wave-level digit matching (ballots).
 #include <algorithm>
+#include <cassert>
 
 #include "common.hpp"
 
@@ -26,41 +27,71 @@ namespace {
 // Digit table layout: table[block][256] counts; gtot[group][256] = counts summed over the GS blocks of a group.
 constexpr int GS = 32;
 
-template <int ITEMS>
+// fold of two depth-key summaries {AND << 8 | OR} (identity 0xff00)
+__device__ __forceinline__ uint32_t key_top_fold(uint32_t a, uint32_t b) { return (a & b & 0xff00u) | ((a | b) & 0xffu); }
+
+// The WEIGHTED form of a pass (W = true: the last pass of the geometry depth sort, launch_radix_sort's `weights`) sums, next to every
+// count of keys, the weights of those keys -- value g weighs tiles[2 g] -- in a second table row per block (wtable), a second set of
+// group totals (wgtot) and a second, weighted rank inside the block: the exclusive prefix of the weights in sorted order (the instance
+// offsets) falls out of the same arithmetic as the output position.  Integer sums: the result does not depend on any order.
+struct WeightArgs {
+    const uint32_t* vals;   // the pass's input values (the histogram kernel gathers through them)
+    uint32_t* wgtot;        // [groups][256], zero on entry
+    RadixWeights w;
+};
+
+template <int ITEMS, bool W = false>
 __global__ void __launch_bounds__(BLOCK) radix_hist_kernel(const uint32_t* __restrict__ keys, int n_cap,
                                                            const uint32_t* __restrict__ n_dev, int bit_lo,
                                                            uint32_t mask, uint32_t* __restrict__ table,
-                                                           uint32_t* __restrict__ gtot) {
+                                                           uint32_t* __restrict__ gtot, WeightArgs wa) {
     __shared__ uint32_t hist[256];
+    __shared__ uint32_t whist[W ? 256 : 1];   // W: sum of the weights per digit
     // element count: launch-time bound n_cap, or -- when the count is still being computed on the device at launch
     // time (speculative launch before the host has read it) -- the device-side value clamped to that bound
     const int n = n_dev ? (int)min((uint32_t)n_cap, n_dev[0]) : n_cap;
     hist[threadIdx.x] = 0;
+    if constexpr (W) whist[threadIdx.x] = 0;
     __syncthreads();
     const int base = blockIdx.x * (BLOCK * ITEMS);
     uint32_t k[ITEMS];   // all loads first (clamped index), then the LDS atomics: one memory latency, not ITEMS
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) k[i] = keys[max(0, min(base + i * BLOCK + (int)threadIdx.x, n - 1))];
+    uint32_t w[W ? ITEMS : 1];   // W: the keys' weights -- the values, then ONE round of gathers through them (a second latency, not ITEMS)
+    if constexpr (W) {
+        uint32_t g[ITEMS];
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) g[i] = wa.vals[max(0, min(base + i * BLOCK + (int)threadIdx.x, n - 1))];
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) w[i] = wa.w.tiles[2 * (size_t)g[i]];   // (common.hpp GeomLayout::tiles: {count, rectangle})
+    }
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const int e = base + i * BLOCK + threadIdx.x;
         if (e < n) atomicAdd(&hist[(k[i] >> bit_lo) & mask], 1u);
+        if constexpr (W) if (e < n && w[i] != 0u) atomicAdd(&whist[(k[i] >> bit_lo) & mask], w[i]);
     }
     __syncthreads();
     const uint32_t c = hist[threadIdx.x];
     table[(size_t)blockIdx.x * 256 + threadIdx.x] = c;
     if (c) atomicAdd(&gtot[(size_t)(blockIdx.x / GS) * 256 + threadIdx.x], c);
+    if constexpr (W) {   // the same row and the same group slot once more, for the weights
+        const uint32_t wc = whist[threadIdx.x];
+        wa.w.wtable[(size_t)blockIdx.x * 256 + threadIdx.x] = wc;
+        if (wc) atomicAdd(&wa.wgtot[(size_t)(blockIdx.x / GS) * 256 + threadIdx.x], wc);
+    }
 }
 
-template <int ITEMS>
+template <int ITEMS, bool W = false>
 __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __restrict__ kin,
                                                               const uint32_t* __restrict__ vin,
                                                               uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
                                                               int n_cap, const uint32_t* __restrict__ n_dev, int bit_lo, int nbits,
                                                               const uint32_t* __restrict__ table,
-                                                              const uint32_t* __restrict__ gtot, int ngroups) {
+                                                              const uint32_t* __restrict__ gtot, int ngroups, WeightArgs wa) {
     __shared__ uint32_t wcnt[4][256];   // per-wave digit counters, later the waves' output cursors
     __shared__ uint32_t wtot[4];
+    __shared__ uint32_t wtot2[W ? 4 : 1], ksum[W ? 4 : 1], smax[W ? 4 : 1];   // W: a second scan's wave sums, key summaries, span
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint32_t mask = (1u << nbits) - 1;
     const int n = n_dev ? (int)min((uint32_t)n_cap, n_dev[0]) : n_cap;
@@ -75,23 +106,61 @@ __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __
         ks[c] = e < n ? kin[e] : 0u;
         vs[c] = e < n ? vin[e] : 0u;
     }
+    uint32_t ws[W ? ITEMS : 1];   // W: the keys' weights, one round of gathers through the values (in flight during the cursor sums)
+    if constexpr (W) {
+#pragma unroll
+        for (int c = 0; c < ITEMS; c++) ws[c] = base + c * 64 + lane < n ? wa.w.tiles[2 * (size_t)vs[c]] : 0u;
+        if (blockIdx.x == 0) {   // the publishing block folds the preprocess waves' depth-key summaries {AND << 8 | OR}
+            uint32_t kv = 0xff00u;
+#pragma unroll 8
+            for (int j = t; j < wa.w.n_key_top; j += BLOCK) kv = key_top_fold(kv, wa.w.key_top[j]);
+            kv = wave_reduce(kv, key_top_fold);
+            if (lane == 0) ksum[wave] = kv;   // (read behind the barrier of the cursor scan)
+        }
+    }
 #pragma unroll
     for (int w = 0; w < 4; w++) wcnt[w][t] = 0;
     // Output cursor of digit t for this block:
     //   sum_{d < t} total[d]  +  sum_{groups before mine} gtot[g][t]  +  sum_{blocks before me in my group} table[b][t]
     uint32_t cursor;
+    uint32_t wcursor = 0;   // W: the same three sums over the weights = the instance offset of the block's first key of digit t
     {
         const int g = blockIdx.x / GS;
-        uint32_t tot = 0, pre = 0;
+        uint32_t tot = 0, pre = 0, wsum = 0, wpre = 0;
 #pragma unroll 8
         for (int gg = 0; gg < ngroups; gg++) {
             const uint32_t v = gtot[(size_t)gg * 256 + t];
             tot += v;
             pre += gg < g ? v : 0u;
+            if constexpr (W) {
+                const uint32_t wv = wa.wgtot[(size_t)gg * 256 + t];
+                wsum += wv;
+                wpre += gg < g ? wv : 0u;
+            }
         }
 #pragma unroll 8
-        for (int b = g * GS; b < (int)blockIdx.x; b++) pre += table[(size_t)b * 256 + t];
+        for (int b = g * GS; b < (int)blockIdx.x; b++) {
+            pre += table[(size_t)b * 256 + t];
+            if constexpr (W) wpre += wa.w.wtable[(size_t)b * 256 + t];
+        }
         cursor = block_excl_scan<4>(tot, wtot) + pre;   // (its barrier also: the wave counters are zero)
+        if constexpr (W) {
+            uint32_t R;   // the sum of all weights: every block has it, the first one publishes it -- as early as the count can be known
+            wcursor = block_excl_scan<4>(wsum, wtot2, &R) + wpre;
+            if (blockIdx.x == 0 && t == 0) {
+                const uint32_t summary = key_top_fold(key_top_fold(ksum[0], ksum[1]), key_top_fold(ksum[2], ksum[3]));
+                wa.w.counters[0] = R;
+                wa.w.counters[2] = summary;
+                // the host's copy: tagged 8-byte stores into pinned host memory -- no copy operation and no event on the stream; the host
+                // recognises the values of THIS forward by the tag (api.hip): {R} and {prefilter violation << 16 | summary}
+                if (wa.w.host_out) {
+                    const uint32_t viol = wa.w.violation ? (wa.w.violation[0] != 0u ? 1u : 0u) : 0u;
+                    __hip_atomic_store(wa.w.host_out, ((unsigned long long)wa.w.host_tag << 32) | R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(wa.w.host_out + 1, ((unsigned long long)wa.w.host_tag << 32) | (viol << 16) | summary, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
+        }
     }
     // rank of every key among the keys of its WAVE with the same digit: wave-level digit matching (ballots) against a
     // wave-private digit counter in LDS -- no workgroup barrier inside the ranking
@@ -106,6 +175,69 @@ __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __
         if (valid && in_round == 0) wcnt[wave][d] = prior + (uint32_t)__popcll(same);
     }
     __syncthreads();
+    if constexpr (W) {
+        // The block's values, weights and digits go through LDS in digit-then-key order (the staging order of the large variant below): ONE
+        // exclusive scan over the staged weights ranks every key by weight among the block's keys of its digit, scan[lp] - scan[bstart[d]].
+        __shared__ uint32_t sV[BLOCK * ITEMS];
+        __shared__ __attribute__((aligned(16))) uint32_t sS[BLOCK * ITEMS];   // weights, then their exclusive scan
+        __shared__ uint8_t sD[BLOCK * ITEMS];
+        __shared__ uint32_t bstart[256], gcur[256], wgcur[256];
+        const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t], c3 = wcnt[3][t];
+        const uint32_t bs = block_excl_scan<4>(c0 + c1 + c2 + c3, wtot);   // (wtot was last read in front of the barrier above)
+        bstart[t] = bs; gcur[t] = cursor; wgcur[t] = wcursor;
+        wcnt[0][t] = bs; wcnt[1][t] = bs + c0; wcnt[2][t] = bs + c0 + c1; wcnt[3][t] = bs + c0 + c1 + c2;   // the waves' staging cursors
+        __syncthreads();
+        uint32_t span = 0;   // 1 + the last output position of a key of this thread with a non-zero weight
+#pragma unroll
+        for (int c = 0; c < ITEMS; c++) {
+            if (base + c * 64 + lane < n) {
+                const uint32_t d = (ks[c] >> bit_lo) & mask;
+                const uint32_t lp = wcnt[wave][d] + rk[c];
+                sV[lp] = vs[c]; sS[lp] = ws[c]; sD[lp] = (uint8_t)d;
+                if (ws[c] != 0u) span = max(span, gcur[d] + (lp - bstart[d]) + 1u);
+            }
+        }
+        span = wave_reduce_max(span);
+        if (lane == 0) smax[wave] = span;
+        __syncthreads();
+        const int nblk = min(BLOCK * ITEMS, n - (int)blockIdx.x * (BLOCK * ITEMS));
+        // thread t scans the ITEMS consecutive staged weights t ITEMS .. (16-byte LDS accesses); slots behind the block's keys count 0
+        uint32_t wv[ITEMS], sum = 0;
+#pragma unroll
+        for (int c = 0; c < ITEMS; c += 4) {
+            const uint4 q = reinterpret_cast<const uint4*>(sS)[(t * ITEMS + c) >> 2];
+            wv[c] = q.x; wv[c + 1] = q.y; wv[c + 2] = q.z; wv[c + 3] = q.w;
+        }
+#pragma unroll
+        for (int c = 0; c < ITEMS; c++) { wv[c] = t * ITEMS + c < nblk ? wv[c] : 0u; sum += wv[c]; }
+        // (every thread scans slots that only it reads and writes; wtot2 was last read far above.  The barrier that the scanned weights need
+        // is the one in front of the output loop below)
+        uint32_t run = block_excl_scan<4>(sum, wtot2);
+#pragma unroll
+        for (int c = 0; c < ITEMS; c += 4) {
+            uint4 q;
+            q.x = run; run += wv[c]; q.y = run; run += wv[c + 1]; q.z = run; run += wv[c + 2]; q.w = run; run += wv[c + 3];
+            reinterpret_cast<uint4*>(sS)[(t * ITEMS + c) >> 2] = q;
+        }
+        // counters[3] = the visible span of the depth order: order[0 .. span) holds every Gaussian with tiles > 0 (they sort in front of the
+        // culled ones) -- the working set of the fused shading (api.hip).  One atomic per block that holds a visible Gaussian.
+        if (t == 0) {
+            const uint32_t m = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
+            if (m != 0u) atomicMax(wa.w.counters + 3, m);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < ITEMS; c++) {
+            const int i = c * BLOCK + t;
+            if (i < nblk) {
+                const uint32_t d = sD[i], b = bstart[d];
+                const uint32_t pos = gcur[d] + ((uint32_t)i - b);
+                vout[pos] = sV[i];                                // (the sorted keys of the last pass have no reader: kout stays unwritten)
+                wa.w.offsets[pos] = wgcur[d] + (sS[i] - sS[b]);
+            }
+        }
+        return;
+    }
     if (ITEMS >= 16) {
         // Large inputs (bandwidth, not launch latency, sets the time): the block's keys are first put in digit order in LDS, then
         // written out -- consecutive lanes write consecutive addresses of a digit's run (a block of 4096 keys holds runs of ~32 per 7-bit
@@ -292,105 +424,6 @@ __global__ void __launch_bounds__(BLOCK) ts12_scatter_kernel(const uint32_t* __r
     }
 }
 
-// ---- instance offsets: exclusive scan of tiles[order[i]] ---------------------------------------------------
-// fold of two depth-key summaries {AND << 8 | OR} (identity 0xff00)
-__device__ __forceinline__ uint32_t key_top_fold(uint32_t a, uint32_t b) { return (a & b & 0xff00u) | ((a | b) & 0xffu); }
-
-// (the counts gathered here are parked, in depth order, in `offsets`: the write kernel reads them back with coalesced loads instead of
-// repeating the P random gathers, then overwrites them with the prefix)
-__global__ void __launch_bounds__(BLOCK) offsets_reduce_kernel(const uint32_t* __restrict__ tiles,
-                                                               const uint32_t* __restrict__ order, int n,
-                                                               uint32_t* __restrict__ counts_out,
-                                                               uint32_t* __restrict__ block_sums,
-                                                               const uint32_t* __restrict__ key_top, int n_key_top,
-                                                               uint32_t* __restrict__ block_key) {
-    __shared__ uint32_t wsum[4];
-    if (threadIdx.x < 64) {   // this block's slice of the preprocess waves' depth-key summaries {AND << 8 | OR}: SCAN_BLOCK_ELEMS / 64 = 32 entries
-        const int j = blockIdx.x * (SCAN_BLOCK_ELEMS / 64) + (int)threadIdx.x;
-        uint32_t kv = (threadIdx.x < SCAN_BLOCK_ELEMS / 64 && j < n_key_top) ? key_top[j] : 0xff00u;
-        kv = wave_reduce(kv, key_top_fold);
-        if (threadIdx.x == 0) block_key[blockIdx.x] = kv;
-    }
-    uint32_t v[8];
-    const int base = blockIdx.x * SCAN_BLOCK_ELEMS + threadIdx.x * 8;
-    uint32_t oi[8];   // two rounds of independent loads instead of 8 dependent pairs
-#pragma unroll
-    for (int i = 0; i < 8; i++) oi[i] = order[min(base + i, n - 1)];
-#pragma unroll
-    for (int i = 0; i < 8; i++) v[i] = tiles[2 * oi[i]];   // (common.hpp GeomLayout::tiles: {count, rectangle})
-#pragma unroll
-    for (int i = 0; i < 8; i++) v[i] = (base + i < n) ? v[i] : 0u;
-    if (base + 8 <= n) {   // (P-sized arrays start 256-byte aligned: two 16-byte stores)
-        reinterpret_cast<uint4*>(counts_out + base)[0] = make_uint4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<uint4*>(counts_out + base)[1] = make_uint4(v[4], v[5], v[6], v[7]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; i++) if (base + i < n) counts_out[base + i] = v[i];
-    }
-    uint32_t sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) sum += v[i];
-    const uint32_t total = block_sum<4>(sum, wsum);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(BLOCK) offsets_write_kernel(int n,
-                                                              const uint32_t* __restrict__ block_sums,
-                                                              uint32_t* __restrict__ offsets, int nblocks,
-                                                              uint32_t* __restrict__ total_out,
-                                                              const uint32_t* __restrict__ block_key,
-                                                              const uint32_t* __restrict__ violation,
-                                                              unsigned long long* __restrict__ host_out, uint32_t host_tag) {
-    __shared__ uint32_t wsum[4];
-    __shared__ uint32_t psum[4];
-    __shared__ uint32_t ksum[4];
-    uint32_t v[8];
-    const int base = blockIdx.x * SCAN_BLOCK_ELEMS + threadIdx.x * 8;
-    if (base + 8 <= n) {   // the counts the reduce kernel parked in `offsets` (depth order)
-        const uint4 a4 = reinterpret_cast<const uint4*>(offsets + base)[0], b4 = reinterpret_cast<const uint4*>(offsets + base)[1];
-        v[0] = a4.x; v[1] = a4.y; v[2] = a4.z; v[3] = a4.w; v[4] = b4.x; v[5] = b4.y; v[6] = b4.z; v[7] = b4.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; i++) v[i] = (base + i < n) ? offsets[base + i] : 0u;
-    }
-    const bool last = blockIdx.x == (unsigned)(nblocks - 1);
-    uint32_t kv = 0xff00u;
-    if (last)   // the last block also folds the blocks' depth-key summaries
-        for (int b = threadIdx.x; b < nblocks; b += BLOCK) kv = key_top_fold(kv, block_key[b]);
-    kv = wave_reduce(kv, key_top_fold);
-    if ((threadIdx.x & 63) == 0) ksum[threadIdx.x >> 6] = kv;
-    // sum of the preceding blocks' totals (the block sums are few: every block adds them up itself, no scan kernel)
-    const uint32_t before = blocks_before<4>(block_sums, (int)blockIdx.x, psum);   // (its barrier also publishes ksum)
-    uint32_t sum = 0, total;
-#pragma unroll
-    for (int i = 0; i < 8; i++) sum += v[i];
-    uint32_t run = before + block_excl_scan<4>(sum, wsum, &total);
-    uint32_t span = 0;   // 1 + position (in depth order) of this thread's last Gaussian that touches a tile
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        if (base + i < n) offsets[base + i] = run;
-        run += v[i];
-        if (v[i] != 0u) span = (uint32_t)(base + i + 1);
-    }
-    // total_out[3] = the visible span of the depth order: order[0 .. span) holds every Gaussian with tiles > 0 (they sort in front of
-    // the culled ones) -- the working set of the fused shading (api.hip).  One atomic per wave that holds a visible Gaussian.
-    span = wave_reduce_max(span);
-    if ((threadIdx.x & 63) == 0 && span != 0u) atomicMax(total_out + 3, span);
-    if (last && threadIdx.x == 0) {
-        const uint32_t R = before + total;
-        const uint32_t summary = key_top_fold(key_top_fold(ksum[0], ksum[1]), key_top_fold(ksum[2], ksum[3]));
-        total_out[0] = R;
-        total_out[2] = summary;
-        // the host's copy: tagged 8-byte stores into pinned host memory -- no copy operation and no event on the stream; the host
-        // recognises the values of THIS forward by the tag (api.hip): {R} and {prefilter violation << 16 | summary}
-        if (host_out) {
-            const uint32_t viol = violation ? (violation[0] != 0u ? 1u : 0u) : 0u;
-            __hip_atomic_store(host_out, ((unsigned long long)host_tag << 32) | R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_out + 1, ((unsigned long long)host_tag << 32) | (viol << 16) | summary, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-
 // ---- emit --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(BLOCK) emit_kernel(int P, const uint32_t* __restrict__ order,
                                                      const uint32_t* __restrict__ tiles,
@@ -569,18 +602,28 @@ void launch_order_desc(const uint32_t* counts, int n, uint32_t* order, uint32_t*
 
 template <int ITEMS>
 static void radix_sort_impl(uint32_t* const key[2], uint32_t* const val[2], int n, const uint32_t* n_dev, int total_bits,
-                            int bits_per_pass, uint32_t* tbl, uint32_t* gtot, hipStream_t s) {
+                            int bits_per_pass, uint32_t* tbl, uint32_t* gtot, hipStream_t s, const RadixWeights* weights) {
     const int per = BLOCK * ITEMS;
     const int nb = (n + per - 1) / per;
     const int ng = (nb + GS - 1) / GS;
     const int passes = (total_bits + bits_per_pass - 1) / bits_per_pass;
+    // the weighted pass: count known at launch (block 0 publishes it for the host), digits staged as bytes, its totals in the slot behind four passes'
+    assert(!weights || (n_dev == nullptr && bits_per_pass <= 8 && passes <= RADIX_WGTOT_SLOT));
     for (int p = 0; p < passes; p++) {
         const int lo = p * bits_per_pass, nbits = std::min(bits_per_pass, total_bits - lo);
         uint32_t* gt = gtot + (size_t)p * ng * 256;
+        if (weights && p == passes - 1) {
+            const WeightArgs wa{val[p & 1], gtot + (size_t)RADIX_WGTOT_SLOT * ng * 256, *weights};
+            hipLaunchKernelGGL((radix_hist_kernel<ITEMS, true>), dim3(nb), dim3(BLOCK), 0, s, key[p & 1], n, n_dev, lo,
+                               (1u << nbits) - 1, tbl, gt, wa);
+            hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, true>), dim3(nb), dim3(BLOCK), 0, s, key[p & 1], val[p & 1],
+                               key[(p + 1) & 1], val[(p + 1) & 1], n, n_dev, lo, nbits, tbl, gt, ng, wa);
+            break;
+        }
         hipLaunchKernelGGL((radix_hist_kernel<ITEMS>), dim3(nb), dim3(BLOCK), 0, s, key[p & 1], n, n_dev, lo,
-                           (1u << nbits) - 1, tbl, gt);
+                           (1u << nbits) - 1, tbl, gt, WeightArgs{});
         hipLaunchKernelGGL((radix_scatter_kernel<ITEMS>), dim3(nb), dim3(BLOCK), 0, s, key[p & 1], val[p & 1],
-                           key[(p + 1) & 1], val[(p + 1) & 1], n, n_dev, lo, nbits, tbl, gt, ng);
+                           key[(p + 1) & 1], val[(p + 1) & 1], n, n_dev, lo, nbits, tbl, gt, ng, WeightArgs{});
     }
 }
 
@@ -588,22 +631,13 @@ static void radix_sort_impl(uint32_t* const key[2], uint32_t* const val[2], int 
 // the result lands in slot (passes & 1) of the ping/pong buffers.  `n` sizes the launch and the scratch
 // (`table`: radix_table_words(n) counters, its radix_gtot() part zeroed by the caller); if `n_dev` is not null the element count is min(n, *n_dev), read on the
 // device (the count need not be known on the host at launch time).
+// `weights`: see common.hpp RadixWeights.
 void launch_radix_sort(uint32_t* const key[2], uint32_t* const val[2], int n, const uint32_t* n_dev, int total_bits,
-                       int bits_per_pass, uint32_t* table, hipStream_t s) {
+                       int bits_per_pass, uint32_t* table, hipStream_t s, const RadixWeights* weights) {
     if (n <= 0) return;
-    uint32_t* gtot = radix_gtot(table, n);  // [passes <= 4][groups][256] group digit totals, zero on entry
-    if (n <= (1 << 20)) radix_sort_impl<4>(key, val, n, n_dev, total_bits, bits_per_pass, table, gtot, s);
-    else radix_sort_impl<16>(key, val, n, n_dev, total_bits, bits_per_pass, table, gtot, s);
-}
-
-void launch_offsets_scan(const uint32_t* tiles, const uint32_t* order, uint32_t* offsets, uint32_t* scan_tmp, int n,
-                         uint32_t* total_out, const uint32_t* key_top, int n_key_top, const uint32_t* violation,
-                         unsigned long long* host_out, uint32_t host_tag, hipStream_t s) {
-    const int nb = scan_blocks(n);
-    uint32_t* block_key = scan_tmp + nb + 1;
-    hipLaunchKernelGGL(offsets_reduce_kernel, dim3(nb), dim3(BLOCK), 0, s, tiles, order, n, offsets, scan_tmp, key_top, n_key_top, block_key);
-    hipLaunchKernelGGL(offsets_write_kernel, dim3(nb), dim3(BLOCK), 0, s, n, scan_tmp, offsets, nb,
-                       total_out, block_key, violation, host_out, host_tag);
+    uint32_t* gtot = radix_gtot(table, n);  // [passes <= 4, + the weighted pass's slot][groups][256] group totals, zero on entry
+    if (n <= (1 << 20)) radix_sort_impl<4>(key, val, n, n_dev, total_bits, bits_per_pass, table, gtot, s, weights);
+    else radix_sort_impl<16>(key, val, n, n_dev, total_bits, bits_per_pass, table, gtot, s, weights);
 }
 
 void launch_emit(int P, const uint32_t* order, const uint32_t* tiles, const uint32_t* offsets, float* rec,

@@ -58,8 +58,10 @@ constexpr int SORT_ITEMS = 16;                      // elements per thread per b
 constexpr int SORT_BLOCK_ELEMS = BLOCK * SORT_ITEMS;  // 4096
 // upper bound of the number of radix blocks for n keys (1024 keys per block for small inputs)
 inline int sort_blocks(int n) { return n <= 0 ? 1 : (n + 1023) / 1024; }
-// radix scratch: [sort_blocks][256] block histograms + [4 passes][sort_blocks/32 + 1][256] group totals
-inline size_t radix_gtot_words(int n) { return (size_t)4 * 256 * (sort_blocks(n) / 32 + 1); }
+// radix scratch: [sort_blocks][256] block histograms + [4 passes + 1][sort_blocks/32 + 1][256] group totals (the fifth slot: the weight
+// totals of a weighted last pass, RadixWeights)
+constexpr int RADIX_WGTOT_SLOT = 4;
+inline size_t radix_gtot_words(int n) { return (size_t)5 * 256 * (sort_blocks(n) / 32 + 1); }
 inline size_t radix_table_words(int n) { return (size_t)256 * sort_blocks(n) + radix_gtot_words(n); }
 // group totals of a sort over (up to) n elements; they must be ZERO when launch_radix_sort runs (the stage in front of each
 // sort clears them in passing: preprocess for the depth sort, emit for the tile sort)
@@ -75,9 +77,9 @@ struct GeomLayout {
                            // the emit kernel everything it needs (it used to gather the count, the radius and the record's mean2D)
     uint32_t* key[2];      // [P] depth keys ping/pong
     uint32_t* idx[2];      // [P] Gaussian ids ping/pong (idx[final] = depth-sorted order)
-    uint32_t* offsets;     // [P] exclusive scan of tiles in depth-sorted order
-    uint32_t* scan_tmp;    // [2 * (scan_blocks(P)+1)]: block sums | per-block depth-key summaries
-    uint32_t* radix_tbl;   // [256 * sort_blocks(P)]
+    uint32_t* offsets;     // [P] exclusive scan of tiles in depth-sorted order (written by the depth sort's last pass)
+    uint32_t* radix_tbl;   // [radix_table_words(P)]
+    uint32_t* radix_wtbl;  // [256 * sort_blocks(P)] per block and digit: the tile counts summed by the depth sort's last pass
     uint32_t* counters;    // [4]: [0] = R, [1] = prefilter violation, [2] = top bytes of the visible depth keys {AND << 8 | OR},
                            // [3] = visible span of the depth order (1 + position of the last Gaussian with tiles > 0)
     uint32_t* key_top;     // [ceil(P / 64)] the same per preprocess wave (identity 0xff00 where a wave has no visible Gaussian)
@@ -101,8 +103,8 @@ inline GeomLayout geom_layout(char* base, int P) {
     g.idx[0] = (uint32_t*)take(p * 4);
     g.idx[1] = (uint32_t*)take(p * 4);
     g.offsets = (uint32_t*)take(p * 4);
-    g.scan_tmp = (uint32_t*)take(((size_t)scan_blocks(P) + 1) * 8);
     g.radix_tbl = (uint32_t*)take(radix_table_words(P) * 4);
+    g.radix_wtbl = (uint32_t*)take((size_t)256 * sort_blocks(P) * 4);
     g.counters = (uint32_t*)take(16);
     g.key_top = (uint32_t*)take((p + 63) / 64 * 4);
     g.needed = (uint8_t*)take(p);
@@ -475,14 +477,23 @@ void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t
 // stable LSD radix sort of (u32 key, u32 value) pairs on bits [0, total_bits) in passes of bits_per_pass (<= 8);
 // input in slot 0 of the ping/pong buffers, result in slot (passes & 1); table: radix_table_words(n) counters
 // element count = n, or min(n, *n_dev) read on the device when n_dev != nullptr (n then only sizes launch + scratch)
+// `weights` (the geometry depth sort only; n_dev must be null): the LAST pass also sums a weight per value -- value g weighs tiles[2 g],
+// the Gaussian's tile count -- through the same histogram rows, group totals and ranks as it counts keys, and writes next to the sorted
+// values offsets[i] = exclusive prefix sum of the weights in sorted order.  Its first workgroup publishes counters[0] = the total,
+// counters[2] = the per-wave depth-key summaries `key_top[n_key_top]` folded into one word, and into host_out (pinned host memory, or
+// null) {host_tag << 32 | total}, {host_tag << 32 | (*violation != 0) << 16 | that word}; counters[3] (zero on entry) becomes 1 + the last
+// sorted position with a non-zero weight.  The sorted KEYS of that pass are not written (nothing reads them).
+struct RadixWeights {
+    const uint32_t* tiles;      // GeomLayout::tiles
+    uint32_t* wtable;           // [256 * sort_blocks(n)] scratch (GeomLayout::radix_wtbl)
+    uint32_t* offsets;          // [n] out
+    uint32_t* counters;         // GeomLayout::counters
+    const uint32_t* key_top; int n_key_top;
+    const uint32_t* violation;  // may be null
+    unsigned long long* host_out; uint32_t host_tag;
+};
 void launch_radix_sort(uint32_t* const key[2], uint32_t* const val[2], int n, const uint32_t* n_dev, int total_bits,
-                       int bits_per_pass, uint32_t* table, hipStream_t s);
-// offsets[i] = exclusive prefix sum of tiles[order[i]]; total -> *total_out
-// total_out[2] = the per-wave depth-key summaries `key_top[n_key_top]` folded into one word; host_out (pinned host memory, or null):
-// {host_tag << 32 | total}, {host_tag << 32 | (*violation != 0) << 16 | that word} stored by the last block
-void launch_offsets_scan(const uint32_t* tiles, const uint32_t* order, uint32_t* offsets, uint32_t* scan_tmp, int n,
-                         uint32_t* total_out, const uint32_t* key_top, int n_key_top, const uint32_t* violation,
-                         unsigned long long* host_out, uint32_t host_tag, hipStream_t s);
+                       int bits_per_pass, uint32_t* table, hipStream_t s, const RadixWeights* weights = nullptr);
 // also clears ranges[2*gx*gy] + the per-tile-block segment counts behind it, the live-segment counter, the group totals of the tile sort's table (`sort_table`,
 // sized for `cap` elements) and the cull's dispatch buckets (`disp_ctr`: ImageLayout::disp_ctr, DISP_CTR_WORDS words)
 void launch_emit(int P, const uint32_t* order, const uint32_t* tiles, const uint32_t* offsets, float* rec,
