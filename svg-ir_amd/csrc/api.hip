@@ -19,6 +19,7 @@
 
 #include "common.hpp"
 #include "workload_history.hpp"
+#include "depth_sort_plan.hpp"
 
 using namespace svgir;
 
@@ -585,7 +586,8 @@ struct ForwardCall {
                 uint32_t* cnt = G.shade_work + partition_work_words(P) - 1;
                 launch_partition(P, G.needed, nullptr, G.shade_list, G.shade_work, cnt, s);
                 sp.subset = G.shade_list; sp.subset_count = cnt;
-            } else if (shade_subset) {   // (a permutation of 0..P-1 whose first counters[3] entries hold every surfel that touches a tile)
+            } else if (shade_subset) {   // (a permutation of 0..P-1 whose first counters[3] entries hold every surfel that touches a tile; behind them, under either
+                                         // depth-sort plan, the others in no order that matters: the shading clears their rows)
                 sp.subset = depth_order; sp.subset_count = G.counters + 3;
             }
             if (shade_forward_impl(&sp, p->shade->reduced, const_cast<float*>(p->features), const_cast<float*>(p->vfeatures), true, s) != 0)
@@ -670,7 +672,12 @@ struct ForwardCall {
         depth_order = G.idx[(depth_bits / 8) & 1];
         // (its last pass sums the tile counts next to the keys: G.offsets, the instance count R and what the host reads with it -- no scan stage)
         const RadixWeights rw{G.tiles, G.radix_wtbl, G.offsets, G.counters, G.key_top, (P + 63) / 64, pa.prefilter_violation, R_pin.at, R_pin.tag};
-        launch_radix_sort(G.key, G.idx, P, nullptr, depth_bits, 8, G.radix_tbl, s, &rw);
+        // (under a speculated byte and up to DEPTH_BUCKET_MAX_P keys: one global pass over the visible keys + in-LDS bucket sorts, which
+        // end in the same slot with the same visible order and offsets -- depth_sort_plan.hpp)
+        static const bool forced_lsd = depth_sort_forced_lsd(getenv("SVGIR_DEPTH_SORT"));
+        static const int bucket_cap = depth_bucket_cap(getenv("SVGIR_DEPTH_BUCKET_CAP"));
+        if (depth_sort_plan(P, spec_top, forced_lsd) == DepthSortPlan::kBuckets) launch_depth_bucket_sort(G.key, G.idx, P, G.radix_tbl, bucket_cap, s, rw);
+        else launch_radix_sort(G.key, G.idx, P, nullptr, depth_bits, 8, G.radix_tbl, s, &rw);
         if (int rc = check("depth sort")) return rc;
         stage_mark(tm, "sort_depth");
 

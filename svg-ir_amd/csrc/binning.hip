@@ -18,6 +18,7 @@
 #include <cassert>
 
 #include "common.hpp"
+#include "depth_sort_plan.hpp"
 
 namespace svgir {
 
@@ -40,7 +41,9 @@ struct WeightArgs {
     RadixWeights w;
 };
 
-template <int ITEMS, bool W = false>
+// F (with W; the bucket plan's one global pass, launch_depth_bucket_sort): a key that weighs nothing is not counted, and the per-block
+// weight rows are not written (the pass's scatter needs the weights' group totals only).
+template <int ITEMS, bool W = false, bool F = false>
 __global__ void __launch_bounds__(BLOCK) radix_hist_kernel(const uint32_t* __restrict__ keys, int n_cap,
                                                            const uint32_t* __restrict__ n_dev, int bit_lo,
                                                            uint32_t mask, uint32_t* __restrict__ table,
@@ -68,7 +71,8 @@ __global__ void __launch_bounds__(BLOCK) radix_hist_kernel(const uint32_t* __res
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const int e = base + i * BLOCK + threadIdx.x;
-        if (e < n) atomicAdd(&hist[(k[i] >> bit_lo) & mask], 1u);
+        if constexpr (F) { if (e < n && w[i] != 0u) atomicAdd(&hist[(k[i] >> bit_lo) & mask], 1u); }
+        else if (e < n) atomicAdd(&hist[(k[i] >> bit_lo) & mask], 1u);
         if constexpr (W) if (e < n && w[i] != 0u) atomicAdd(&whist[(k[i] >> bit_lo) & mask], w[i]);
     }
     __syncthreads();
@@ -77,7 +81,7 @@ __global__ void __launch_bounds__(BLOCK) radix_hist_kernel(const uint32_t* __res
     if (c) atomicAdd(&gtot[(size_t)(blockIdx.x / GS) * 256 + threadIdx.x], c);
     if constexpr (W) {   // the same row and the same group slot once more, for the weights
         const uint32_t wc = whist[threadIdx.x];
-        wa.w.wtable[(size_t)blockIdx.x * 256 + threadIdx.x] = wc;
+        if constexpr (!F) wa.w.wtable[(size_t)blockIdx.x * 256 + threadIdx.x] = wc;
         if (wc) atomicAdd(&wa.wgtot[(size_t)(blockIdx.x / GS) * 256 + threadIdx.x], wc);
     }
 }
@@ -285,6 +289,276 @@ __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __
             kout[pos] = ks[c];
             vout[pos] = vs[c];
         }
+    }
+}
+
+// ---- bucket plan of the geometry depth sort (depth_sort_plan.hpp) -------------------------------------------------
+// Under a speculated common top byte 24 key bits are left, and the culled Gaussians -- more than half of a closed surface's surfels -- emit
+// nothing.  ONE global pass (filtered weighted histogram above + the scatter below) puts the visible keys, stably, into the 256 buckets of
+// bits 16..23; each bucket is a contiguous range that one workgroup finishes on bits 0..15 inside LDS, and the same workgroup scans the
+// weights in final order: the instance offsets.  Three launches instead of three passes of two.
+
+// The scatter of that pass: radix_scatter_kernel's cursors and ranking over the keys that weigh something; a key's weight travels with it
+// (wout: the offsets array, which the bucket kernel reads and then overwrites).  Block 0 publishes what the weighted LSD pass publishes --
+// it needs the weights' group totals only -- and counters[3] = the number of visible keys.
+template <int ITEMS>
+__global__ void __launch_bounds__(BLOCK) depth_bucket_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
+                                                                     uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
+                                                                     uint32_t* __restrict__ wout, int n, int bit_lo,
+                                                                     const uint32_t* __restrict__ table, const uint32_t* __restrict__ gtot,
+                                                                     const uint32_t* __restrict__ wgtot, int ngroups, RadixWeights w) {
+    __shared__ uint32_t wcnt[4][256];   // per-wave digit counters, later the waves' output cursors
+    __shared__ uint32_t wtot[4], wtot2[4], wtot3[4], ksum[4], wcul[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int base = blockIdx.x * (BLOCK * ITEMS) + wave * (64 * ITEMS);
+    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint32_t ks[ITEMS], vs[ITEMS], ws[ITEMS], rk[ITEMS];
+#pragma unroll
+    for (int c = 0; c < ITEMS; c++) {
+        const int e = base + c * 64 + lane;
+        ks[c] = e < n ? kin[e] : 0u;
+        vs[c] = e < n ? vin[e] : 0u;
+    }
+#pragma unroll
+    for (int c = 0; c < ITEMS; c++) ws[c] = base + c * 64 + lane < n ? w.tiles[2 * (size_t)vs[c]] : 0u;
+    if (blockIdx.x == 0) {   // the publishing block folds the preprocess waves' depth-key summaries {AND << 8 | OR}
+        uint32_t kv = 0xff00u;
+#pragma unroll 8
+        for (int j = t; j < w.n_key_top; j += BLOCK) kv = key_top_fold(kv, w.key_top[j]);
+        kv = wave_reduce(kv, key_top_fold);
+        if (lane == 0) ksum[wave] = kv;   // (read behind the barrier of the cursor scan)
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) wcnt[q][t] = 0;
+    uint32_t cursor, nvis, cull_base;   // cull_base: where this block's first key without weight goes
+    {
+        const int g = blockIdx.x / GS;
+        uint32_t tot = 0, pre = 0, wsum = 0;
+#pragma unroll 8
+        for (int gg = 0; gg < ngroups; gg++) {
+            const uint32_t v = gtot[(size_t)gg * 256 + t];
+            tot += v;
+            pre += gg < g ? v : 0u;
+            if (blockIdx.x == 0) wsum += wgtot[(size_t)gg * 256 + t];
+        }
+#pragma unroll 8
+        for (int b = g * GS; b < (int)blockIdx.x; b++) pre += table[(size_t)b * 256 + t];
+        cursor = block_excl_scan<4>(tot, wtot, &nvis) + pre;   // (its barrier also: the wave counters are zero)
+        cull_base = nvis + blockIdx.x * (BLOCK * ITEMS) - block_sum<4>(pre, wtot3);   // (every block in front of this one is full)
+        if (blockIdx.x == 0) {
+            uint32_t R;
+            (void)block_excl_scan<4>(wsum, wtot2, &R);
+            if (t == 0) {
+                const uint32_t summary = key_top_fold(key_top_fold(ksum[0], ksum[1]), key_top_fold(ksum[2], ksum[3]));
+                w.counters[0] = R;
+                w.counters[2] = summary;
+                w.counters[3] = nvis;
+                if (w.host_out) {   // (tag format: radix_scatter_kernel)
+                    const uint32_t viol = w.violation ? (w.violation[0] != 0u ? 1u : 0u) : 0u;
+                    __hip_atomic_store(w.host_out, ((unsigned long long)w.host_tag << 32) | R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(w.host_out + 1, ((unsigned long long)w.host_tag << 32) | (viol << 16) | summary, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
+        }
+    }
+    uint32_t ncul = 0;
+#pragma unroll
+    for (int c = 0; c < ITEMS; c++) {
+        const bool valid = base + c * 64 + lane < n && ws[c] != 0u;
+        const uint32_t d = (ks[c] >> bit_lo) & 255u;
+        const unsigned long long same = wave_match(d, 8, valid);
+        const uint32_t in_round = (uint32_t)__popcll(same & lt_mask);
+        const uint32_t prior = wcnt[wave][d];   // (the DS operations of a wave execute in order: every lane reads before the leader writes)
+        rk[c] = prior + in_round;
+        if (valid && in_round == 0) wcnt[wave][d] = prior + (uint32_t)__popcll(same);
+        // a key without weight: its rank among those of its wave, in key order
+        const unsigned long long culled = __ballot(base + c * 64 + lane < n && ws[c] == 0u);
+        if (!valid) rk[c] = ncul + (uint32_t)__popcll(culled & lt_mask);
+        ncul += (uint32_t)__popcll(culled);
+    }
+    if (lane == 0) wcul[wave] = ncul;
+    __syncthreads();
+    {   // digit t: the waves' cursors = block cursor + counts of the waves in front
+        const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t];
+        __syncthreads();
+        wcnt[0][t] = cursor; wcnt[1][t] = cursor + c0; wcnt[2][t] = cursor + c0 + c1; wcnt[3][t] = cursor + c0 + c1 + c2;
+    }
+    __syncthreads();
+    for (int q = 0; q < wave; q++) cull_base += wcul[q];
+#pragma unroll
+    for (int c = 0; c < ITEMS; c++) {
+        if (base + c * 64 + lane >= n) continue;
+        if (ws[c] != 0u) {
+            const uint32_t pos = wcnt[wave][(ks[c] >> bit_lo) & 255u] + rk[c];
+            kout[pos] = ks[c];
+            vout[pos] = vs[c];
+            wout[pos] = ws[c];
+        } else {
+            // (the values without weight follow the visible ones, in their input order: val[1] stays a permutation of the input values, and
+            // the fused shading walks its back to clear the rows of the surfels this view does not shade -- shade.hip zero_rest_rows)
+            vout[cull_base + rk[c]] = vs[c];
+        }
+    }
+}
+
+constexpr int DB_THREADS = 1024, DB_WAVES = DB_THREADS / 64, DB_ROUNDS = DEPTH_BUCKET_CAP / DB_THREADS;
+
+// One stable 8-bit counting pass of the whole workgroup (DB_THREADS threads, all of them) over m <= DEPTH_BUCKET_CAP items.  get(i) is
+// item i = {sort word, payload}, its digit (word >> shift) & 255; put(pos, item) stores it.  Wave w ranks the w-th run of consecutive items
+// (wave_match against wave-private counters, no workgroup barrier inside), thread d < 256 then turns the 16 counts of digit d into the
+// waves' cursors.  CARRY = false: positions 0 .. m, the digit bases are the exclusive scan of this call's counts.  CARRY = true: the bases
+// are cur[256], which the call advances -- a pass over a longer range, chunk by chunk in order (ties that straddle two chunks stay in
+// order).  Ends with a barrier: the items are in place, every scratch array is free.
+template <bool CARRY, class Get, class Put>
+__device__ __forceinline__ void bucket_pass(int m, int shift, Get get, Put put, uint32_t (*wcnt)[256], uint32_t* cur, uint32_t* wsum) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    for (int i = t; i < DB_WAVES * 256; i += DB_THREADS) (&wcnt[0][0])[i] = 0u;
+    __syncthreads();
+    const int per = ((m + DB_WAVES - 1) / DB_WAVES + 63) & ~63;   // (<= 64 DB_ROUNDS)
+    const int base = wave * per;
+    uint2 it[DB_ROUNDS];
+    uint32_t rk[DB_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < DB_ROUNDS; r++) {
+        if (r * 64 < per) {   // (uniform over the workgroup)
+            const int i = base + r * 64 + lane;
+            const bool valid = i < m;
+            it[r] = valid ? get(i) : make_uint2(0u, 0u);
+            const uint32_t d = (it[r].x >> shift) & 255u;
+            const unsigned long long same = wave_match(d, 8, valid);
+            const uint32_t in_round = (uint32_t)__popcll(same & lt_mask);
+            const uint32_t prior = wcnt[wave][d];   // (the DS operations of a wave execute in order: every lane reads before the leader writes)
+            rk[r] = prior + in_round;
+            if (valid && in_round == 0) wcnt[wave][d] = prior + (uint32_t)__popcll(same);
+        }
+    }
+    __syncthreads();
+    uint32_t c[DB_WAVES], total = 0;
+#pragma unroll
+    for (int q = 0; q < DB_WAVES; q++) { c[q] = t < 256 ? wcnt[q][t] : 0u; total += c[q]; }
+    uint32_t run;
+    if constexpr (CARRY) run = t < 256 ? cur[t] : 0u;
+    else run = block_excl_scan<DB_WAVES>(total, wsum);
+    if (t < 256) {   // (column t of the counters is this thread's alone until the barrier)
+#pragma unroll
+        for (int q = 0; q < DB_WAVES; q++) { wcnt[q][t] = run; run += c[q]; }
+        if constexpr (CARRY) cur[t] = run;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < DB_ROUNDS; r++) {
+        if (r * 64 < per) {
+            const int i = base + r * 64 + lane;
+            if (i < m) put(wcnt[wave][(it[r].x >> shift) & 255u] + rk[r], it[r]);
+        }
+    }
+    __syncthreads();
+}
+
+// Workgroup d finishes bucket d: the keys whose bits 16..23 are d, n of them from position `start` of slot 1 (key1 / val1 / their weights in
+// `offsets`); start, n and the weight base are exclusive sums over the digits of the pass's group totals.
+//   n <= cap: keys {low 16 bits | local index}, ids and weights into LDS, two in-LDS passes, the weights scanned in final order, out.
+//   n > cap, low 16 bits all equal: the order is already there; the weights (gathered through the ids) are scanned chunk by chunk.
+//   n > cap otherwise: the two passes run chunk by chunk through global memory -- the bucket's own range of slot 0 and back -- then that scan.
+// Nothing outside [start, start + n) is touched: the buckets are disjoint.
+__global__ void __launch_bounds__(DB_THREADS) depth_bucket_sort_kernel(uint32_t* key0, uint32_t* val0, uint32_t* key1, uint32_t* val1, uint32_t* offsets,
+                                                                       const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ gtot,
+                                                                       const uint32_t* __restrict__ wgtot, int ngroups, int cap) {
+    __shared__ uint32_t sA[DEPTH_BUCKET_CAP], sB[DEPTH_BUCKET_CAP], sI[DEPTH_BUCKET_CAP], sW[DEPTH_BUCKET_CAP];
+    __shared__ uint32_t wcnt[DB_WAVES][256];
+    __shared__ uint32_t cur[256], wsum[DB_WAVES], wsum2[DB_WAVES], hdr[3], red[2][DB_WAVES];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t cnt = 0, wt = 0;
+    if (t < 256)
+        for (int g = 0; g < ngroups; g++) { cnt += gtot[(size_t)g * 256 + t]; wt += wgtot[(size_t)g * 256 + t]; }
+    const uint32_t cpre = block_excl_scan<DB_WAVES>(cnt, wsum);
+    const uint32_t wpre = block_excl_scan<DB_WAVES>(wt, wsum2);
+    if (t == (int)blockIdx.x) { hdr[0] = cpre; hdr[1] = cnt; hdr[2] = wpre; }
+    __syncthreads();
+    const uint32_t start = hdr[0], wbase = hdr[2];
+    const int n = (int)hdr[1];
+    if (n == 0) return;
+    if (n <= cap) {
+        for (int i = t; i < n; i += DB_THREADS) {
+            sA[i] = (key1[start + i] << 16) | (uint32_t)i;
+            sI[i] = val1[start + i];
+            sW[i] = offsets[start + i];
+        }
+        // (the barrier behind the passes' clearing of the counters also orders these stores)
+        bucket_pass<false>(n, 16, [&](int i) { return make_uint2(sA[i], 0u); }, [&](uint32_t pos, uint2 it) { sB[pos] = it.x; }, wcnt, cur, wsum);
+        bucket_pass<false>(n, 24, [&](int i) { return make_uint2(sB[i], 0u); }, [&](uint32_t pos, uint2 it) { sA[pos] = it.x; }, wcnt, cur, wsum);
+        // the weights in final order, DB_ROUNDS consecutive ones per thread, and their exclusive scan (into sB)
+        uint32_t wv[DB_ROUNDS], sum = 0;
+#pragma unroll
+        for (int j = 0; j < DB_ROUNDS; j++) {
+            const int i = t * DB_ROUNDS + j;
+            wv[j] = i < n ? sW[sA[i] & 0xffffu] : 0u;
+            sum += wv[j];
+        }
+        uint32_t run = block_excl_scan<DB_WAVES>(sum, wsum2);
+#pragma unroll
+        for (int j = 0; j < DB_ROUNDS; j++) {
+            const int i = t * DB_ROUNDS + j;
+            if (i < n) sB[i] = run;
+            run += wv[j];
+        }
+        __syncthreads();
+        for (int i = t; i < n; i += DB_THREADS) {
+            val1[start + i] = sI[sA[i] & 0xffffu];
+            offsets[start + i] = wbase + sB[i];
+        }
+        return;
+    }
+    {   // do the low 16 bits differ at all?
+        uint32_t a = 0xffffu, o = 0u;
+        for (int i = t; i < n; i += DB_THREADS) { const uint32_t k = key1[start + i] & 0xffffu; a &= k; o |= k; }
+        a = wave_reduce(a, [](uint32_t x, uint32_t y) { return x & y; });
+        o = wave_reduce(o, [](uint32_t x, uint32_t y) { return x | y; });
+        if (lane == 0) { red[0][wave] = a; red[1][wave] = o; }
+        __syncthreads();
+        a = 0xffffu; o = 0u;
+#pragma unroll
+        for (int q = 0; q < DB_WAVES; q++) { a &= red[0][q]; o |= red[1][q]; }
+        if (a != o) {
+            for (int pass = 0; pass < 2; pass++) {
+                const uint32_t* sk = (pass ? key0 : key1) + start; const uint32_t* sv = (pass ? val0 : val1) + start;
+                uint32_t* dk = (pass ? key1 : key0) + start; uint32_t* dv = (pass ? val1 : val0) + start;
+                const int shift = 8 * pass;
+                if (t < 256) cur[t] = 0u;
+                __syncthreads();
+                for (int i = t; i < n; i += DB_THREADS) atomicAdd(&cur[(sk[i] >> shift) & 255u], 1u);
+                __syncthreads();
+                const uint32_t ex = block_excl_scan<DB_WAVES>(t < 256 ? cur[t] : 0u, wsum);
+                if (t < 256) cur[t] = ex;   // (read behind the first barrier of the pass below)
+                for (int c0 = 0; c0 < n; c0 += cap)
+                    bucket_pass<true>(min(cap, n - c0), shift, [&](int i) { return make_uint2(sk[c0 + i], sv[c0 + i]); },
+                                      [&](uint32_t pos, uint2 it) { dk[pos] = it.x; dv[pos] = it.y; }, wcnt, cur, wsum);
+                __threadfence_block();   // (the next pass, and the scan below, read what other waves of this workgroup stored)
+                __syncthreads();
+            }
+        }
+    }
+    uint32_t carry = wbase;
+    for (int c0 = 0; c0 < n; c0 += DB_THREADS * DB_ROUNDS) {
+        uint32_t wv[DB_ROUNDS], sum = 0;
+#pragma unroll
+        for (int j = 0; j < DB_ROUNDS; j++) {
+            const int i = c0 + t * DB_ROUNDS + j;
+            wv[j] = i < n ? tiles[2 * (size_t)val1[start + i]] : 0u;
+            sum += wv[j];
+        }
+        uint32_t all;
+        uint32_t run = carry + block_excl_scan<DB_WAVES>(sum, wsum, &all);
+#pragma unroll
+        for (int j = 0; j < DB_ROUNDS; j++) {
+            const int i = c0 + t * DB_ROUNDS + j;
+            if (i < n) offsets[start + i] = run;
+            run += wv[j];
+        }
+        carry += all;
+        __syncthreads();   // (wsum is free again)
     }
 }
 
@@ -638,6 +912,21 @@ void launch_radix_sort(uint32_t* const key[2], uint32_t* const val[2], int n, co
     uint32_t* gtot = radix_gtot(table, n);  // [passes <= 4, + the weighted pass's slot][groups][256] group totals, zero on entry
     if (n <= (1 << 20)) radix_sort_impl<4>(key, val, n, n_dev, total_bits, bits_per_pass, table, gtot, s, weights);
     else radix_sort_impl<16>(key, val, n, n_dev, total_bits, bits_per_pass, table, gtot, s, weights);
+}
+
+// depth_sort_plan.hpp.  Group totals: the counts in slot 0, the weights in the weighted pass's slot.
+void launch_depth_bucket_sort(uint32_t* const key[2], uint32_t* const val[2], int n, uint32_t* table, int cap, hipStream_t s, const RadixWeights& w) {
+    if (n <= 0) return;
+    constexpr int ITEMS = 4;
+    assert(n <= DEPTH_BUCKET_MAX_P && cap >= DEPTH_BUCKET_CAP_MIN && cap <= DEPTH_BUCKET_CAP);
+    const int nb = (n + BLOCK * ITEMS - 1) / (BLOCK * ITEMS), ng = (nb + GS - 1) / GS;
+    uint32_t* gtot = radix_gtot(table, n);
+    uint32_t* wgtot = gtot + (size_t)RADIX_WGTOT_SLOT * ng * 256;
+    const WeightArgs wa{val[0], wgtot, w};
+    hipLaunchKernelGGL((radix_hist_kernel<ITEMS, true, true>), dim3(nb), dim3(BLOCK), 0, s, key[0], n, (const uint32_t*)nullptr, 16, 255u, table, gtot, wa);
+    hipLaunchKernelGGL((depth_bucket_scatter_kernel<ITEMS>), dim3(nb), dim3(BLOCK), 0, s, key[0], val[0], key[1], val[1], w.offsets, n, 16, table, gtot,
+                       wgtot, ng, w);
+    hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(256), dim3(DB_THREADS), 0, s, key[0], val[0], key[1], val[1], w.offsets, w.tiles, gtot, wgtot, ng, cap);
 }
 
 void launch_emit(int P, const uint32_t* order, const uint32_t* tiles, const uint32_t* offsets, float* rec,
