@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "geom_bwd.hpp"
 #include "workload_history.hpp"
 #include "depth_sort_plan.hpp"
 
@@ -340,6 +341,7 @@ CfgRef cfg_ref(const svgir_params* p) {
 // (measured: cfg3_train, P = 200 k, svgss rows: grad_reduce 85 -> 64 us, geom_bwd 28 -> 24 us against ~10 us for the partition; cfg2,
 // P = 200 k, rgss packed rows: only geom_bwd gains, 31 -> ~25 us: not worth it; cfg5, P = 2 M: 498 -> 345 us and 171 -> 88 us)
 constexpr int kListMinP = 400000, kListMinPRows = 50000;   // (round 5, rgss at P = 200 k with the count folded into seg_build: geom_bwd -7 us, scatter launch +5, seg_build +2: no gain)
+// (below the thresholds geom_bwd applies the rule without a list: its waves test the weights and compact the blended surfels themselves)
 
 // Does a composite launch with `nonempty` waves of work fill the machine several times over?  (256 CUs x 8-11 resident waves: from ~4
 // rounds on; SVGIR_FWD_FILL = 0 / 1 forces the low- / high-occupancy variant)
@@ -1051,6 +1053,9 @@ struct BackwardCall {
     int geom_backward() {
         GeomBwdArgs ga;
         ga.list = R > 0 ? blended : nullptr; ga.list_count = blended_n;
+        // (no list: the kernel tests the weights itself.  The gradient tensors it leaves alone were cleared in front of it in every mode:
+        // by the composite's waves, by the side-stream clear joined in composite(), or -- run-time widths -- on this stream in clears();
+        // R == 0: the preprocess zeroed every weight)
         camera_args(ga, p);
         ga.cov3D = p->cov3D_precomp ? p->cov3D_precomp : G.cov3D; ga.radii = radii; ga.clamped = G.clamped; ga.svgss = svgss;
         ga.dL_dmean2D = g->dL_dmeans2D; ga.dL_dconic = g->dL_dconic; ga.dL_dcolor = g->dL_dcolors; ga.dL_dnormal = g->dL_dnormal;
@@ -1060,7 +1065,7 @@ struct BackwardCall {
         ga.dL_dmean3D = g->dL_dmeans3D; ga.dL_dcov3D = g->dL_dcov3D; ga.dL_dsh = g->dL_dsh; ga.dL_dscale = g->dL_dscales;
         ga.dL_drot = g->dL_drotations; ga.dL_dviewmat = g->dL_dviewmat; ga.dL_dprojmat = g->dL_dprojmat; ga.dL_dcampos = g->dL_dcampos;
         if (ga.scales && !ga.rotations) return fail(SVGIR_ERR_INVALID, "rotations missing");
-        launch_geom_bwd(ga, s);
+        launch_geom_bwd_blended(ga, g->out_weights, s);
         stage_mark(tm, "geom_bwd");
         hipError_t e = p->debug ? hipStreamSynchronize(s) : hipSuccess;
         if (e == hipSuccess) e = hipGetLastError();

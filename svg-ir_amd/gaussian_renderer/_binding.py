@@ -110,7 +110,8 @@ def carve_gradients(dev, shapes, P, shade_grads=None):
 def fill_grads(dev, upstream, grads, gblob, out_weights):
     """The svgir_grads of one backward call from {field: upstream gradient} and {field: gradient tensor}, and the keep-alive list.
     `out_weights`: the forward's weights [P,1] or None -- with them the per-Gaussian kernels behind the composite walk the blended
-    Gaussians only (all others have zero gradients); worth it from a few hundred thousand surfels on."""
+    Gaussians only (all others have zero gradients): through a list from a few hundred thousand surfels on, below that by a test of
+    the weight inside the kernel."""
     g = N.Grads()
     keep = []
     for name, t in upstream.items():

@@ -62,7 +62,7 @@ class _CBinding:
                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                      dL_dout_normal, dL_dout_opacity, dL_dout_depth, dL_dout_feature, sh, degree,
                                      campos, geomBuffer, R, binningBuffer, imageBuffer, backward_geometry, debug, *, out_weights=None):
-        """`out_weights` (extension, keyword only): the forward's weights [P,1] (_binding.fill_grads; here from ~0.4 M surfels on)."""
+        """`out_weights` (extension, keyword only): the forward's weights [P,1] (_binding.fill_grads: the per-Gaussian backward then processes the blended surfels only)."""
         dev, P, S, M = means3D.device, means3D.size(0), B.width(features), B.sh_count(sh)
         upstream = dict(dL_dout_color=dL_dout_color, dL_dout_normal=dL_dout_normal, dL_dout_depth=dL_dout_depth,
                         dL_dout_opacity=dL_dout_opacity, dL_dout_feature=dL_dout_feature)
