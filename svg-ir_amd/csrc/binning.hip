@@ -564,34 +564,50 @@ __global__ void __launch_bounds__(DB_THREADS) depth_bucket_sort_kernel(uint32_t*
 
 // ---- single-pass tile sort (T <= 4096 tiles) ----------------------------------------------------------------------
 // The tile id has <= 12 bits at 800 x 800 and below: instead of two 6-bit radix passes (four launches) + a ranges kernel, ONE stable
-// counting sort over the whole id -- (1) per-workgroup histograms of TS12_KEYS keys over the tile ids (LDS atomics), (2) per tile
+// counting sort over the whole id -- (1) per-workgroup histograms of TS12K keys over the tile ids (LDS atomics), (2) per tile
 // the exclusive prefix over the workgroups and the tile's total, (3) scatter: every workgroup scans the totals itself (tile bases = the
 // tiles' RANGES: workgroup 0 writes them out, identifyTileRanges for free), adds its row of prefixes, ranks its keys stably (wave-level
-// matching on the 12 bits against wave-private 16-bit LDS counters) and writes.  Rows hold nbins = T rounded up to 256 counters.
-__global__ void __launch_bounds__(BLOCK) ts12_hist_kernel(const uint32_t* __restrict__ keys, int n_cap, const uint32_t* __restrict__ n_dev,
+// matching on the 12 bits against wave-private 16-bit LDS counters) and writes the values -- not the sorted tile ids: nothing reads them.
+// Rows hold nbins = T rounded up to the workgroup size counters.
+// A workgroup = 512 threads and 4096 keys: half the table rows of 256 x 2048 (cfg2: 165 rows of 2560 counters; column scan 7.3 -> 5.2 us,
+// histogram 5.2 -> 5.0, scatter unchanged: profiles/tile_bin_ab.txt); -DTS12_THREADS_V=256 builds the smaller one for A/B runs.
+// The launches are sized by an instance CAPACITY (api.hip: a speculative one lies 12.5 % above the count): every kernel bounds its work
+// by the key blocks of the count it reads on the device -- no histogram row for a block without keys, the column scan walks the written
+// rows only, a scatter workgroup without keys returns (workgroup 0 still writes every range).
+#ifndef TS12_THREADS_V
+#define TS12_THREADS_V 512
+#endif
+constexpr int TS12T = TS12_THREADS_V, TS12W = TS12T / 64, TS12K = 8 * TS12T;   // threads, waves and keys of a workgroup
+static_assert(TS12K >= TS12_KEYS && TS12_BINS % TS12T == 0, "common.hpp tile12_table_words sizes the table for rows of TS12_KEYS keys");
+__host__ __device__ constexpr int ts12_blocks(int n) { return (n + TS12K - 1) / TS12K; }   // key blocks that hold keys
+__global__ void __launch_bounds__(TS12T) ts12_hist_kernel(const uint32_t* __restrict__ keys, int n_cap, const uint32_t* __restrict__ n_dev,
                                                           uint32_t* __restrict__ table, int nbins) {
     __shared__ uint32_t hist[TS12_BINS];
     const int n = n_dev ? (int)min((uint32_t)n_cap, n_dev[0]) : n_cap;
+    if ((int)blockIdx.x >= ts12_blocks(n)) return;   // (a launch sized by a capacity: no row for a block without keys)
     const int t = threadIdx.x;
-    for (int i = t; i < nbins; i += BLOCK) hist[i] = 0u;
+    for (int i = t; i < nbins; i += TS12T) hist[i] = 0u;
     __syncthreads();
-    const int base = blockIdx.x * TS12_KEYS;
-    uint32_t k[TS12_KEYS / BLOCK];
+    const int base = blockIdx.x * TS12K;
+    uint32_t k[TS12K / TS12T];
 #pragma unroll
-    for (int i = 0; i < TS12_KEYS / BLOCK; i++) k[i] = keys[max(0, min(base + i * BLOCK + t, n - 1))];
+    for (int i = 0; i < TS12K / TS12T; i++) k[i] = keys[max(0, min(base + i * TS12T + t, n - 1))];
 #pragma unroll
-    for (int i = 0; i < TS12_KEYS / BLOCK; i++)
-        if (base + i * BLOCK + t < n) atomicAdd(&hist[k[i] & (TS12_BINS - 1)], 1u);
+    for (int i = 0; i < TS12K / TS12T; i++)
+        if (base + i * TS12T + t < n) atomicAdd(&hist[k[i] & (TS12_BINS - 1)], 1u);
     __syncthreads();
     uint32_t* row = table + (size_t)blockIdx.x * nbins;
-    for (int i = t; i < nbins; i += BLOCK) row[i] = hist[i];
+    for (int i = t; i < nbins; i += TS12T) row[i] = hist[i];
 }
 
 // per tile id: exclusive prefix of the workgroups' counts (in place) and the total.  A workgroup = 16 tile ids x 16 row segments: a thread
 // first sums its segment (loads only: all in flight together), the 16 segment sums of a tile meet in LDS, then the thread rewrites its
 // segment as running prefixes -- two short memory round trips instead of one per row.
-__global__ void __launch_bounds__(BLOCK) ts12_colscan_kernel(uint32_t* __restrict__ table, int nb, uint32_t* __restrict__ totals, int nbins) {
+__global__ void __launch_bounds__(BLOCK) ts12_colscan_kernel(uint32_t* __restrict__ table, int nb_cap, int n_cap, const uint32_t* __restrict__ n_dev,
+                                                             uint32_t* __restrict__ totals, int nbins) {
     __shared__ uint32_t psum[16][17];
+    // (the rows that were written: the key blocks of the count; the totals still sit behind the nb_cap rows of the launch)
+    const int nb = n_dev ? (int)min((uint32_t)nb_cap, (uint32_t)ts12_blocks((int)min((uint32_t)n_cap, n_dev[0]))) : nb_cap;
     const int col = threadIdx.x & 15, seg = threadIdx.x >> 4;
     const int d = blockIdx.x * 16 + col;
     const int rps = (nb + 15) / 16, r0 = min(nb, seg * rps), r1 = min(nb, r0 + rps);
@@ -623,19 +639,21 @@ __global__ void __launch_bounds__(BLOCK) ts12_colscan_kernel(uint32_t* __restric
     for (; r < r1; r++) { const uint32_t c = colp[(size_t)r * nbins]; colp[(size_t)r * nbins] = run; run += c; }
 }
 
-__global__ void __launch_bounds__(BLOCK) ts12_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
-                                                             uint32_t* __restrict__ kout, uint32_t* __restrict__ vout, int n_cap,
+__global__ void __launch_bounds__(TS12T) ts12_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
+                                                             uint32_t* __restrict__ vout, int n_cap,
                                                              const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ table,
                                                              const uint32_t* __restrict__ totals, uint32_t* __restrict__ ranges, int T, int nbins) {
     __shared__ uint32_t cur[TS12_BINS];          // global position of this workgroup's first key of every tile
-    __shared__ uint16_t wcnt[4][TS12_BINS];      // per-wave tile counters (a workgroup holds 2048 keys)
-    __shared__ uint32_t wtot[4];
-    constexpr int PERMAX = TS12_BINS / BLOCK;    // up to 16 consecutive tiles per thread in the scan
-    constexpr int ROUNDS = TS12_KEYS / BLOCK;    // 8 rounds of 64 keys per wave
-    const int per = nbins / BLOCK;               // (nbins is a multiple of 256)
+    __shared__ uint16_t wcnt[TS12W][TS12_BINS];  // per-wave tile counters (a wave holds 512 keys)
+    uint32_t* wtot = cur;                        // (scan scratch in the cursors' first words: with it two workgroups are exactly a CU's 160 KiB)
+    constexpr int PERMAX = TS12_BINS / TS12T;    // up to 8 consecutive tiles per thread in the scan
+    constexpr int ROUNDS = TS12K / TS12T;        // 8 rounds of 64 keys per wave
+    const int per = nbins / TS12T;               // (nbins is a multiple of the workgroup size)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int n = n_dev ? (int)min((uint32_t)n_cap, n_dev[0]) : n_cap;
-    const int base = blockIdx.x * TS12_KEYS + wave * (64 * ROUNDS);   // wave w owns the w-th quarter, round-major = key order
+    // (no keys: nothing to place; workgroup 0 still writes every range, all of them (0, 0) when the view has no instance)
+    if (blockIdx.x != 0 && (int)blockIdx.x >= ts12_blocks(n)) return;
+    const int base = blockIdx.x * TS12K + wave * (64 * ROUNDS);   // wave w owns the w-th run of 512 keys, round-major = key order
     const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     uint32_t ks[ROUNDS], vs[ROUNDS];
     uint16_t rk[ROUNDS];
@@ -657,9 +675,10 @@ __global__ void __launch_bounds__(BLOCK) ts12_scatter_kernel(const uint32_t* __r
 #pragma unroll
     for (int j = 0; j < PERMAX; j++) sum += tot[j];
 #pragma unroll
-    for (int w = 0; w < 4; w++)
-        for (int i = t; i < nbins / 2; i += BLOCK) reinterpret_cast<uint32_t*>(&wcnt[w][0])[i] = 0u;
-    uint32_t run = block_excl_scan<4>(sum, wtot);   // (its barrier also: the wave counters are zero)
+    for (int w = 0; w < TS12W; w++)
+        for (int i = t; i < nbins / 2; i += TS12T) reinterpret_cast<uint32_t*>(&wcnt[w][0])[i] = 0u;
+    uint32_t run = block_excl_scan<TS12W>(sum, wtot);   // (its barrier also: the wave counters are zero)
+    __syncthreads();   // (every wave has read the scan scratch: the cursors may be written)
 #pragma unroll
     for (int j = 0; j < PERMAX; j++) {
         if (j < per) {
@@ -689,11 +708,10 @@ __global__ void __launch_bounds__(BLOCK) ts12_scatter_kernel(const uint32_t* __r
         if (base + c * 64 + lane < n) {
             const uint32_t d = ks[c] & (TS12_BINS - 1);
             uint32_t pos = cur[d] + rk[c];
-            if (wave > 0) pos += wcnt[0][d];
-            if (wave > 1) pos += wcnt[1][d];
-            if (wave > 2) pos += wcnt[2][d];
-            kout[pos] = ks[c];
-            vout[pos] = vs[c];
+#pragma unroll
+            for (int w = 0; w < TS12W - 1; w++)
+                if (wave > w) pos += wcnt[w][d];
+            vout[pos] = vs[c];   // (the sorted tile ids are not written: nothing reads them, the ranges come from the totals)
         }
     }
 }
@@ -940,12 +958,12 @@ void launch_emit(int P, const uint32_t* order, const uint32_t* tiles, const uint
 void launch_tile_sort12(uint32_t* const key[2], uint32_t* const val[2], int n, const uint32_t* n_dev, uint32_t* table, uint32_t* ranges, int T,
                         hipStream_t s) {
     if (n <= 0) return;
-    const int nb = (n + TS12_KEYS - 1) / TS12_KEYS;
-    const int nbins = (T + BLOCK - 1) / BLOCK * BLOCK;   // (<= TS12_BINS: tile_sort_plan)
+    const int nb = ts12_blocks(n);
+    const int nbins = (T + TS12T - 1) / TS12T * TS12T;   // (<= TS12_BINS: tile_sort_plan)
     uint32_t* totals = table + (size_t)nb * nbins;
-    hipLaunchKernelGGL(ts12_hist_kernel, dim3(nb), dim3(BLOCK), 0, s, key[0], n, n_dev, table, nbins);
-    hipLaunchKernelGGL(ts12_colscan_kernel, dim3(nbins / 16), dim3(BLOCK), 0, s, table, nb, totals, nbins);
-    hipLaunchKernelGGL(ts12_scatter_kernel, dim3(nb), dim3(BLOCK), 0, s, key[0], val[0], key[1], val[1], n, n_dev, table, totals, ranges, T, nbins);
+    hipLaunchKernelGGL(ts12_hist_kernel, dim3(nb), dim3(TS12T), 0, s, key[0], n, n_dev, table, nbins);
+    hipLaunchKernelGGL(ts12_colscan_kernel, dim3(nbins / 16), dim3(BLOCK), 0, s, table, nb, n, n_dev, totals, nbins);
+    hipLaunchKernelGGL(ts12_scatter_kernel, dim3(nb), dim3(TS12T), 0, s, key[0], val[0], val[1], n, n_dev, table, totals, ranges, T, nbins);
 }
 
 // `ranges` must already be zero (launch_emit clears it)
