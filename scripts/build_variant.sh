@@ -10,7 +10,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/build/variants/$NAME
 mkdir -p "$OUT"
 FLAGS=$(make -s -C "$ROOT/svg-ir_amd/csrc" print-hipflags)
-ALL="api preprocess binning render_fwd render_bwd render_bwd_plain render_generic geom_bwd grad_reduce image_ops shade subset epilogue loss optim bvh pbgi"
+ALL=$(make -s -C "$ROOT/svg-ir_amd/csrc" print-units)   # every translation unit of the product (csrc/Makefile SRCS)
 pids=()
 OBJS=()
 for f in $ALL; do

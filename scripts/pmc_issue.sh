@@ -2,6 +2,9 @@
 # Instruction-issue counters of the composite / shading kernels (one --pmc pass, kernel-trace only) -> what bench.py reports as
 # roofline.issue_frac.  usage: scripts/pmc_issue.sh <workload> <tag>   -> gpurun_out/<tag>_issue.json
 set -u
+set -e   # a counter pass that fails, or runs into its time limit, ends the script
+# the profiler run under its own time limit (PMC_TIMEOUT seconds, default 600)
+rocprofv3() { timeout -k 10 "${PMC_TIMEOUT:-600}" "$(type -P rocprofv3)" "$@"; }
 export TMPDIR=/tmp
 R=$PWD
 W=${1:-cfg2}

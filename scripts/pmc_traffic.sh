@@ -2,6 +2,9 @@
 # HBM traffic of the composite kernels from the L2 memory-side request counters (separate --pmc passes, kernel-trace
 # only).  usage: scripts/pmc_traffic.sh <workload> <tag>   -> gpurun_out/<tag>_traffic.json
 set -u
+set -e   # a counter pass that fails, or runs into its time limit, ends the script
+# every profiler run under its own time limit (PMC_TIMEOUT seconds, default 600)
+rocprofv3() { timeout -k 10 "${PMC_TIMEOUT:-600}" "$(type -P rocprofv3)" "$@"; }
 export TMPDIR=/tmp
 R=$PWD
 W=${1:-cfg2}

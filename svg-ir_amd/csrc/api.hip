@@ -973,7 +973,7 @@ struct BackwardCall {
     // never pays for it -- together with the scratch clear; then the partition of the blended surfels
     int seg_build() {
         void* sc_clear = rows ? (void*)ba.row_of : (void*)ba.grad_rows;   // (null: run-time-width kernels, no scratch)
-        const size_t sc_bytes = rows ? grad_rowof_bytes(caps.cap_R) : align_up((size_t)p->P * grad_row_geom(p->S, ba.VS).RS * 4);
+        const size_t sc_bytes = rows ? grad_rowof_bytes(caps.cap_R) : align_up((size_t)p->P * packed_row_geom(p->S).RS * 4);
         bool use_list = false;
         if (R > 0) {
             // (fused shading: the same launch builds the tables and zeroes the env-gradient accumulator of the shading backward below)
@@ -1117,7 +1117,7 @@ size_t svgir_backward_scratch_bytes_for(int32_t variant, int32_t P, size_t binni
     if (!render_specialised(S, variant == SVGIR_SVGSS ? VS : 0, variant == SVGIR_SVGSS))
         return 256;   // run-time-width kernels accumulate straight into the dL_d* tensors: no scratch (a token size, never touched)
     if (variant != SVGIR_SVGSS || VS == 0)   // one packed gradient row per Gaussian
-        return align_up((size_t)(P > 0 ? P : 1) * grad_row_geom(S, 0).RS * 4);
+        return align_up((size_t)(P > 0 ? P : 1) * packed_row_geom(S).RS * 4);
     // the binning blob's instance capacity (bin_capacity); and one gradient row per (sub-tile, instance) pair that survived the cull of
     // THIS view when its count is known, else four per instance
     ViewCounts vc;

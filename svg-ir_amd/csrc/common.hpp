@@ -234,6 +234,22 @@ inline GradRowGeom grad_row_geom(int S, int VS) {
     g.NC0 = 7 + S; g.P4 = (g.NC0 + 3) / 4 * 4; g.VS = VS; g.GEO = g.P4 + VS; g.RS = (g.GEO + 6 + 3) / 4 * 4;
     return g;
 }
+// Packed rows (the composites WITHOUT vfeatures, render_bwd_plain.hip): ONE row per Gaussian, accumulated with float atomics and
+// unpacked by geom_bwd.hip.  Layout (floats): [0, NC0) colour3, normal3 (x10), depth, features S | pad to 4 | [GEO, GEO + 6) mean2D.xy,
+// conic.xyz, opacity | pad to 4 -- 80 bytes at S = 5, so rows start at bytes 0 / 16 / 32 / 48 of a 64-byte segment and a wave's two
+// pieces of a row (channel columns, geometric values) touch 2.75 segments on average.
+// -DPACKED_ROW_ALIGNED=1 builds the layout that was measured against it (profiles/bwd_rows_ab.txt): rows on a 128-byte
+// stride, channel columns at [0, NC0), geometric values at [16, 22), each piece inside one segment (widths whose whole row fits 16
+// floats, S <= 1, keep their 64-byte row).  Fewer atomic requests, but 1.6 times the bytes to clear and to unpack: 1 - 4 us SLOWER
+// per cfg2 step, not the default.
+#ifndef PACKED_ROW_ALIGNED
+#define PACKED_ROW_ALIGNED 0
+#endif
+struct PackedRowGeom { int NC0, GEO, RS; };   // floats: channel columns [0, NC0), geometric values [GEO, GEO + 6), row stride RS
+constexpr PackedRowGeom packed_row_geom(int S) {
+    const int NC0 = 7 + S, P4 = (NC0 + 3) / 4 * 4, RC = (P4 + 6 + 3) / 4 * 4;
+    return (!PACKED_ROW_ALIGNED || RC <= 16 || P4 > 16) ? PackedRowGeom{NC0, P4, RC} : PackedRowGeom{NC0, 16, 32};
+}
 inline size_t grad_rowof_bytes(int cap) { return align_up((size_t)4 * cap * 4); }
 inline size_t grad_scratch_bytes(int cap, size_t rows, int S, int VS) {   // reverse map + `rows` gradient rows
     return grad_rowof_bytes(cap) + align_up(rows * grad_row_geom(S, VS).RS * 4);
@@ -459,7 +475,7 @@ struct GeomBwdArgs {
     const int32_t* radii; const uint32_t* clamped;
     float scale_modifier, tanx, tany, focal_x, focal_y;
     CfgRef cfg; int svgss;
-    // composite gradients: the caller's tensors; when `packed` is set (one GradRowGeom(S, 0) row per Gaussian, written by
+    // composite gradients: the caller's tensors; when `packed` is set (one packed_row_geom(S) row per Gaussian, written by
     // the backward composite) the kernel first unpacks the Gaussian's row into them
     float *dL_dmean2D, *dL_dconic, *dL_dcolor, *dL_dnormal, *dL_ddepth, *dL_dopacity, *dL_dfeature;
     const float* packed; int S;

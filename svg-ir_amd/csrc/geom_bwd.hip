@@ -138,14 +138,14 @@ __global__ void __launch_bounds__(GB_BLOCK) __attribute__((amdgpu_waves_per_eu(C
 
         // ---------------- every input of this Gaussian ----------------
         if (a.packed) {
-            // rgss: the backward composite accumulated this Gaussian's gradients in one packed row (common.hpp GradRowGeom:
+            // rgss: the backward composite accumulated this Gaussian's gradients in one packed row (common.hpp packed_row_geom:
             // colour3, normal3, depth, feature S | pad | mean2D.xy, conic.xyz, opacity); it is unpacked into the caller's tensors below
-            const int P4 = (7 + a.S + 3) / 4 * 4, RS = (P4 + 6 + 3) / 4 * 4;
-            const float* row = a.packed + (size_t)idx * RS;
+            const PackedRowGeom rg = packed_row_geom(a.S);
+            const float* row = a.packed + (size_t)idx * rg.RS;
             // (rows are 16-byte aligned multiples of four floats: the head {colour3, normal3, depth, .} and the tail {mean2D.xy, conic.xyz,
             // opacity, . .} are four 128-bit loads -- the lanes of a wave are a row apart, so it is the number of instructions that costs)
             const float4 h0 = reinterpret_cast<const float4*>(row)[0], h1 = reinterpret_cast<const float4*>(row)[1];
-            const float4 t0 = reinterpret_cast<const float4*>(row + P4)[0], t1 = reinterpret_cast<const float4*>(row + P4)[1];
+            const float4 t0 = reinterpret_cast<const float4*>(row + rg.GEO)[0], t1 = reinterpret_cast<const float4*>(row + rg.GEO)[1];
             in_color[0] = h0.x; in_color[1] = h0.y; in_color[2] = h0.z; in_normal[0] = h0.w; in_normal[1] = h1.x; in_normal[2] = h1.y;
             in_depth = h1.z;
             in_m2d[0] = t0.x; in_m2d[1] = t0.y; in_conic[0] = t0.z; in_conic[1] = t0.w; in_conic[2] = t1.x;
@@ -203,8 +203,7 @@ __global__ void __launch_bounds__(GB_BLOCK) __attribute__((amdgpu_waves_per_eu(C
             }
         }
         if (a.packed) {   // (run-time feature width: row -> tensor, behind the loads above)
-            const int P4 = (7 + a.S + 3) / 4 * 4, RS = (P4 + 6 + 3) / 4 * 4;
-            const float* row = a.packed + (size_t)idx * RS;
+            const float* row = a.packed + (size_t)idx * packed_row_geom(a.S).RS;
             for (int c = 0; c < a.S; c++) a.dL_dfeature[(size_t)idx * a.S + c] = row[7 + c];
         }
         float dmean[3];

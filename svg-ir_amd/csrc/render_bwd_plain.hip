@@ -11,13 +11,14 @@
 //     candidate ahead) into SGPRs and enter the per-pixel math as scalar operands -- no LDS staging buffer, no broadcast
 //     ds_reads, no VGPRs for uniform data;
 //   * all per-Gaussian sums over the 64 pixels run on the matrix pipe.  The blend weight w and ONE more per-(pixel,
-//     candidate) scalar v = G dL_dalpha go to a 16-row LDS panel (8 candidates x {w, v}); rows w x G[pixel][colour3 normal3
-//     depth feature S] give the channel gradients, rows v x Mom[pixel][1 px py px^2 px py py^2] give six pixel moments from
+//     candidate) scalar v = G dL_dalpha go to an LDS panel (8 candidates per block); the w rows of TWO consecutive blocks x
+//     G[pixel][colour3 normal3 depth feature S] give the channel gradients of 16 candidates in one 16-row contraction (3 MFMAs per
+//     candidate in all, not 4), rows v x Mom[pixel][1 px py px^2 px py py^2] give per block six pixel moments from
 //     which the six geometric gradients (mean2D.xy, conic.xyz, opacity) follow per candidate:
 //         sum_p v dx = X M0 - M1,  sum_p v dx^2 = X (X M0 - 2 M1) + M3,  ...   (X, Y, px, py relative to the sub-tile centre)
 //     with dL_ddist = v (-0.5 opacity) -- v_mfma_f32_16x16x4_f32, exact fp32 products;
 //   * the un-weighted depth-differencing term (quirk Q5) needs sum_p [pixel blends] (-gD): one DPP wave reduction per candidate;
-//   * results: float atomics into ONE packed gradient row per Gaussian (common.hpp GradRowGeom), unpacked by geom_bwd.hip.
+//   * results: float atomics into ONE packed gradient row per Gaussian (common.hpp packed_row_geom), unpacked by geom_bwd.hip.
 #include <algorithm>
 
 #include "common.hpp"
@@ -37,6 +38,9 @@ typedef const __attribute__((address_space(4))) uint32_t cuint;
 #ifndef BWDP_WPE
 #define BWDP_WPE 4
 #endif
+#ifndef BWDP_MFMA_ACC
+#define BWDP_MFMA_ACC 1   // accumulators per 16-long MFMA chain (2: even and odd steps apart, summed at the end -- profiles/bwd_rows_ab.txt)
+#endif
 
 template <int S>
 struct PlainGeom {
@@ -44,7 +48,7 @@ struct PlainGeom {
     static constexpr int NC0 = 7 + S;            // colour3, normal3, depth, feature S
     static constexpr int GROW = NC0 + 1;
     static constexpr int PS = 68;                // panel row stride (floats)
-    static constexpr int PROWS = 24;             // panel rows: 8 blend weights w | 8 v | 8 u (Q5 term)
+    static constexpr int PROWS = 32;             // panel rows: 2 x 8 blend weights w (a PAIR of blocks) | 8 v | 8 u (Q5 term) of the current block
     static constexpr size_t off_m = (size_t)PROWS * PS * 4;            // moments + Q5 sums [SB][8]
     static constexpr size_t off_c = off_m + (size_t)SB * 8 * 4;        // per-candidate constants of the block [3][SB] float4 (LDS-DMA target)
     static constexpr size_t off_q = off_c + (size_t)3 * SB * 16;       // the segment's {gid, slot} entries, deepest first
@@ -59,9 +63,9 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
     using PG = PlainGeom<S>;
     constexpr int SB = PG::SB, NC0 = PG::NC0, GROW = PG::GROW, PS = PG::PS;
     constexpr int SS = S > 0 ? S : 1;
-    constexpr int P4 = (NC0 + 3) / 4 * 4, GEO = P4, RS = (GEO + 6 + 3) / 4 * 4;   // common.hpp GradRowGeom (VS = 0)
+    constexpr int GEO = packed_row_geom(S).GEO, RS = packed_row_geom(S).RS;   // common.hpp: the packed row of a Gaussian
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sP = reinterpret_cast<float*>(smem);                    // [24][PS] rows 0..7: blend weights, 8..15: v, 16..23: u
+    float* sP = reinterpret_cast<float*>(smem);                    // [32][PS] rows 0..15: blend weights of two blocks, 16..23: v, 24..31: u
     float* sG = sP;                                                // [64][GROW] upstream gradients (transposition only)
     float* sM = reinterpret_cast<float*>(smem + PG::off_m);        // [SB][8] six moments, Q5 sum, pad
     float4* sC = reinterpret_cast<float4*>(smem + PG::off_c);      // [3][SB] record float4 #0, #1, #3 of the block's candidates
@@ -245,6 +249,9 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
         for (int kk = 0; kk < 16; kk++) Bp[kk] = colB < NC0 ? gB[kk * GROW] : 0.f;
     }
     wave_lds_sync();   // sG aliases the panel
+    // (the weight rows of a pair's second block enter the channel contraction also where that block never runs -- masked there, finite here)
+#pragma unroll
+    for (int k = 0; k < SB; k++) sP[(SB + k) * PS + lane] = 0.f;
 
     // The segment's list entries, deepest first (the replay walks back to front): LDS copy for the per-lane consumers
     // (atomics of phase B); the per-candidate math reads them with scalar loads.
@@ -286,7 +293,13 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
     prefetch_consts(cstart);
     DEV_TRACE_MARK(0);   // segment setup
     dev_items++; dev_cands += (unsigned)nent;
+    // Blocks are taken in PAIRS counted from cstart: the blend weights of both blocks fill the 16 rows of ONE channel contraction
+    // (w_a | w_b) x G behind the pair's second block -- or behind the segment's last block, then with the rows of the block that did
+    // not run masked.  Moments and geometric gradients stay per block.
+    uint32_t live16 = 0;   // live bits of the pair: first block in bits 0..7, second in 8..15 (wave-uniform)
     for (int c0 = cstart; c0 < nent; c0 += SB) {
+        const int par = ((c0 - cstart) / SB) & 1;   // (uniform) position of the block in its pair
+        float* sPw = sP + par * (SB * PS) + lane;   // this block's weight rows
         uint32_t live = 0;  // bit k set: candidate c0+k has at least one blending pixel (wave-uniform)
         // ---------------- phase A: lane = pixel, one candidate at a time, attributes in SGPRs ----------------
         // (scalar loads and LDS stores share one completion counter: the panel stores of candidate k are issued right AFTER the
@@ -298,7 +311,7 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
             en1 = fetch_entry(c0 + k + 2);
             const float dx = cur.X - pxf, dy = cur.Y - pyf;
             if (k > 0) {
-                sP[(k - 1) * PS + lane] = hw; sP[(SB + k - 1) * PS + lane] = hv; sP[(2 * SB + k - 1) * PS + lane] = hu;
+                sPw[(k - 1) * PS] = hw; sP[(2 * SB + k - 1) * PS + lane] = hv; sP[(3 * SB + k - 1) * PS + lane] = hu;
             }
             const float pw = pair_power(cur.cxx, cur.cxy, cur.cyy, dx, dy);
             const float Gs = exp_nonpos(pw);
@@ -328,11 +341,11 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
             live |= (__builtin_amdgcn_ballot_w64(pre) != 0ull ? 1u : 0u) << k;
             cur = nxt;
         }
-        sP[(SB - 1) * PS + lane] = hw; sP[(2 * SB - 1) * PS + lane] = hv; sP[(3 * SB - 1) * PS + lane] = hu;
+        sPw[(SB - 1) * PS] = hw; sP[(3 * SB - 1) * PS + lane] = hv; sP[(4 * SB - 1) * PS + lane] = hu;
         DEV_TRACE_MARK(2);   // phase A
         if (live != 0) {     // uniform
         wave_lds_sync();          // panel rows visible
-        // ---------------- phase B: panel x [G | Mom] on the matrix pipe ----------------
+        // ---------------- phase B: panel x Mom on the matrix pipe ----------------
         // D layout: lane l, register r -> row 4 (l >> 4) + r, column l & 15
         // (lane-derived addresses are re-derived here every block: hoisted out of the loop they would hold ~20 VGPRs across phase A)
         int lB = lane;
@@ -340,17 +353,20 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
         const int colB = lB & 15, grpB = lB >> 4;
         f32x4 accM = {0.f, 0.f, 0.f, 0.f};
         {   // rows (v | u) x Mom: lanes 0..31, columns 0..5 = the six pixel moments of v; lanes 32..63, column 0 = sum of u
-            const float4* ap = reinterpret_cast<const float4*>(sP + (SB + colB) * PS + 16 * grpB);
+            const float4* ap = reinterpret_cast<const float4*>(sP + (2 * SB + colB) * PS + 16 * grpB);
             const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3];
             const float av[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w,
                                   a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
             float c0l = cx0;
             asm volatile("" : "+v"(c0l));   // (opaque: the 16 operand values are not hoisted out of the block loop into 16 VGPRs)
+            f32x4 accM2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 16; kk++) {
                 const float mx = (float)(kk & 7) - 3.5f;
-                accM = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], (c0l + mx * (cx1 + mx * cx2)) * momy[kk >> 3], accM, 0, 0, 0);
+                f32x4& acc = (BWDP_MFMA_ACC == 2 && (kk & 1)) ? accM2 : accM;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], (c0l + mx * (cx1 + mx * cx2)) * momy[kk >> 3], acc, 0, 0, 0);
             }
+            if (BWDP_MFMA_ACC == 2) accM += accM2;
         }
         if (grpB < 2) {
             if (colB < 6) {
@@ -360,15 +376,6 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
         } else if (colB == 0) {
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) sM[(4 * (grpB - 2) + rr) * 8 + 6] = accM[rr];
-        }
-        f32x4 accP = {0.f, 0.f, 0.f, 0.f};
-        {   // rows (w | v) x G: lanes 0..31 = the channel gradients of the 8 candidates
-            const float4* ap = reinterpret_cast<const float4*>(sP + colB * PS + 16 * grpB);
-            const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3];
-            const float av[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w,
-                                  a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) accP = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], Bp[kk], accP, 0, 0, 0);
         }
         __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the block's constants have landed in LDS (issued a whole block ago)
         wave_lds_sync();
@@ -395,15 +402,37 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
                 if (ge != 0.f) atomic_add_f32(a.grad_rows + (uint32_t)(sQ[c0 + cq].x * (uint32_t)RS + (uint32_t)(GEO + jq)), ge);
             }
         }
-        if (grpB < 2) {
+        wave_lds_sync();   // moments / constants / panel consumed before they are overwritten
+        }
+        live16 = par ? (live16 | (live << SB)) : live;
+        if ((par || c0 + SB >= nent) && live16 != 0) {   // (uniform) the pair is complete, or the segment ends on its first block
+            wave_lds_sync();          // weight rows visible
+            // ---------------- rows (w_a | w_b) x G: the channel gradients of the pair's 16 candidates, row = 8 (block of the pair) + k ----------------
+            int lP = lane;
+            asm volatile("" : "+v"(lP));
+            const int colP = lP & 15, grpP = lP >> 4;
+            f32x4 accP = {0.f, 0.f, 0.f, 0.f};
+            {
+                const float4* ap = reinterpret_cast<const float4*>(sP + colP * PS + 16 * grpP);
+                const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3];
+                const float av[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w,
+                                      a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
+                f32x4 accP2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    f32x4& acc = (BWDP_MFMA_ACC == 2 && (kk & 1)) ? accP2 : accP;
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], Bp[kk], acc, 0, 0, 0);
+                }
+                if (BWDP_MFMA_ACC == 2) accP += accP2;
+            }
+            const int cp0 = c0 - par * SB;   // first candidate of the pair
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) {
-                const int cB = 4 * grpB + rr;
-                const bool mine = ((live >> cB) & 1u) && colB < NC0 && accP[rr] != 0.f;
-                if (mine) atomic_add_f32(a.grad_rows + (uint32_t)(sQ[c0 + cB].x * (uint32_t)RS + (uint32_t)colB), accP[rr]);
+                const int cB = 4 * grpP + rr;   // (rows of a block that did not run, or without a blending pixel, are masked: never read as results)
+                const bool mine = ((live16 >> cB) & 1u) && colP < NC0 && accP[rr] != 0.f;
+                if (mine) atomic_add_f32(a.grad_rows + (uint32_t)(sQ[cp0 + cB].x * (uint32_t)RS + (uint32_t)colP), accP[rr]);
             }
-        }
-        wave_lds_sync();   // moments / constants / panel consumed before they are overwritten
+            wave_lds_sync();   // weight rows consumed before the next pair overwrites them
         }
         if (c0 + SB < nent) prefetch_consts(c0 + SB);
         DEV_TRACE_MARK(1);   // geometric epilogue
