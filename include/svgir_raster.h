@@ -524,6 +524,63 @@ int svgir_smooth_loss_forward(int32_t W, int32_t H, int32_t n_terms, const svgir
 int svgir_smooth_loss_backward(int32_t W, int32_t H, int32_t n_terms, const svgir_smooth_term* terms, const double* stats, const float* g,
                                void* stream);
 
+/* The model's activation getters, fused (scene/gaussian_model.py:104-125, 270-355: get_scaling, get_rotation, get_opacity, get_geo_normal,
+ * get_shading_normal, get_base_color / get_albedo, get_roughness; gaussian_renderer/svgss.py:109: viewdirs; svgss.py:316: the regulariser
+ * mse_loss(_normal, 0)): the step from the optimizer's raw parameters to what the shading and the rasterizer consume, one forward launch
+ * (plus a one-workgroup reduction when normal_reg is requested) and one backward launch.  All tensors are device fp32, contiguous; the 4-
+ * and 12-float rows must be 16-byte aligned (they move as float4).
+ *   raw inputs : xyz [P,3], scaling [P,3], rotation [P,4] as (r,x,y,z), opacity [P,1], normal [P,12] (index c * 4 + v: channel c of corner
+ *                v), base_color [P,12], roughness [P,4]; base_color_scale [3] (NULL = ones), campos [3].  A raw input may be NULL when no
+ *                requested output (backward: no requested result) reads it -- stage 1 passes no material pointers.
+ *   outputs    : each optional (NULL = not produced); every element of a requested one is written, no other memory is touched.
+ *     scales [P,3]            exp(s); NaN -> 1e-6, +inf (an exp that overflows fp32) -> FLT_MAX
+ *     rotations [P,4]         q / max(|q|, 1e-12); NaN -> 1e-6.  A row whose norm is not finite: finite / inf = 0, inf / inf = NaN -> 1e-6
+ *                             (+-inf would become +-FLT_MAX as in nan_to_num, but cannot arise: |q / |q|| <= 1)
+ *     opacities [P,1]         sigmoid(o)
+ *     geo_normal [P,3]        (2 (x z + r y), 2 (y z - r x), 1 - 2 (x x + y y)) of the ACTIVATED rotation; not renormalised
+ *     shading_normal [P,4,3]  corner v, channel c: normalize(geo_normal + normal[p, c * 4 + v]), norm clamped at 1e-12
+ *     shading_normal12 [P,12] the same numbers at index c * 4 + v (the transpose(1, 2).reshape get_radiance_loss builds)
+ *     out_base_color [P,12]   (sigmoid(b_j) * 0.77 + 0.03) * base_color_scale[j / 4]
+ *     out_roughness [P,4]     sigmoid(r) * 0.9 + 0.09; NaN -> 1e-8
+ *     viewdirs [P,3]          normalize(campos - xyz), norm clamped at 1e-12
+ *     normal_reg              float32(sum / (12 P)), sum = sum of normal^2 over the 12 P elements in double: `partial` =
+ *                             svgir_activate_partials(P) doubles (one per workgroup: lane sums in index order, xor butterfly per wave,
+ *                             the waves in order), added in a fixed order by the reduce kernel into normal_reg_sum (device double) and
+ *                             normal_reg (device float).  No atomics: two runs give the same bits.  The reference's 0.1 stays in the caller.
+ *   Arithmetic: every value is evaluated in double from the fp32 inputs (exp included; sigmoid from e = exp(-|x|) as 1 / (1 + e) or
+ *   e / (1 + e), its derivative as e / (1 + e)^2) and rounded to fp32 once.  Norms are double and do not overflow where an fp32 norm would.
+ *   A replaced element holds the fp32 constant (1e-6f, 1e-8f, FLT_MAX).  The same code runs whatever set of outputs is requested: an
+ *   output requested alone has the bits it has when all are requested.
+ *   backward   : autograd of the lines above, recomputed from the raw inputs (the forward saves nothing).  svgir_activation_grads holds one
+ *     upstream gradient per output (NULL = the output is outside the graph and contributes nothing; dL_dnormal_reg is ONE device float, the
+ *     caller's weight included) and one result per raw input; each result that is not NULL is WRITTEN COMPLETELY (no accumulation, no
+ *     pre-clear).  dL_drotation collects rotations, geo_normal and the shading normals through geo_normal; dL_dnormal the shading normals
+ *     (both layouts) and the regulariser (g 2 normal / (12 P)); dL_dxyz only viewdirs (the caller adds the rasterizer's).  normalize's
+ *     clamp as in torch: norm < 1e-12 gives g / 1e-12 (a zero quaternion: finite), else (g - u (g . u)) / norm.
+ *     ONE DECISION of this project's own: where nan_to_num replaced a value, the raw element gets ZERO gradient -- a scaling element whose
+ *     exp is NaN or overflows, a NaN roughness element, and the WHOLE rotation row when its norm is not finite.  Torch yields NaN there,
+ *     which the reference scrubs in replace_nangrad_to_zero.  Everything else propagates as in autograd (a NaN opacity, base_color, offset
+ *     or position gives NaN), and upstream NaNs pass through unchanged.
+ *   P == 0: success, nothing launched.  P < 0, a requested output / result whose raw input (or campos; normal_reg: partial and
+ *   normal_reg_sum) is missing, the shading normals' gradient without both rotation and normal, a misaligned row, nothing requested: -1 and
+ *   a message, before any HIP call. */
+typedef struct svgir_activation {
+    int32_t P;
+    const float *xyz, *scaling, *rotation, *opacity, *normal, *base_color, *roughness;   /* raw parameters */
+    const float *base_color_scale, *campos;
+    float *scales, *rotations, *opacities, *geo_normal, *shading_normal, *shading_normal12, *out_base_color, *out_roughness, *viewdirs;
+    double *partial, *normal_reg_sum;
+    float *normal_reg;
+} svgir_activation;
+typedef struct svgir_activation_grads {
+    const float *dL_dscales, *dL_drotations, *dL_dopacities, *dL_dgeo_normal, *dL_dshading_normal, *dL_dshading_normal12;
+    const float *dL_dout_base_color, *dL_dout_roughness, *dL_dviewdirs, *dL_dnormal_reg;
+    float *dL_dxyz, *dL_dscaling, *dL_drotation, *dL_dopacity, *dL_dnormal, *dL_dbase_color, *dL_droughness;
+} svgir_activation_grads;
+size_t svgir_activate_partials(int32_t P);
+int svgir_activate_forward(const svgir_activation* a, void* stream);
+int svgir_activate_backward(const svgir_activation* a, const svgir_activation_grads* g, void* stream);
+
 /* The consumers of the rasterizer's gradients: Adam over the per-Gaussian parameter block, the
  * densification statistics, and the row compaction behind pruning (scene/gaussian_model.py:737-773, 1020-1062, 1270-1276).
  *

@@ -92,6 +92,22 @@ class RadianceLossParams(C.Structure):
                 ("work", C.c_void_p)]
 
 
+class Activation(C.Structure):
+    """svgir_activation: raw parameters and requested outputs of svgir_activate_forward / svgir_activate_backward."""
+    _fields_ = [("P", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "xyz", "scaling", "rotation", "opacity", "normal", "base_color", "roughness", "base_color_scale", "campos",
+        "scales", "rotations", "opacities", "geo_normal", "shading_normal", "shading_normal12", "out_base_color", "out_roughness",
+        "viewdirs", "partial", "normal_reg_sum", "normal_reg")]
+
+
+class ActivationGrads(C.Structure):
+    """svgir_activation_grads: one upstream gradient per output, one result per raw input."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "dL_dscales", "dL_drotations", "dL_dopacities", "dL_dgeo_normal", "dL_dshading_normal", "dL_dshading_normal12",
+        "dL_dout_base_color", "dL_dout_roughness", "dL_dviewdirs", "dL_dnormal_reg",
+        "dL_dxyz", "dL_dscaling", "dL_drotation", "dL_dopacity", "dL_dnormal", "dL_dbase_color", "dL_droughness")]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -157,6 +173,13 @@ def _load():
     lib.svgir_radiance_loss_forward.argtypes = [C.POINTER(RadianceLossParams)] + [C.c_void_p] * 5
     lib.svgir_radiance_loss_backward.restype = C.c_int
     lib.svgir_radiance_loss_backward.argtypes = [C.POINTER(RadianceLossParams)] + [C.c_void_p] * 8
+    # the fused activation getters (svgir_harness/activations.py): the two parameter blocks, stream
+    lib.svgir_activate_partials.restype = C.c_size_t
+    lib.svgir_activate_partials.argtypes = [C.c_int32]
+    lib.svgir_activate_forward.restype = C.c_int
+    lib.svgir_activate_forward.argtypes = [C.POINTER(Activation), C.c_void_p]
+    lib.svgir_activate_backward.restype = C.c_int
+    lib.svgir_activate_backward.argtypes = [C.POINTER(Activation), C.POINTER(ActivationGrads), C.c_void_p]
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -178,7 +201,7 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance", "svgir_geometry_loss_partials",
            "svgir_geometry_loss_forward", "svgir_geometry_loss_backward", "svgir_smooth_loss_partials", "svgir_smooth_loss_forward",
            "svgir_smooth_loss_backward", "svgir_env_backdrop", "svgir_radiance_loss_work_bytes", "svgir_radiance_loss_forward",
-           "svgir_radiance_loss_backward")
+           "svgir_radiance_loss_backward", "svgir_activate_partials", "svgir_activate_forward", "svgir_activate_backward")
 
 
 _scope = threading.local()

@@ -41,7 +41,11 @@ class TrainStep:
 
     LAMBDA_DSSIM = 0.2   # arguments/__init__.py: lambda_dssim
 
-    def __init__(self, dev, seed=5, name="cfg3_train", Ns=64, fused=True, scene=None, radiance_grad=False):
+    # the activated tensors a raw-parameter step feeds to the shading and the rasterizer (svgir_harness/activations.py)
+    ACTIVATED = ("scales", "rotations", "opacities", "shading_normal", "base_color", "roughness", "viewdirs")
+    RAW = ("xyz", "scaling", "rotation", "opacity", "normal", "base_color", "roughness")
+
+    def __init__(self, dev, seed=5, name="cfg3_train", Ns=64, fused=True, scene=None, radiance_grad=False, raw_params=False, activate=None):
         from gaussian_renderer import shading
         from gaussian_renderer.svgss_rasterization import GaussianRasterizer
         from . import losses, optim, render_view
@@ -52,6 +56,14 @@ class TrainStep:
         # the cache sits in the optimizer (group 'radiances', :527) but never receives a gradient; what learns is the scalar ratio
         # (lr 0.01, :526-528).  radiance_grad=True is the earlier rounds' form (the [P, Ns, 3] cache itself is a differentiated leaf).
         self.radiance_grad = radiance_grad
+        # raw_params=True: the parameter block holds what the reference's optimizer holds -- log-scales, logits, normal offsets -- and every
+        # step starts with the activation getters (`activate`: svgir_harness.activations.activate unless another callable of the same
+        # signature is given), as GaussianModel's properties do in front of render_view.  The default keeps the activated tensors as the
+        # parameters.
+        self.raw_params, self.activate, self.last_activated = raw_params, activate, None
+        if raw_params and activate is None:
+            from . import activations
+            self.activate = activations.activate
         sc = self.sc = scenes.make(name) if scene is None else scene
         sct = self.sct = runner.to_torch(sc, dev)
         self.P, self.W, self.H = int(sc["means3D"].shape[0]), sc["W"], sc["H"]
@@ -66,6 +78,10 @@ class TrainStep:
         par = {"xyz": sct["means3D"], "scaling": sct["scales"], "rotation": sct["rotations"], "opacity": sct["opacities"],
                "shs": sct["shs"], "base_color": sd["base_color"], "roughness": sd["roughness"], "normal": sd["normals"],
                "radiance": sd["radiance"], "env": sd["env"]}
+        if raw_params:   # the inverse activations of the scene's values (scene/gaussian_model.py:113, 118, 125); zero normal offsets
+            logit = lambda y: torch.log(y / (1 - y))  # noqa: E731
+            par.update(scaling=torch.log(par["scaling"]), opacity=logit(par["opacity"]), base_color=logit((par["base_color"] - 0.03) / 0.77),
+                       roughness=logit((par["roughness"] - 0.09) / 0.9), normal=torch.zeros(P, 12, device=dev))
         if not radiance_grad:
             par["radiance_ratio"] = torch.ones((), device=dev)
         self.params = {k: torch.nn.Parameter(v.detach().clone().contiguous()) for k, v in par.items()}
@@ -89,13 +105,25 @@ class TrainStep:
             e.record()
             self.marks.append((name, e))
 
-    def step(self, offsets=None, keep_grads=False):
+    def step(self, offsets=None, keep_grads=False, viewdirs=None):
         """One iteration.  `offsets` [P]: the random azimuths of this iteration's incident lattices (drawn here when None);
-        keep_grads: leave the parameters' .grad in place behind the optimizer step (tests)."""
+        keep_grads: leave the parameters' .grad in place behind the optimizer step (tests); `viewdirs` [P,3]: view directions to shade
+        with instead of the ones computed here (tests: the ones another step's activation produced)."""
         p, st = self.params, self.st
         self._mark("begin")
         campos = st.campos
-        viewdirs = torch.nn.functional.normalize(campos[None, :] - p["xyz"].detach(), dim=-1)
+        if self.raw_params:   # the getters first; their outputs stand where the activated parameters stand below
+            act = self.activate({k: p[k] for k in self.RAW}, campos, None, self.ACTIVATED, False)
+            if keep_grads:
+                for v in act.values():
+                    v.retain_grad()
+            self.last_activated = act
+            p = dict(p, scaling=act["scales"], rotation=act["rotations"], opacity=act["opacities"], normal=act["shading_normal"],
+                     base_color=act["base_color"], roughness=act["roughness"])
+            viewdirs = act["viewdirs"]   # from the kernel, not detached (the shading kernels return no gradient for it: xyz gets zeros here)
+            self._mark("activate_fwd")
+        elif viewdirs is None:
+            viewdirs = torch.nn.functional.normalize(campos[None, :] - p["xyz"].detach(), dim=-1)
         offs = torch.empty(self.P, device=self.dev).uniform_(0.0, 2 * math.pi) if offsets is None else offsets   # sample_incident_rays(training): random azimuths
         lattice = self.shading.FibonacciLattice(self.geo_n, self.Ns, offs)
         self.last_offsets = offs
