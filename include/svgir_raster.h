@@ -524,6 +524,68 @@ int svgir_smooth_loss_forward(int32_t W, int32_t H, int32_t n_terms, const svgir
 int svgir_smooth_loss_backward(int32_t W, int32_t H, int32_t n_terms, const svgir_smooth_term* terms, const double* stats, const float* g,
                                void* stream);
 
+/* The tail of an eval view (eval_relighting_tensoIR.py:284-294, 333-378; eval_nvs.py:79; train.py:276-301): the per-view metrics, the 8-bit
+ * images that get written and the albedo scale, fused in csrc/view_metrics.hip.  No entry point waits for the device, none uses atomics
+ * (two runs give the same bits); invalid arguments are rejected with SVGIR_ERR_INVALID and a message before any HIP call.
+ *
+ * A PLANE OPERAND describes how a [3,H,W] operand is formed per pixel from what the caller holds; it is never stored.  fp32, in torch's
+ * operation order, every product and sum rounded on its own (no contraction), so the composed value has the bits torch would hold:
+ *   x = src[c]
+ *   x = (x * scale) + offset                  skipped when scale == 1 and offset == 0        (normal * 0.5 + 0.5)
+ *   x = (x * m) + ((1 - m) * f)               when mask != NULL; f = fill[c] if fill != NULL, else bg[c]
+ *   x = srgb(x)                               when srgb != 0: rgb_to_srgb (utils/graphics_utils.py:198-215), NaN-propagating clip
+ * src, fill: [3,H,W]; mask: [1,H,W]; contiguous fp32 device planes.  bg: three host floats.  fill without mask is invalid. */
+typedef struct svgir_plane_op {
+    const float *src, *mask, *fill;
+    float bg[3];
+    float scale, offset;
+    int32_t srgb;
+} svgir_plane_op;
+
+/* Metrics of up to SVGIR_METRIC_MAX_TERMS operand pairs of one image size from one call: one launch over 16 x 16 tiles for the terms with
+ * SSIM (the tiling and the SSIM arithmetic of the L1 + SSIM forward above; operands composed on load, the 26 x 26 halo is zero padding
+ * applied AFTER composition), one for the terms without (no halo, no LDS passes), and a small reduction, one workgroup per term.  Per
+ * pixel d = a - b in fp32; d^2 (exact in double) and |d| are summed in double per workgroup in a fixed order (wave reduction, then the
+ * four waves in order), the workgroup records then in a fixed order per term.  `terms` is a HOST array read during the call.
+ *   partial  svgir_view_metrics_partials(W, H, n_terms) doubles of device scratch
+ *   rows     [n_terms][SVGIR_METRIC_COLS] device doubles, the caller's (e.g. row v of a [views, terms, 10] table; nothing else is touched):
+ *            mse_0, mse_1, mse_2, psnr_0, psnr_1, psnr_2, mean(mse_c), mean(psnr_c), ssim, l1
+ *            mse_c = mean over H W of d^2 (utils/image_utils.py:32-33); psnr_c = -10 log10(mse_c) in double = 20 log10(1 / sqrt(mse_c))
+ *            (:36-37), +inf where mse_c == 0; ssim = the mean SSIM map over 3 H W, NaN when want_ssim == 0; l1 = mean |d| over 3 H W.
+ *            A NaN pixel makes its own channel's columns, the two means, ssim and l1 NaN, and nothing else.
+ * n_terms outside 1 ... SVGIR_METRIC_MAX_TERMS, a NULL src, fill without mask, a NULL partial / rows, W or H <= 0: -1 and a message. */
+#define SVGIR_METRIC_MAX_TERMS 4
+#define SVGIR_METRIC_COLS 10
+typedef struct svgir_metric_term {
+    svgir_plane_op a, b;
+    int32_t want_ssim;
+} svgir_metric_term;
+size_t svgir_view_metrics_partials(int32_t W, int32_t H, int32_t n_terms);
+int svgir_view_metrics(int32_t W, int32_t H, int32_t n_terms, const svgir_metric_term* terms, double* partial, double* rows, void* stream);
+
+/* The arrays torchvision's save_image hands to PIL, for up to SVGIR_CAPTURE_MAX operands in one launch: out [n,H,W,3] uint8,
+ *   out = (uint8) clamp((x * 255) + 0.5, 0, 255)
+ * (torchvision.utils.save_image: `mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to("cpu", torch.uint8)`, restated from its source;
+ * unpinned by torchvision itself, which is not a dependency of this project).  The product and the sum are rounded separately in fp32,
+ * the cast truncates.  DECISION: NaN gives 0 (torch leaves the cast of NaN undefined); +inf gives 255, -inf gives 0.  Every byte of out is
+ * written.  An operand with srgb != 0 is rejected: powf differs from torch's pow by ulps, a byte contract cannot hold there.
+ * `ops` is a HOST array read during the call.  n outside 1 ... SVGIR_CAPTURE_MAX, a NULL src / out, fill without mask, srgb != 0,
+ * W or H <= 0: -1 and a message. */
+#define SVGIR_CAPTURE_MAX 16
+int svgir_capture_u8(int32_t W, int32_t H, int32_t n, const svgir_plane_op* ops, uint8_t* out, void* stream);
+
+/* The albedo scale of the relighting eval (eval_relighting_tensoIR.py:285-294): over the pixels with ((r + g) + b) / 3 > 0 of
+ * render_albedo [3,H,W] (fp32, that order: render_albedo.mean(dim=0) > 0), per channel the mean of clamp(gt / render, 1e-6, 1), gt =
+ * gt_albedo [3,H,W], through srgb first when gt_srgb != 0.  The division is the correctly rounded fp32 one; the clamp propagates NaN
+ * (gt / 0 = inf clamps to 1; 0 / 0 = NaN makes that channel NaN).  Double sums in a fixed order.
+ *   partial  svgir_albedo_scale_partials(W, H) doubles of device scratch
+ *   scale3   3 device floats; count: 1 device int32, the number of selected pixels.  An empty selection gives NaN and 0 (torch's mean
+ *            of nothing).  scale3 can be handed on as svgir_activation.base_color_scale without visiting the host.
+ * A NULL pointer, W or H <= 0: -1 and a message. */
+size_t svgir_albedo_scale_partials(int32_t W, int32_t H);
+int svgir_albedo_scale(int32_t W, int32_t H, const float* render_albedo, const float* gt_albedo, int32_t gt_srgb, double* partial,
+                       float* scale3, int32_t* count, void* stream);
+
 /* The model's activation getters, fused (scene/gaussian_model.py:104-125, 270-355: get_scaling, get_rotation, get_opacity, get_geo_normal,
  * get_shading_normal, get_base_color / get_albedo, get_roughness; gaussian_renderer/svgss.py:109: viewdirs; svgss.py:316: the regulariser
  * mse_loss(_normal, 0)): the step from the optimizer's raw parameters to what the shading and the rasterizer consume, one forward launch

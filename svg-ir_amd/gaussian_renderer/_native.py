@@ -108,6 +108,17 @@ class ActivationGrads(C.Structure):
         "dL_dxyz", "dL_dscaling", "dL_drotation", "dL_dopacity", "dL_dnormal", "dL_dbase_color", "dL_droughness")]
 
 
+class PlaneOp(C.Structure):
+    """svgir_plane_op: how a [3,H,W] operand of svgir_view_metrics / svgir_capture_u8 is formed per pixel."""
+    _fields_ = [("src", C.c_void_p), ("mask", C.c_void_p), ("fill", C.c_void_p), ("bg", C.c_float * 3), ("scale", C.c_float),
+                ("offset", C.c_float), ("srgb", C.c_int32)]
+
+
+class MetricTerm(C.Structure):
+    """svgir_metric_term: one operand pair of svgir_view_metrics."""
+    _fields_ = [("a", PlaneOp), ("b", PlaneOp), ("want_ssim", C.c_int32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -180,6 +191,17 @@ def _load():
     lib.svgir_activate_forward.argtypes = [C.POINTER(Activation), C.c_void_p]
     lib.svgir_activate_backward.restype = C.c_int
     lib.svgir_activate_backward.argtypes = [C.POINTER(Activation), C.POINTER(ActivationGrads), C.c_void_p]
+    # the eval view's tail (svgir_harness/metrics.py): W, H, count, host descriptors, device pointers, stream
+    lib.svgir_view_metrics_partials.restype = C.c_size_t
+    lib.svgir_view_metrics_partials.argtypes = [C.c_int32] * 3
+    lib.svgir_view_metrics.restype = C.c_int
+    lib.svgir_view_metrics.argtypes = [C.c_int32] * 3 + [C.POINTER(MetricTerm)] + [C.c_void_p] * 3
+    lib.svgir_capture_u8.restype = C.c_int
+    lib.svgir_capture_u8.argtypes = [C.c_int32] * 3 + [C.POINTER(PlaneOp)] + [C.c_void_p] * 2
+    lib.svgir_albedo_scale_partials.restype = C.c_size_t
+    lib.svgir_albedo_scale_partials.argtypes = [C.c_int32] * 2
+    lib.svgir_albedo_scale.restype = C.c_int
+    lib.svgir_albedo_scale.argtypes = [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 4
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -201,7 +223,8 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_pbgi_irradiance_sample_backward", "svgir_pbgi_irradiance", "svgir_geometry_loss_partials",
            "svgir_geometry_loss_forward", "svgir_geometry_loss_backward", "svgir_smooth_loss_partials", "svgir_smooth_loss_forward",
            "svgir_smooth_loss_backward", "svgir_env_backdrop", "svgir_radiance_loss_work_bytes", "svgir_radiance_loss_forward",
-           "svgir_radiance_loss_backward", "svgir_activate_partials", "svgir_activate_forward", "svgir_activate_backward")
+           "svgir_radiance_loss_backward", "svgir_activate_partials", "svgir_activate_forward", "svgir_activate_backward",
+           "svgir_view_metrics_partials", "svgir_view_metrics", "svgir_capture_u8", "svgir_albedo_scale_partials", "svgir_albedo_scale")
 
 
 _scope = threading.local()

@@ -1,0 +1,216 @@
+"""The tail of an eval view, fused (csrc/view_metrics.hip): MSE / PSNR / SSIM / L1 rows of composed image pairs (`view_metrics`, the
+drop-ins `mse` and `psnr` for utils/image_utils.py:32-37), the 8-bit arrays that get written as images (`captures_u8`: what torchvision's
+save_image hands to PIL), the albedo scale of the relighting eval (`albedo_scale`: eval_relighting_tensoIR.py:285-294) and the whole tail
+of one relighting frame (`relighting_frame`: :333-378).  Nothing here waits for the device: every result is a device tensor, a metrics row
+can be written straight into row v of the [views, terms, 10] table that `view_parallel.run_views` gathers at the end."""
+import ctypes as C
+
+import torch
+
+from gaussian_renderer import _native as N
+
+MAX_TERMS = 4       # SVGIR_METRIC_MAX_TERMS
+CAPTURE_MAX = 16    # SVGIR_CAPTURE_MAX
+COLS = ("mse_0", "mse_1", "mse_2", "psnr_0", "psnr_1", "psnr_2", "mse", "psnr", "ssim", "l1")   # SVGIR_METRIC_COLS = 10
+# what the reference's capture loop composites over the background (eval_relighting_tensoIR.py:337); every other name is saved as it is
+MASKED_CAPTURES = ("roughness", "diffuse", "specular", "lights", "local_lights", "global_lights", "visibility", "direct")
+
+
+class Plane:
+    """A plane operand (svgir_plane_op): how a [3,H,W] image is formed per pixel from the tensors the caller holds; see `plane`."""
+    __slots__ = ("src", "mask", "fill", "bg", "scale", "offset", "srgb")
+
+    def __init__(self, src, mask, fill, bg, scale, offset, srgb):
+        self.src, self.mask, self.fill, self.bg, self.scale, self.offset, self.srgb = src, mask, fill, bg, scale, offset, srgb
+
+    @property
+    def size(self):
+        return int(self.src.shape[-2]), int(self.src.shape[-1])
+
+
+def _gpu(t, what):
+    if not torch.is_tensor(t):
+        raise TypeError(f"metrics: {what} must be a tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise RuntimeError(f"metrics: {what} must live on the GPU (libsvgir_raster.so has no CPU path)")
+    return t
+
+
+def _bg3(bg):
+    """Three host floats from a number, a sequence of three, or a CPU tensor ([3], [3,1,1] or one element)."""
+    if bg is None:
+        return (0.0, 0.0, 0.0)
+    if torch.is_tensor(bg):
+        if bg.device.type != "cpu":
+            raise RuntimeError("metrics: bg is read on the host: pass numbers or a CPU tensor (a device tensor would need a host wait); "
+                               "a per-pixel background goes into fill")
+        bg = bg.reshape(-1).tolist()
+    elif not isinstance(bg, (tuple, list)):
+        bg = [float(bg)]
+    bg = [float(v) for v in bg]
+    if len(bg) == 1:
+        bg = bg * 3
+    if len(bg) != 3:
+        raise ValueError(f"metrics: bg must be one number or three, got {len(bg)}")
+    return tuple(bg)
+
+
+def plane(src, mask=None, bg=None, fill=None, scale=1.0, offset=0.0, srgb=False):
+    """The operand  srgb?( (src * scale + offset) * mask + (1 - mask) * (fill | bg) ), formed in fp32 in torch's operation order inside
+    the kernels (never stored).  src [3,H,W] (a [1,H,W] plane is repeated to three channels, as torchvision's make_grid does before
+    an image is saved); mask [1,H,W] or [H,W]; fill [3,H,W] or bg (a number, three numbers, a CPU tensor: host values); the affine is
+    skipped when scale == 1 and offset == 0; srgb: utils/graphics_utils.py `rgb_to_srgb` last."""
+    src = _gpu(src, "src")
+    if src.dim() != 3 or src.shape[0] not in (1, 3):
+        raise ValueError(f"metrics: src must be [3,H,W] (or [1,H,W]), got {tuple(src.shape)}")
+    dev = src.device
+    H, W = int(src.shape[1]), int(src.shape[2])
+    if src.shape[0] == 1:
+        src = src.expand(3, H, W)
+    src = N.f32c(src.detach(), dev)
+    if mask is not None:
+        mask = _gpu(mask, "mask")
+        if tuple(mask.shape) not in ((1, H, W), (H, W)):
+            raise ValueError(f"metrics: mask must be [1,{H},{W}], got {tuple(mask.shape)}")
+        mask = N.f32c(mask.detach(), dev)
+    if fill is not None:
+        fill = _gpu(fill, "fill")
+        if tuple(fill.shape) != (3, H, W):
+            raise ValueError(f"metrics: fill must be [3,{H},{W}], got {tuple(fill.shape)}")
+        fill = N.f32c(fill.detach(), dev)
+    return Plane(src, mask, fill, _bg3(bg), float(scale), float(offset), bool(srgb))
+
+
+def _as_plane(p):
+    return p if isinstance(p, Plane) else plane(p)
+
+
+def _fill_op(op, p):
+    op.src, op.mask, op.fill = p.src.data_ptr(), N.ptr(p.mask), N.ptr(p.fill)
+    op.bg[0], op.bg[1], op.bg[2] = p.bg
+    op.scale, op.offset, op.srgb = p.scale, p.offset, int(p.srgb)
+
+
+def _same_size(planes, what):
+    size, dev = planes[0].size, planes[0].src.device
+    for p in planes:
+        if p.size != size or p.src.device != dev:
+            raise ValueError(f"{what}: every operand of a launch must have one image size and one device, got {p.size} and {size}")
+    return size[0], size[1], dev
+
+
+def view_metrics(terms, out=None):
+    """Rows of COLS = (mse_0, mse_1, mse_2, psnr_0, psnr_1, psnr_2, mean mse, mean psnr, ssim, l1) for up to 4 terms of one image size
+    from one call (one launch for the terms with SSIM, one for those without, one small reduction).  terms: [(a, b, want_ssim)] or
+    [(a, b)] (SSIM wanted), a / b a `plane(...)` or a plain [3,H,W] tensor.  Returns float64 [n,10] on the device; `out`: a contiguous
+    float64 [n,10] device view to write instead (a row of a caller's table; nothing else of the table is touched).  mse_c, psnr_c are
+    utils/image_utils.py:32-37 per channel, evaluated in double from the fp32 differences; psnr is +inf where the mse is exactly 0;
+    ssim is NaN where it was not wanted."""
+    terms = [tuple(t) for t in terms]
+    n = len(terms)
+    pairs = [(_as_plane(t[0]), _as_plane(t[1])) for t in terms]
+    if not pairs:
+        raise ValueError("view_metrics: no term given")
+    H, W, dev = _same_size([p for pair in pairs for p in pair], "view_metrics")
+    arr = (N.MetricTerm * n)()
+    for k, (t, (a, b)) in enumerate(zip(terms, pairs)):
+        _fill_op(arr[k].a, a)
+        _fill_op(arr[k].b, b)
+        arr[k].want_ssim = int(bool(t[2])) if len(t) > 2 else 1
+    with torch.cuda.device(dev):
+        if out is None:
+            out = N.out_tensor((n, len(COLS)), torch.float64, dev)
+        elif (out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n, len(COLS)) or not out.is_contiguous()):
+            raise ValueError(f"view_metrics: out must be a contiguous float64 [{n},{len(COLS)}] tensor on {dev}")
+        partial = torch.empty(max(N.lib.svgir_view_metrics_partials(W, H, n), 1), dtype=torch.float64, device=dev)
+        N.check(N.lib.svgir_view_metrics(W, H, n, arr, partial.data_ptr(), out.data_ptr(), N.stream_ptr(dev)), "view_metrics")
+    return out
+
+
+def _pair3(img1, img2, what):
+    for t in (img1, img2):
+        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[0] != 3:
+            raise ValueError(f"{what}: only [3,H,W] images are implemented, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    return view_metrics([(img1, img2, False)])
+
+
+def mse(img1, img2):
+    """Drop-in for utils/image_utils.py:32: the per-channel mean squared error, [3,1] fp32 on the device."""
+    return _pair3(img1, img2, "mse")[0, 0:3].to(torch.float32).reshape(3, 1)
+
+
+def psnr(img1, img2):
+    """Drop-in for utils/image_utils.py:36: 20 log10(1 / sqrt(mse)) per channel, [3,1] fp32 on the device (no host wait: the
+    reference's callers take `.mean()` of it)."""
+    return _pair3(img1, img2, "psnr")[0, 3:6].to(torch.float32).reshape(3, 1)
+
+
+def captures_u8(planes):
+    """uint8 [n,H,W,3]: for each of up to 16 operands the array torchvision's save_image hands to PIL,
+    (x * 255 + 0.5).clamp(0, 255).to(uint8) in HWC order (restated from torchvision's source; unpinned by torchvision itself), in one
+    launch.  NaN gives 0.  Operands with srgb are refused by the library (no byte contract holds against torch's pow)."""
+    planes = [_as_plane(p) for p in planes]
+    if not planes:
+        raise ValueError("captures_u8: no operand given")
+    H, W, dev = _same_size(planes, "captures_u8")
+    n = len(planes)
+    arr = (N.PlaneOp * n)()
+    for k, p in enumerate(planes):
+        _fill_op(arr[k], p)
+    with torch.cuda.device(dev):
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+        if N.POISON:
+            out.fill_(0xA5)
+        N.check(N.lib.svgir_capture_u8(W, H, n, arr, out.data_ptr(), N.stream_ptr(dev)), "capture_u8")
+    return out
+
+
+def albedo_scale(render_albedo, gt_albedo, gt_srgb=False):
+    """eval_relighting_tensoIR.py:285-294: over the pixels where render_albedo.mean(dim=0) > 0, the per-channel mean of
+    (gt / render).clamp(1e-6, 1); gt_srgb=True applies rgb_to_srgb to gt_albedo first (:289).  Returns (scale [3] fp32, count [1] int32),
+    both on the device: the scale goes into `activations.activate(..., base_color_scale=)` as it is.  An empty selection gives NaN and 0."""
+    r, g = _gpu(render_albedo, "render_albedo"), _gpu(gt_albedo, "gt_albedo")
+    if r.dim() != 3 or r.shape[0] != 3 or tuple(g.shape) != tuple(r.shape):
+        raise ValueError(f"albedo_scale: both images must be [3,H,W] of one size, got {tuple(r.shape)} and {tuple(g.shape)}")
+    dev = r.device
+    r, g = N.f32c(r.detach(), dev), N.f32c(g.detach(), dev)
+    H, W = int(r.shape[1]), int(r.shape[2])
+    with torch.cuda.device(dev):
+        partial = torch.empty(max(N.lib.svgir_albedo_scale_partials(W, H), 1), dtype=torch.float64, device=dev)
+        scale = N.out_tensor((3,), torch.float32, dev)
+        count = N.out_tensor((1,), torch.int32, dev)
+        N.check(N.lib.svgir_albedo_scale(W, H, r.data_ptr(), g.data_ptr(), int(bool(gt_srgb)), partial.data_ptr(), scale.data_ptr(),
+                                         count.data_ptr(), N.stream_ptr(dev)), "albedo_scale")
+    return scale, count
+
+
+def _captured(render_pkg, name, mask, bg):
+    """The operand the reference's capture loop saves for `name` (eval_relighting_tensoIR.py:333-346)."""
+    if name == "normal":
+        return plane(render_pkg["normal"], mask=mask, bg=bg, scale=0.5, offset=0.5)
+    if name in MASKED_CAPTURES or name == "pbr":
+        return plane(render_pkg[name], mask=mask, bg=bg)
+    if name == "pbr_env":   # (the raw pbr: see relighting_frame)
+        return plane(render_pkg["pbr"], mask=mask, fill=render_pkg["env_only"])
+    return plane(render_pkg[name])
+
+
+def relighting_frame(render_pkg, gt_image, gt_albedo, gt_normal, mask, bg, capture_list):
+    """The tail of one frame of eval_relighting_tensoIR.py:333-378: ONE captures_u8 launch and ONE view_metrics call with three terms.
+    Returns ({name: uint8 [H,W,3]}, rows float64 [3,10]): the images of `capture_list` plus "gt" (gt_image over the background, :348-349),
+    and the metric rows of  pbr vs gt,  base_color vs srgb(gt_albedo over the background),  normal vs gt_normal over the background
+    (SSIM for the first two).  The metrics see the planes as the reference's loop leaves them in render_pkg: composited over the
+    background when they were captured, the normal after `* 0.5 + 0.5`.  render_pkg itself is not modified.
+    One deviation: "pbr_env" composites the RAW pbr over env_only; the reference composites the pbr its loop has already composited
+    over bg when "pbr" comes first in the list -- equal for a binary mask.  bg: a number or three (host values)."""
+    names = list(capture_list)
+    ops = [_captured(render_pkg, k, mask, bg) for k in names]
+    gt = plane(gt_image, mask=mask, bg=bg)
+    u8 = captures_u8(ops + [gt])
+    images = {k: u8[i] for i, k in enumerate(names)}
+    images["gt"] = u8[len(names)]
+    seen = lambda k: _captured(render_pkg, k, mask, bg) if k in names else plane(render_pkg[k])   # noqa: E731
+    rows = view_metrics([(seen("pbr"), gt, True),
+                         (plane(render_pkg["base_color"]), plane(gt_albedo, mask=mask, bg=bg, srgb=True), True),
+                         (seen("normal"), plane(gt_normal, mask=mask, bg=bg), False)])
+    return images, rows
