@@ -168,6 +168,11 @@ typedef struct svgir_grads {
                                  * instead of all P.  Used where building the list costs less than it saves: svgss with vfeatures from 50 000
                                  * surfels on, otherwise from 400 000. */
     float* dL_dradiance_ratio;  /* optional [1] (ABI 13; needs shade->sp.radiance_ratio): see svgir_shade_backward */
+    /* Appended within ABI 14 (a zero-initialised svgir_grads keeps the earlier behaviour, bit for bit): the fused shading's gradient
+     * w.r.t. the RAW view directions sp.viewdirs, see svgir_shade_backward_view.  Optional (NULL: not computed; needs
+     * svgir_params.shade); written completely, rows of surfels that received no blend weight are zero.  It follows the placement rule
+     * of the four per-surfel tensors above: inside clear_base together with them, or outside together with them. */
+    float* dL_dviewdirs;        /* optional [P,3] */
 } svgir_grads;
 
 int svgir_abi_version(void);
@@ -346,6 +351,19 @@ int svgir_shade_backward(const svgir_shade_params* p, const float* dL_dreduced, 
                          const float* dL_dvfeatures, float* dL_dbase_color,
                          float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
                          float* env_grad_work, float* dL_dradiance_ratio, void* stream);
+
+/* svgir_shade_backward plus the gradient w.r.t. the view directions (added within ABI 14; svgir_shade_backward itself is unchanged and
+ * returns what it returned before).  In the reference `viewdirs = normalize(camera_center - means3D)` is a differentiable function of
+ * the surfel positions (gaussian_renderer/svgss.py:109) and the specular lobe uses it in V = normalize(viewdirs), H = normalize((L + V)
+ * / 2), N.V, N.H and the Schlick term's V.H (svgss.py:595-631); sign(V.N) has no gradient.  dL_dviewdirs [P,3] is required, written
+ * completely (rows outside a subset are zero) and is the gradient w.r.t. the RAW rows of p->viewdirs, the normalisation
+ * v / max(|v|, 1e-12) included; svgir_activate_backward turns it into dL_dxyz.  Summed without atomics: two calls give the same bits.
+ * It is a second pass behind the kernel of svgir_shade_backward, which runs unchanged: every other output has the bits that entry
+ * point writes (dL_denv: float atomics, the same sum in the order of the day). */
+int svgir_shade_backward_view(const svgir_shade_params* p, const float* dL_dreduced, const float* dL_dfeatures,
+                              const float* dL_dvfeatures, float* dL_dbase_color,
+                              float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
+                              float* env_grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream);
 
 /* Shading fused into the rasterizer calls (svgir_params.shade; ABI 12).  The only consumers of the shading's outputs are the packed
  * `features` / `vfeatures` rows the svgss composite blends (gaussian_renderer/svgss.py:143-182), and it reads the rows of the surfels

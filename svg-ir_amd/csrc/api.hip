@@ -822,6 +822,12 @@ struct BackwardCall {
         ~ClearJoin() { join(); }
     } cleared{s};
 
+    // whether [t, t + floats) lies inside the caller's clear_base region
+    bool in_clear_region(const float* t, size_t floats) const {
+        const char* b = (const char*)g->clear_base, *q = (const char*)t;
+        return b && q >= b && q + floats * 4 <= b + g->clear_bytes;
+    }
+
     int run() {
         if (int rc = locate()) return rc < 0 ? rc : 0;
         tm = stage_begin(s);
@@ -847,6 +853,10 @@ struct BackwardCall {
             if (!render_specialised(p->S, p->VS, true)) return fail(SVGIR_ERR_INVALID, "fused shading without a specialised composite");
             if (g->dL_dreduced && !p->shade->all_surfels) return fail(SVGIR_ERR_INVALID, "fused shading: dL_dreduced needs all_surfels");
             if (!p->shade->all_surfels && !g->out_weights) return fail(SVGIR_ERR_INVALID, "fused shading: out_weights (the forward's) must be provided");
+            if (g->dL_dviewdirs && in_clear_region(g->dL_dviewdirs, 3 * (size_t)p->P) != in_clear_region(g->dL_dbase_color, 12 * (size_t)p->P))
+                return fail(SVGIR_ERR_INVALID, "fused shading: dL_dviewdirs must lie inside clear_base together with the per-surfel shading gradients, or outside together with them");
+        } else if (g->dL_dviewdirs) {
+            return fail(SVGIR_ERR_INVALID, "dL_dviewdirs needs the fused shading (svgir_params.shade)");
         }
         v = view_grid(p->W, p->H);
         svgss = p->variant == SVGIR_SVGSS;
@@ -1041,9 +1051,10 @@ struct BackwardCall {
         const size_t Pz = (size_t)p->P;
         const bool precleared = in_clear(g->dL_dbase_color, 12 * Pz) && in_clear(g->dL_droughness, 4 * Pz) &&
                                 in_clear(g->dL_dshade_normals, 12 * Pz) &&
-                                (!g->dL_dradiance || in_clear(g->dL_dradiance, 3 * Pz * (size_t)sp.Ns));
+                                (!g->dL_dradiance || in_clear(g->dL_dradiance, 3 * Pz * (size_t)sp.Ns)) &&
+                                (!g->dL_dviewdirs || in_clear(g->dL_dviewdirs, 3 * Pz));
         if (shade_backward_impl(&sp, g->dL_dreduced, g->dL_dfeatures, g->dL_dvfeatures, g->dL_dbase_color, g->dL_droughness,
-                                g->dL_dshade_normals, g->dL_dradiance, g->dL_denv, g->env_grad_work, g->dL_dradiance_ratio, precleared,
+                                g->dL_dshade_normals, g->dL_dradiance, g->dL_denv, g->env_grad_work, g->dL_dradiance_ratio, g->dL_dviewdirs, precleared,
                                 shade_tabs.env != nullptr, s) != 0)
             return fail(SVGIR_ERR_INVALID, "fused shading: svgir_shade_backward rejected its parameters");
         stage_mark(tm, "shade_bwd");

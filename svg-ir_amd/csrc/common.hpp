@@ -571,11 +571,13 @@ void launch_zero_rows(int P, const uint32_t* list, const uint32_t* count_dev, fl
 // lets the composite backward's waves clear them in passing), so the rows outside the subset need no zero-fill launch
 // tables_ready = the f(env) / lattice tables (and, backward, the zeroed env-gradient accumulator) were already produced by a kernel in
 // front (shade_tables.hpp): no prologue launch
+// dL_dviewdirs [P,3] or null: the view-direction gradient (svgir_shade_backward_view); it follows rows_precleared like the four tensors
 ShadeTables shade_tables(const svgir_shade_params* p, float* zero, int nzero);
 int shade_forward_impl(const svgir_shade_params* p, float* reduced, float* features, float* vfeatures, bool tables_ready, void* stream);
 int shade_backward_impl(const svgir_shade_params* p, const float* dL_dreduced, const float* dL_dfeatures, const float* dL_dvfeatures,
                         float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
-                        float* env_grad_work, float* dL_dradiance_ratio, bool rows_precleared, bool tables_ready, void* stream);
+                        float* env_grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, bool rows_precleared, bool tables_ready,
+                        void* stream);
 
 #if defined(__HIPCC__)
 // ---- device helpers ----------------------------------------------------------------------------------------

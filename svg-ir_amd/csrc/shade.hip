@@ -729,6 +729,7 @@ struct ShadeBwdArgs {
     float* ratio_part;   // [gridDim.x] or null: per-workgroup partial sums of dL/d(radiance_ratio)
     int zero_rest;   // subset launches: the waves also zero-fill the gradient rows of the surfels OUTSIDE the subset (a few rows per processed
                      // surfel: stores nobody waits for, in a kernel that is bound by instruction issue)
+    float* d_viewdirs;   // [P,3], the VIEW instantiations only: gradient w.r.t. the RAW view directions
 };
 
 // ---- backward sample record (BREC = 20 floats = five float4, written and read with 128-bit LDS instructions):
@@ -840,7 +841,16 @@ __device__ __forceinline__ float stride4_sum(float v) {
 // the 12 atomic instructions per 64 samples were ~500 of the kernel's 552 us of LDS time, hidden behind nothing.  (And
 // the per-workgroup partial sums are exact to fp32 precision whatever the order of the adds.)  The next chunk of samples
 // is prefetched into registers while the current one is processed.
-template <bool RATIO>
+// VIEW: a second pass that writes ONLY the gradient w.r.t. the view directions (ShadeBwdArgs::d_viewdirs; DESIGN.md "View-direction
+// gradient"), launched behind the plain kernel.  V enters the specular lobe through H = normalize((L + V) / 2) (N.H and the Schlick
+// term's V.H) and through N.V; the sign of V.N has no gradient.  Every term is linear in the per-(sample, corner) adjoints d_fs and d_NoH,
+// so a lane applies the adjoint of H's normalisation to its own corner's share and keeps three sums; they meet once per surfel (DPP +
+// shuffles in a fixed order: no atomics, reproducible).  The pass shares the plain kernel's staging and arithmetic up to those adjoints;
+// every other output -- stores, LDS atomics, the ratio's sum -- is compiled out, and so is the arithmetic only they need.  (One kernel
+// for everything was built first: with the extra lines in it the instruction selector fused the multiplies and adds of the OTHER
+// gradients differently, a few ulp on ~10 % of the rows, and a view_gradient call must return their bits unchanged.)
+// A template parameter so that the VIEW = false kernels are exactly the code they were.
+template <bool RATIO, bool VIEW = false>
 __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_eu(SHADE_BWPE, SHADE_BWPE))) shade_bwd_kernel(const ShadeBwdArgs a, int env_in_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const svgir_shade_params& p = a.p;
@@ -850,7 +860,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
     float* sS = smem + (size_t)wave * (64 * BREC);
     float* sK = smem + (size_t)BWAVES * (64 * BREC) + (size_t)wave * (4 * KB_G * KREC);   // this wave's batch of per-(Gaussian, corner) records
     double* sEnv = reinterpret_cast<double*>(smem + (size_t)BWAVES * (64 * BREC + 4 * KB_G * KREC));   // [ntex] (only when env_in_lds)
-    if (env_in_lds) {
+    if (!VIEW && env_in_lds) {
         for (int i = threadIdx.x; i < ntex; i += BWAVES * 64) sEnv[i] = 0.0;
     }
     __syncthreads();
@@ -873,6 +883,10 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
     auto zero_rows = [&](int n) {
         for (int i = 0; i < n && zj < nrest; i++, zj += (uint32_t)gstep) {
             const size_t gz = (size_t)sub[(uint32_t)p.P - 1u - zj];
+            if (VIEW) {   // (the plain kernel in front has zeroed the other tensors' rows)
+                if (lane < 3) a.d_viewdirs[gz * 3 + lane] = 0.f;
+                continue;
+            }
             if (lane < 12) { a.d_base[gz * 12 + lane] = 0.f; a.d_normals[gz * 12 + lane] = 0.f; }
             if (lane < 4) a.d_rough[gz * 4 + lane] = 0.f;
             if (a.d_radiance) {
@@ -906,10 +920,8 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
         if (gj < P) {
         const size_t gg = sid(gj);
         float V[3] = {p.viewdirs[gg * 3], p.viewdirs[gg * 3 + 1], p.viewdirs[gg * 3 + 2]};
-        {
-            const float iv = inv_norm(V[0] * V[0] + V[1] * V[1] + V[2] * V[2]);   // = 1 / max(|.|, 1e-12)
-            V[0] *= iv; V[1] *= iv; V[2] *= iv;
-        }
+        const float iv = inv_norm(V[0] * V[0] + V[1] * V[1] + V[2] * V[2]);   // = 1 / max(|.|, 1e-12)
+        V[0] *= iv; V[1] *= iv; V[2] *= iv;
         GaussConst c;
         load_corner(p, gg, k, V, c);
         // Upstream gradients of this (Gaussian, corner): dL_dreduced plus the rows of the packed features / vfeatures
@@ -973,6 +985,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
             o[44 + ch] = dir_b[ch]; o[47 + ch] = dir_n[ch];
         }
         o[50] = c.n2c;
+        if (VIEW) o[51] = iv;   // (the record's last slot, unused otherwise: the adjoint of V's own normalisation needs 1 / |v|)
         o[9] = c.a2; o[10] = c.kk; o[11] = c.nom1; o[15] = c.r; o[16] = c.sgn; o[17] = c.inv_len; o[18] = c.NoV_raw; o[19] = dir_r;
         }
     }
@@ -983,6 +996,8 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
         const size_t gg = sid(g);
         zero_rows(zquota);
         float V[3], kAd[3], kAl[3], kBd[3], kBl[3], qd[3], ql[3], gmig[3], dir_b[3], dir_n[3], dir_r, grad_const;
+        [[maybe_unused]] float inv_v = 0.f;            // VIEW: 1 / max(|v|, 1e-12) of the raw view direction
+        [[maybe_unused]] float d_V[3] = {0, 0, 0};     // VIEW: this lane's share of dL/dV (V the unit view vector)
         GaussConst c;
         {
             const float4* q = reinterpret_cast<const float4*>(sK + (jb * 4 + k) * KREC);
@@ -997,6 +1012,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
             gmig[0] = q9.z; gmig[1] = q9.w; gmig[2] = q10.x;
             grad_const = k == 0 ? q10.y : (k == 1 ? q10.z : q10.w);   // lane k owns channel k (< 3) of dL/dradiance
             dir_b[0] = q11.x; dir_b[1] = q11.y; dir_b[2] = q11.z; dir_n[0] = q11.w; dir_n[1] = q12.x; dir_n[2] = q12.y; c.n2c = q12.z;
+            if (VIEW) inv_v = q12.w;
         }
         DEV_TRACE_MARK(0);   // inputs -> per-(Gaussian, corner) constants
         dev_n++;
@@ -1074,7 +1090,29 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
                 const float d_NoL = (NoLr >= 1e-6f && NoLr <= 1.f) ? d_nom2 * (1.f - c.kk) : 0.f;
 #pragma unroll
                 for (int j = 0; j < 3; j++) d_Nh[j] += d_NoH * r[4 + j] + d_NoL * Lv[j];
+                if (VIEW) {
+                    // The Schlick term frac0 = 0.04 + 0.96 * 2^((-5.55473 x - 6.98316) x), x = clamp(V.H, 1e-6, 1): the clamp passes its
+                    // gradient on the closed interval, tested on the raw dot product; dL/dfrac0 = d_fs * a2 / nom whatever nom's clamp does.
+                    const float vh = V[0] * r[4] + V[1] * r[5] + V[2] * r[6];
+                    const float x = fminf(1.f, fmaxf(1e-6f, vh));
+                    const float d_x = (vh >= 1e-6f && vh <= 1.f)
+                                          ? d_fs * c.a2 * inv_nom * (r[7] - 0.04f) * 0.69314718055994531f * (-2.f * 5.55473f * x - 6.98316f) : 0.f;
+                    // dL/dH of this corner: N.H and V.H;  dL/dV from V.H
+                    const float dH[3] = {d_NoH * c.Nh[0] + d_x * V[0], d_NoH * c.Nh[1] + d_x * V[1], d_NoH * c.Nh[2] + d_x * V[2]};
+                    // H = h / max(|h|, 1e-12), h = (L + V) / 2 (the staging's own arithmetic: the record has no slot for 1 / |h|, and
+                    // rsqrt((1 + L.V) / 2) holds for unit L and V only -- not for a zero direction or a zero view vector):
+                    // dh = (dH - H (H.dH)) / |h|, under the clamp 1e12 dH; dL/dV += dh / 2
+                    // (fmaf: what the compiler makes of the staging's (d * il + V) * 0.5 -- for L = -V bit for bit that is the rounding
+                    // residual of d * il, not 0, and the record's H is its direction; 1 / |h| must belong to the same h)
+                    const float h[3] = {fmaf(r[0], r[3], V[0]) * 0.5f, fmaf(r[1], r[3], V[1]) * 0.5f, fmaf(r[2], r[3], V[2]) * 0.5f};
+                    const float ih = inv_norm(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
+                    const float hd = ih < 1e12f ? r[4] * dH[0] + r[5] * dH[1] + r[6] * dH[2] : 0.f;
+                    const float hs = 0.5f * ih;
+#pragma unroll
+                    for (int j = 0; j < 3; j++) d_V[j] += d_x * r[4 + j] + hs * (dH[j] - r[4 + j] * hd);
+                }
 
+                if (VIEW) continue;   // (the light's adjoints belong to the plain kernel)
                 // ---- adjoint of the sample: sum the four corners (one quad), then lane k takes channel / tap k ----
 #pragma unroll
                 for (int ch = 0; ch < 3; ch++) { xg[ch] = quad_sum(xg[ch]); xl[ch] = quad_sum(xl[ch]); }
@@ -1119,6 +1157,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
             // dL/dradiance of the chunk: the values parked in the records leave as whole rows (3 cnt consecutive floats)
             wave_lds_sync();
             __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the next Gaussian's inputs (LDS-DMA) and the next chunk's samples, both issued an inner loop ago
+            if (VIEW) continue;
             if (RATIO && ratio_zero) {   // (uniform, rare: incident = 0 everywhere, the sum above is 0 -- the scalar's gradient from the raw cache)
                 const float* rawp = p.radiance + (gg * Ns + s0) * 3;
 #pragma unroll
@@ -1148,6 +1187,10 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
             const float d_NoV = nov_in ? s_nom1 * (1.f - c.kk) : 0.f;
 #pragma unroll
             for (int j = 0; j < 3; j++) d_Nh[j] += d_NoV * V[j];
+            if (VIEW) {
+#pragma unroll
+                for (int j = 0; j < 3; j++) d_V[j] += d_NoV * c.Nh[j];
+            }
         }
         // Nh = sgn * n / |n|  =>  dn += sgn/|n| * (dNh - Nn (Nn . dNh)),  Nn = n/|n|; under the norm clamp Nh = sgn * n * 1e12 is linear
         // in n and the projection term is absent
@@ -1160,7 +1203,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
 #pragma unroll
         for (int j = 0; j < 3; j++) { d_n[j] = stride4_sum(d_n[j]); d_fd[j] = stride4_sum(d_fd[j]); }
         d_r = stride4_sum(d_r);
-        if (sg == 0) {
+        if (!VIEW && sg == 0) {
 #pragma unroll
             for (int j = 0; j < 3; j++) {
                 a.d_normals[gg * 12 + k * 3 + j] = d_n[j] + dir_n[j];
@@ -1168,13 +1211,22 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
             }
             a.d_rough[gg * 4 + k] = d_r + dir_r;
         }
+        if (VIEW) {
+            // the 4 corners and 16 sample groups of the surfel, then V = v / max(|v|, 1e-12): dv = (dV - V (V.dV)) / |v|, under the clamp
+            // 1e12 dV (V = 1e12 v is linear in v there)
+#pragma unroll
+            for (int j = 0; j < 3; j++) d_V[j] = stride4_sum(quad_sum(d_V[j]));
+            const float dot = inv_v < 1e12f ? V[0] * d_V[0] + V[1] * d_V[1] + V[2] * d_V[2] : 0.f;
+            const float Vl = lane == 0 ? V[0] : (lane == 1 ? V[1] : V[2]), dl = lane == 0 ? d_V[0] : (lane == 1 ? d_V[1] : d_V[2]);
+            if (lane < 3) a.d_viewdirs[gg * 3 + lane] = inv_v * (dl - Vl * dot);
+        }
         DEV_TRACE_MARK(3);   // row stores + per-Gaussian chain rule and stores
     }
     }
     zero_rows(0x7fffffff);   // (what is left of this wave's share: waves with few or no surfels of their own)
     DEV_TRACE_END(0, dev_n, (unsigned)Ns, 0u);
     __syncthreads();
-    if (RATIO && a.ratio_part) {   // the workgroup's partial sum, waves in order (the epilogue adds the workgroups in a fixed order: reproducible)
+    if (!VIEW && RATIO && a.ratio_part) {   // the workgroup's partial sum, waves in order (the epilogue adds the workgroups in a fixed order: reproducible)
         const float rz = ratio_now().ratio;
         const float ws = wave_sum(ratio_acc) * (rz != 0.f ? 1.f / rz : 1.f);   // (sum over gk * incident -> sum over gk * raw)
         if (lane == 0) smem[wave] = ws;   // (the sample records are free: every wave passed the barrier above)
@@ -1186,7 +1238,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
         }
         __syncthreads();
     }
-    if (env_in_lds) {
+    if (!VIEW && env_in_lds) {
         for (int i = threadIdx.x; i < ntex; i += BWAVES * 64) {
             const float v = (float)sEnv[i];
             if (v != 0.f) atomic_add_f32(&a.d_envtab[i], v);
@@ -1289,7 +1341,16 @@ int svgir_shade_backward(const svgir_shade_params* p, const float* dL_dreduced, 
                          float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
                          float* env_grad_work, float* dL_dradiance_ratio, void* stream) {
     return svgir::shade_backward_impl(p, dL_dreduced, dL_dfeatures, dL_dvfeatures, dL_dbase_color, dL_droughness, dL_dnormals, dL_dradiance,
-                                      dL_denv, env_grad_work, dL_dradiance_ratio, false, false, stream);
+                                      dL_denv, env_grad_work, dL_dradiance_ratio, nullptr, false, false, stream);
+}
+
+int svgir_shade_backward_view(const svgir_shade_params* p, const float* dL_dreduced, const float* dL_dfeatures,
+                              const float* dL_dvfeatures, float* dL_dbase_color,
+                              float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
+                              float* env_grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream) {
+    if (!dL_dviewdirs) return SVGIR_ERR_INVALID;
+    return svgir::shade_backward_impl(p, dL_dreduced, dL_dfeatures, dL_dvfeatures, dL_dbase_color, dL_droughness, dL_dnormals, dL_dradiance,
+                                      dL_denv, env_grad_work, dL_dradiance_ratio, dL_dviewdirs, false, false, stream);
 }
 
 }  // extern "C"
@@ -1297,7 +1358,8 @@ int svgir_shade_backward(const svgir_shade_params* p, const float* dL_dreduced, 
 int svgir::shade_backward_impl(const svgir_shade_params* p, const float* dL_dreduced, const float* dL_dfeatures,
                                const float* dL_dvfeatures, float* dL_dbase_color,
                                float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
-                               float* env_grad_work, float* dL_dradiance_ratio, bool rows_precleared, bool tables_ready, void* stream) {
+                               float* env_grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, bool rows_precleared, bool tables_ready,
+                               void* stream) {
     if (!p || p->P < 0 || p->Ns <= 0 || p->env_h <= 0 || p->env_w <= 0) return SVGIR_ERR_INVALID;
     if (p->P == 0) return 0;
     if ((!dL_dreduced && !dL_dfeatures && !dL_dvfeatures) || (dL_dvfeatures && !p->viewmatrix) || !dL_dbase_color || !dL_droughness || !dL_dnormals || !dL_denv ||
@@ -1315,10 +1377,10 @@ int svgir::shade_backward_impl(const svgir_shade_params* p, const float* dL_dred
 
     ShadeBwdArgs a;
     a.p = *p; a.g_red = dL_dreduced; a.g_feat = dL_dfeatures; a.g_vfeat = dL_dvfeatures; a.d_base = dL_dbase_color; a.d_rough = dL_droughness; a.d_normals = dL_dnormals;
-    a.d_radiance = dL_dradiance; a.d_envtab = env_grad_work;
+    a.d_radiance = dL_dradiance; a.d_envtab = env_grad_work; a.d_viewdirs = dL_dviewdirs;
     a.ratio_part = dL_dradiance_ratio ? env_grad_work + ntex : nullptr;   // (SVGIR_SHADE_RATIO_WORK floats behind the env-gradient table)
-    a.zero_rest = (p->subset && !rows_precleared) ? 1 : 0;   // (every output is written completely: rows outside the subset are zero)
     const bool ratio = p->radiance_ratio != nullptr;
+    a.zero_rest = (p->subset && !rows_precleared) ? 1 : 0;   // (every output is written completely: rows outside the subset are zero)
     const size_t per_wave = (size_t)(64 * BREC + 4 * KB_G * KREC) * 4;
     size_t lds = BWAVES * per_wave;
     int env_in_lds = 0;
@@ -1330,9 +1392,9 @@ int svgir::shade_backward_impl(const svgir_shade_params* p, const float* dL_dred
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) return SVGIR_ERR_HIP;
         if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(shade_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(shade_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return SVGIR_ERR_HIP;
+            for (const void* f : {reinterpret_cast<const void*>(shade_bwd_kernel<false>), reinterpret_cast<const void*>(shade_bwd_kernel<true>),
+                                  reinterpret_cast<const void*>(shade_bwd_kernel<false, true>), reinterpret_cast<const void*>(shade_bwd_kernel<true, true>)})
+                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SVGIR_ERR_HIP;
             if (dev >= 0 && dev < 64) attr_set[dev] = true;
         }
     }
@@ -1345,6 +1407,11 @@ int svgir::shade_backward_impl(const svgir_shade_params* p, const float* dL_dred
     hipLaunchKernelGGL(env_grad_kernel, dim3((ntex + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, p->env, env_grad_work,
                        dL_denv, ntex, p->env_softplus, a.ratio_part, blocks, dL_dradiance_ratio);
     stage_mark(tm, "shade_env_grad");
+    if (dL_dviewdirs) {   // the view-direction pass: the same grid; the sample and surfel records only (no env image)
+        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, true>), dim3(blocks), dim3(BWAVES * 64), BWAVES * per_wave, s, a, 0);
+        else hipLaunchKernelGGL((shade_bwd_kernel<false, true>), dim3(blocks), dim3(BWAVES * 64), BWAVES * per_wave, s, a, 0);
+        stage_mark(tm, "shade_bwd_view");
+    }
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
 

@@ -49,7 +49,7 @@ class Grads(C.Structure):
         "dL_ddepth", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations", "dL_dviewmat",
         "dL_dprojmat", "dL_dcampos", "clear_base")] + [("clear_bytes", C.c_size_t)] + [(n, C.c_void_p) for n in (
         "dL_dbase_color", "dL_droughness", "dL_dshade_normals", "dL_dradiance", "dL_denv", "env_grad_work", "dL_dreduced",
-        "out_weights", "dL_dradiance_ratio")]
+        "out_weights", "dL_dradiance_ratio", "dL_dviewdirs")]
 
 
 class ViewCall(C.Structure):
@@ -212,7 +212,7 @@ lib = _load()
 EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_binning_bytes",
            "svgir_image_ncontrib_offset", "svgir_image_ranges_offset", "svgir_binning_point_list_offset", "svgir_forward", "svgir_forward_batch", "svgir_backward", "svgir_mark_visible",
            "svgir_backward_scratch_bytes", "svgir_backward_scratch_bytes_for", "svgir_speculation_stats", "svgir_reset_workload_history", "svgir_set_profiling", "svgir_last_timings", "svgir_last_error", "svgir_shade_forward",
-           "svgir_shade_backward", "svgir_incident_dirs", "svgir_resample_bilinear", "svgir_unpack_planes",
+           "svgir_shade_backward", "svgir_shade_backward_view", "svgir_incident_dirs", "svgir_resample_bilinear", "svgir_unpack_planes",
            "svgir_unpack_forward", "svgir_unpack_backward", "svgir_depth2normal", "svgir_depth2normal_backward", "svgir_pack_rgss_forward",
            "svgir_pack_rgss_backward", "svgir_unpack_rgss_forward", "svgir_unpack_rgss_backward", "svgir_l1_ssim_partials",
            "svgir_l1_ssim_forward", "svgir_l1_ssim_backward", "svgir_adam_step", "svgir_densify_stats",

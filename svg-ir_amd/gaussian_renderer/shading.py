@@ -27,6 +27,8 @@ N.lib.svgir_shade_forward.restype = C.c_int
 N.lib.svgir_shade_forward.argtypes = [C.POINTER(ShadeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 N.lib.svgir_shade_backward.restype = C.c_int
 N.lib.svgir_shade_backward.argtypes = [C.POINTER(ShadeParams)] + [C.c_void_p] * 11
+N.lib.svgir_shade_backward_view.restype = C.c_int
+N.lib.svgir_shade_backward_view.argtypes = [C.POINTER(ShadeParams)] + [C.c_void_p] * 12
 N.lib.svgir_incident_dirs.restype = C.c_int
 N.lib.svgir_incident_dirs.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 6
 N.lib.svgir_resample_bilinear.restype = C.c_int
@@ -130,10 +132,10 @@ def _radiance_grads(ctx, i_rad, i_ratio, ratio, env_h, env_w, dev):
     return want_rad, d_ratio, gwork
 
 
-def _shade_backward(ctx, i_ratio, inputs, lat, softplus, scale, g_red, g_feat=None, g_vfeat=None, **kw):
-    """The backward of _Shade / _ShadePack: ONE svgir_shade_backward.  `inputs`: the saved (base_color, roughness, normals, viewdirs,
-    radiance, visibility, dirs, areas, env, ratio); returns the gradients of (base_color, roughness, normals, radiance, env, ratio),
-    shaped like them, None where none is produced."""
+def _shade_backward(ctx, i_ratio, inputs, lat, softplus, scale, g_red, g_feat=None, g_vfeat=None, view=False, **kw):
+    """The backward of _Shade / _ShadePack: ONE svgir_shade_backward (`view`: svgir_shade_backward_view).  `inputs`: the saved (base_color,
+    roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, ratio); returns the gradients of (base_color, roughness, normals,
+    radiance, env, ratio, viewdirs), shaped like them, None where none is produced."""
     base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, ratio = inputs
     p, keep, dev, P, Ns, env_h, env_w = _params(base_color, roughness, normals, viewdirs, radiance, visibility,
                                                 lat if lat is not None else dirs, areas, env, softplus, scale, ratio=ratio, **kw)
@@ -141,7 +143,12 @@ def _shade_backward(ctx, i_ratio, inputs, lat, softplus, scale, g_red, g_feat=No
     d_base, d_rough, d_norm, d_env = (torch.empty_like(keep[i]) for i in (0, 1, 2, 8))  # all overwritten
     want_rad, d_ratio, gwork = _radiance_grads(ctx, 4, i_ratio, ratio, env_h, env_w, dev)
     d_rad = torch.empty_like(keep[4]) if want_rad else None
-    if P:
+    d_view = N.out_tensor(keep[3].shape, torch.float32, dev) if view else None
+    if P and view:
+        N.check(N.lib.svgir_shade_backward_view(p, N.ptr(gr), N.ptr(gf), N.ptr(gv), d_base.data_ptr(), d_rough.data_ptr(),
+                                                d_norm.data_ptr(), N.ptr(d_rad), d_env.data_ptr(), gwork.data_ptr(), N.ptr(d_ratio),
+                                                d_view.data_ptr(), N.stream_ptr(dev)), "shade_backward_view")
+    elif P:
         N.check(N.lib.svgir_shade_backward(p, N.ptr(gr), N.ptr(gf), N.ptr(gv), d_base.data_ptr(), d_rough.data_ptr(),
                                            d_norm.data_ptr(), N.ptr(d_rad), d_env.data_ptr(), gwork.data_ptr(), N.ptr(d_ratio),
                                            N.stream_ptr(dev)), "shade_backward")
@@ -151,16 +158,16 @@ def _shade_backward(ctx, i_ratio, inputs, lat, softplus, scale, g_red, g_feat=No
             d_ratio.zero_()
     return (d_base.reshape(base_color.shape), d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape),
             None if d_rad is None else d_rad.reshape(radiance.shape), d_env.reshape(env.shape),
-            None if d_ratio is None else d_ratio.reshape(ratio.shape))
+            None if d_ratio is None else d_ratio.reshape(ratio.shape), None if d_view is None else d_view.reshape(viewdirs.shape))
 
 
 class _Shade(torch.autograd.Function):
     """reduced[P,70] = [pbr12, diffuse_light12, specular12, direct12, indirect12, mean_incident3, mean_local3,
-    mean_global3, mean_visibility1]; differentiable w.r.t. base_color, roughness, normals, radiance, env."""
+    mean_global3, mean_visibility1]; differentiable w.r.t. base_color, roughness, normals, radiance, env (and viewdirs: view_gradient)."""
 
     @staticmethod
     def forward(ctx, base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, softplus, scale,
-                env_transform=None, ratio=None):
+                env_transform=None, ratio=None, view_gradient=False):
         p, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas,
                                             env, softplus, scale, env_transform=env_transform, ratio=ratio)
         reduced = torch.empty((P, NRED), dtype=torch.float32, device=dev)
@@ -168,15 +175,16 @@ class _Shade(torch.autograd.Function):
             N.check(N.lib.svgir_shade_forward(p, reduced.data_ptr(), None, None, N.stream_ptr(dev)), "shade_forward")
         lat = dirs if isinstance(dirs, FibonacciLattice) else None
         ctx.save_for_backward(base_color, roughness, normals, viewdirs, radiance, visibility, None if lat else dirs, areas, env, ratio)
-        ctx.cfg = (softplus, scale, env_transform, lat)
+        ctx.cfg = (softplus, scale, env_transform, lat, bool(view_gradient))
         return reduced
 
     @staticmethod
     def backward(ctx, g_reduced):
-        softplus, scale, env_transform, lat = ctx.cfg
-        d_base, d_rough, d_norm, d_rad, d_env, d_ratio = _shade_backward(ctx, 12, ctx.saved_tensors, lat, softplus, scale, g_reduced,
-                                                                         env_transform=env_transform)
-        return (d_base, d_rough, d_norm, None, d_rad, None, None, None, d_env, None, None, None, d_ratio)
+        softplus, scale, env_transform, lat, view = ctx.cfg
+        d_base, d_rough, d_norm, d_rad, d_env, d_ratio, d_view = _shade_backward(ctx, 12, ctx.saved_tensors, lat, softplus, scale, g_reduced,
+                                                                                 view=view and ctx.needs_input_grad[3],
+                                                                                 env_transform=env_transform)
+        return (d_base, d_rough, d_norm, d_view, d_rad, None, None, None, d_env, None, None, None, d_ratio, None)
 
 
 class _ShadePack(torch.autograd.Function):
@@ -185,7 +193,7 @@ class _ShadePack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, viewmatrix,
-                softplus, scale, training, env_transform=None, ratio=None):
+                softplus, scale, training, env_transform=None, ratio=None, view_gradient=False):
         p, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas,
                                             env, softplus, scale, viewmatrix=viewmatrix, training=training,
                                             env_transform=env_transform, ratio=ratio)
@@ -199,20 +207,20 @@ class _ShadePack(torch.autograd.Function):
         lat = dirs if isinstance(dirs, FibonacciLattice) else None
         ctx.save_for_backward(base_color, roughness, normals, viewdirs, radiance, visibility, None if lat else dirs, areas, env,
                               viewmatrix, ratio)
-        ctx.cfg = (softplus, scale, training, env_transform, lat)
+        ctx.cfg = (softplus, scale, training, env_transform, lat, bool(view_gradient))
         ctx.set_materialize_grads(False)
         return feats, vfeats, red
 
     @staticmethod
     def backward(ctx, g_feat, g_vfeat, g_red):
         *inputs, viewmatrix, ratio = ctx.saved_tensors
-        softplus, scale, training, env_transform, lat = ctx.cfg
+        softplus, scale, training, env_transform, lat, view = ctx.cfg
         if g_feat is None and g_vfeat is None and g_red is None:
-            return (None,) * 15
-        d_base, d_rough, d_norm, d_rad, d_env, d_ratio = _shade_backward(
-            ctx, 14, (*inputs, ratio), lat, softplus, scale, g_red, g_feat, g_vfeat, viewmatrix=viewmatrix, training=training,
-            env_transform=env_transform)
-        return (d_base, d_rough, d_norm, None, d_rad, None, None, None, d_env, None, None, None, None, None, d_ratio)
+            return (None,) * 16
+        d_base, d_rough, d_norm, d_rad, d_env, d_ratio, d_view = _shade_backward(
+            ctx, 14, (*inputs, ratio), lat, softplus, scale, g_red, g_feat, g_vfeat, view=view and ctx.needs_input_grad[3],
+            viewmatrix=viewmatrix, training=training, env_transform=env_transform)
+        return (d_base, d_rough, d_norm, d_view, d_rad, None, None, None, d_env, None, None, None, None, None, d_ratio, None)
 
 
 def _env_of(light):
@@ -231,15 +239,18 @@ def _env_of(light):
 
 def rendering_equation4(base_color, roughness, normals, viewdirs, radiance, direct_light_env_light=None,
                         visibility_precompute=None, incident_dirs_precompute=None, incident_areas_precompute=None, *,
-                        radiance_ratio=None):
+                        radiance_ratio=None, view_gradient=False):
     """Drop-in for gaussian_renderer/svgss.py:537-593.  Returns (pbr [n,12], extra_results).
+    `view_gradient` (extension, keyword only): also differentiate w.r.t. `viewdirs` when it requires a gradient, as the reference's
+    autograd does (its viewdirs = normalize(camera_center - means3D) carry a gradient into the positions); off, the backward makes exactly
+    the calls it made before and `viewdirs` gets no gradient.
     `radiance_ratio` (extension, keyword only): the reference hands in `pc.get_radiances` = nan_to_num(_radiances.detach() *
     _radiance_ratio) (gaussian_model.py:323-324); pass the RAW cache as `radiance` and the scalar here and the kernels form the product
     themselves -- no [n, Ns, 3] temporaries, and the backward returns the scalar's gradient directly."""
     dirs, areas = incident_dirs_precompute, incident_areas_precompute
     env, softplus, scale, transform = _env_of(direct_light_env_light)
     red = _Shade.apply(base_color, roughness, normals, viewdirs, radiance, visibility_precompute, dirs, areas, env,
-                       softplus, scale, transform, radiance_ratio)
+                       softplus, scale, transform, radiance_ratio, bool(view_gradient))
     extra_results = {
         # (with a FibonacciLattice the [n, Ns, 3] tensor is never built: an empty stand-in keeps the chunk loop's
         #  torch.cat over every key working, `incident_dirs_precompute.dirs()` materialises the real thing)
@@ -261,12 +272,13 @@ def rendering_equation4(base_color, roughness, normals, viewdirs, radiance, dire
 
 
 def shade_and_pack(base_color, roughness, normals, viewdirs, radiance, direct_light_env_light, visibility, dirs, areas,
-                   viewmatrix, is_training, radiance_ratio=None):
+                   viewmatrix, is_training, radiance_ratio=None, *, view_gradient=False):
     """Shading + the packing of svgss.py:143-166: returns (features [n,S], vfeatures [n,VS], reduced [n,70]).
-    The packing and its adjoint are done inside the kernels in both the no-grad and the autograd path."""
+    The packing and its adjoint are done inside the kernels in both the no-grad and the autograd path.
+    `view_gradient`: see rendering_equation4."""
     env, softplus, scale, transform = _env_of(direct_light_env_light)
     return _ShadePack.apply(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, viewmatrix,
-                            softplus, scale, bool(is_training), transform, radiance_ratio)
+                            softplus, scale, bool(is_training), transform, radiance_ratio, bool(view_gradient))
 
 
 # ---- shading fused into the rasterizer calls: "shade only what the view reads" ---------------------------------------------------
@@ -288,7 +300,7 @@ class _ShadedRasterize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, opacities, scales, rotations, base_color, roughness, normals, viewdirs, radiance,
                 visibility, dirs, areas, env, raster_settings, softplus, scale, training, env_transform, all_surfels, want_reduced,
-                ratio=None):
+                ratio=None, view_gradient=False):
         from .svgss_rasterization import _C, forward_args
         st = raster_settings
         sp, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env,
@@ -308,7 +320,7 @@ class _ShadedRasterize(torch.autograd.Function):
         lat = dirs if isinstance(dirs, FibonacciLattice) else None
         ctx.save_for_backward(means3D, sh, scales, rotations, base_color, roughness, normals, viewdirs, radiance, visibility,
                               None if lat else dirs, areas, env, feats, vfeats, weights, radii, gb, bb, ib, ratio)
-        ctx.cfg = (st, R, softplus, scale, training, env_transform, lat, all_surfels)
+        ctx.cfg = (st, R, softplus, scale, training, env_transform, lat, all_surfels, bool(view_gradient))
         ctx.mark_non_differentiable(weights, radii)
         ctx.set_materialize_grads(False)
         if red is None:
@@ -320,7 +332,8 @@ class _ShadedRasterize(torch.autograd.Function):
         from .svgss_rasterization import _C, backward_args
         (means3D, sh, scales, rotations, base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, feats,
          vfeats, weights, radii, gb, bb, ib, ratio) = ctx.saved_tensors
-        st, R, softplus, scale, training, env_transform, lat, all_surfels = ctx.cfg
+        st, R, softplus, scale, training, env_transform, lat, all_surfels, view = ctx.cfg
+        view = view and ctx.needs_input_grad[9]
         dev = means3D.device
         sp, keep, _, P, Ns, env_h, env_w = _params(base_color, roughness, normals, viewdirs, radiance, visibility,
                                                    lat if lat is not None else dirs, areas, env, softplus, scale,
@@ -330,9 +343,9 @@ class _ShadedRasterize(torch.autograd.Function):
         empty = torch.empty(0, dtype=torch.float32, device=dev)
         args = backward_args(st, means3D, feats, vfeats, radii, empty, scales, rotations, empty, sh, R, gb, bb, ib, g_color, g_normal,
                              g_opacity, g_depth, g_feature, g_vfeature)
-        if not any(ctx.needs_input_grad[i] for i in (6, 7, 8, 10, 14, 22)):   # frozen materials (evaluation): the rasterizer's backward alone
+        if not view and not any(ctx.needs_input_grad[i] for i in (6, 7, 8, 10, 14, 22)):   # frozen materials (evaluation): the rasterizer's backward alone
             res = _C.rasterize_gaussians_backward(*args)
-            return (res[3], res[0], res[7], res[2], res[8], res[9]) + (None,) * 17
+            return (res[3], res[0], res[7], res[2], res[8], res[9]) + (None,) * 18
         fs = _fused_struct(sp, None, all_surfels)
         d_env = N.out_tensor(keep[8].shape, torch.float32, dev)
         want_rad, d_ratio, gwork = _radiance_grads(ctx, 10, 22, ratio, env_h, env_w, dev)
@@ -346,6 +359,8 @@ class _ShadedRasterize(torch.autograd.Function):
             sg["_shapes"]["dL_dradiance"] = keep[4].shape
         if d_ratio is not None:
             sg["dL_dradiance_ratio"] = d_ratio
+        if view:   # (svgir_grads.dL_dviewdirs: carved out of the same allocation as the four per-surfel tensors, as the library asks)
+            sg["_shapes"]["dL_dviewdirs"] = keep[3].shape
         if P == 0:
             d_env.zero_()
             if d_ratio is not None:
@@ -354,10 +369,11 @@ class _ShadedRasterize(torch.autograd.Function):
         d_base, d_rough, d_norm, d_rad = sg["dL_dbase_color"], sg["dL_droughness"], sg["dL_dshade_normals"], sg.get("dL_dradiance")
         (g_means2D, _gc, g_opac, g_means3D, _gf, _gvf, _gcov, g_sh, g_scales, g_rot, _gv, _gp, _gcp) = res
         return (g_means3D, g_means2D, g_sh, g_opac, g_scales, g_rot, d_base.reshape(base_color.shape),
-                d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape), None,
+                d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape),
+                sg["dL_dviewdirs"].reshape(viewdirs.shape) if view else None,
                 None if d_rad is None else d_rad.reshape(radiance.shape), None, None,
                 None, d_env.reshape(env.shape), None, None, None, None, None, None, None,
-                None if d_ratio is None else d_ratio.reshape(ratio.shape))
+                None if d_ratio is None else d_ratio.reshape(ratio.shape), None)
 
 
 def fused_shade(base_color, roughness, normals, viewdirs, radiance, direct_light_env_light, visibility, dirs, areas, viewmatrix,
@@ -372,14 +388,14 @@ def fused_shade(base_color, roughness, normals, viewdirs, radiance, direct_light
 
 def render_shaded(raster_settings, means3D, means2D, opacities, shs, scales, rotations, base_color, roughness, normals, viewdirs,
                   radiance, direct_light_env_light, visibility, dirs, areas, is_training, all_surfels=False, want_reduced=False,
-                  radiance_ratio=None):
+                  radiance_ratio=None, *, view_gradient=False):
     """Shading + packing + svgss rasterization of one view (the reference's svgss.py:116-182) with the shading restricted to the
     surfels the view reads.  Returns the rasterizer's 9-tuple (num_rendered, color, normal, opacity, depth, feature, vfeature,
     weights, radii) and `reduced` [P,70] (rows of unshaded surfels zero; an empty tensor unless want_reduced).
     all_surfels=True shades every surfel (needed when a loss reads `reduced` directly: the reference's lambda_light term,
-    svgss.py:359-364)."""
+    svgss.py:359-364).  `view_gradient`: see rendering_equation4 (svgir_grads.dL_dviewdirs)."""
     env, softplus, scale, transform = _env_of(direct_light_env_light)
     out = _ShadedRasterize.apply(means3D, means2D, shs, opacities, scales, rotations, base_color, roughness, normals, viewdirs,
                                  radiance, visibility, dirs, areas, env, raster_settings, softplus, scale, bool(is_training),
-                                 transform, bool(all_surfels), bool(want_reduced), radiance_ratio)
+                                 transform, bool(all_surfels), bool(want_reduced), radiance_ratio, bool(view_gradient))
     return out[:9], out[9]

@@ -45,7 +45,8 @@ class TrainStep:
     ACTIVATED = ("scales", "rotations", "opacities", "shading_normal", "base_color", "roughness", "viewdirs")
     RAW = ("xyz", "scaling", "rotation", "opacity", "normal", "base_color", "roughness")
 
-    def __init__(self, dev, seed=5, name="cfg3_train", Ns=64, fused=True, scene=None, radiance_grad=False, raw_params=False, activate=None):
+    def __init__(self, dev, seed=5, name="cfg3_train", Ns=64, fused=True, scene=None, radiance_grad=False, raw_params=False, activate=None, *,
+                 view_gradient=False):
         from gaussian_renderer import shading
         from gaussian_renderer.svgss_rasterization import GaussianRasterizer
         from . import losses, optim, render_view
@@ -61,6 +62,9 @@ class TrainStep:
         # signature is given), as GaussianModel's properties do in front of render_view.  The default keeps the activated tensors as the
         # parameters.
         self.raw_params, self.activate, self.last_activated = raw_params, activate, None
+        # view_gradient=True: the shading also differentiates w.r.t. the view directions, as the reference's autograd does -- the gradient
+        # reaches xyz through the activation kernels (raw_params) or through torch's normalize.  Off (the default), xyz gets none of it.
+        self.view_gradient = bool(view_gradient)
         if raw_params and activate is None:
             from . import activations
             self.activate = activations.activate
@@ -120,10 +124,10 @@ class TrainStep:
             self.last_activated = act
             p = dict(p, scaling=act["scales"], rotation=act["rotations"], opacity=act["opacities"], normal=act["shading_normal"],
                      base_color=act["base_color"], roughness=act["roughness"])
-            viewdirs = act["viewdirs"]   # from the kernel, not detached (the shading kernels return no gradient for it: xyz gets zeros here)
+            viewdirs = act["viewdirs"]   # from the kernel, not detached (without view_gradient the shading returns no gradient for it: xyz gets zeros here)
             self._mark("activate_fwd")
         elif viewdirs is None:
-            viewdirs = torch.nn.functional.normalize(campos[None, :] - p["xyz"].detach(), dim=-1)
+            viewdirs = torch.nn.functional.normalize(campos[None, :] - (p["xyz"] if self.view_gradient else p["xyz"].detach()), dim=-1)
         offs = torch.empty(self.P, device=self.dev).uniform_(0.0, 2 * math.pi) if offsets is None else offsets   # sample_incident_rays(training): random azimuths
         lattice = self.shading.FibonacciLattice(self.geo_n, self.Ns, offs)
         self.last_offsets = offs
@@ -133,11 +137,12 @@ class TrainStep:
         if self.fused:   # the shading runs inside the rasterizer calls, for the surfels this view reads (include/svgir_raster.h: svgir_fused_shade)
             rendered, _ = self.shading.render_shaded(st, p["xyz"], means2D, p["opacity"], p["shs"], p["scaling"], p["rotation"],
                                                      p["base_color"], p["roughness"], p["normal"], viewdirs, radiance, self.light,
-                                                     self.visibility, lattice, None, True, radiance_ratio=ratio)
+                                                     self.visibility, lattice, None, True, radiance_ratio=ratio,
+                                                     **({"view_gradient": True} if self.view_gradient else {}))
         else:
             feats, vfeats, _ = self.shading.shade_and_pack(p["base_color"], p["roughness"], p["normal"], viewdirs, radiance,
                                                           self.light, self.visibility, lattice, None, st.viewmatrix, True,
-                                                          radiance_ratio=ratio)
+                                                          radiance_ratio=ratio, **({"view_gradient": True} if self.view_gradient else {}))
             self._mark("shade_fwd")
             rast = self.GaussianRasterizer(st)
             rendered = rast(means3D=p["xyz"], means2D=means2D, opacities=p["opacity"], shs=p["shs"], scales=p["scaling"],
