@@ -80,7 +80,8 @@ def backward(out, grads, variant):
 
 def forward_raw(sc, variant):
     """Forward through the `_C` binding (no autograd) keeping the three state blobs; also decodes the depth-sorted instance
-    list and the tile ranges from them (include/svgir_raster.h introspection offsets).  `sc` is a to_torch() scene."""
+    list and the tile ranges from them (include/svgir_raster.h introspection offsets).  `sc` is a to_torch() scene; it holds `shs` or
+    `colors_precomp`."""
     from gaussian_renderer import _native as N
     dev = sc["means3D"].device
     st = settings(sc, variant)
@@ -89,11 +90,11 @@ def forward_raw(sc, variant):
     if variant == "svgss":
         from gaussian_renderer.svgss_rasterization import _C
         VS = sc["vfeatures"].shape[1]
-        out = _C.rasterize_gaussians(st.bg, sc["means3D"], sc["features"], sc["vfeatures"], empty, sc["opacities"],
+        out = _C.rasterize_gaussians(st.bg, sc["means3D"], sc["features"], sc["vfeatures"], sc.get("colors_precomp", empty), sc["opacities"],
                                      sc.get("scales", empty), sc.get("rotations", empty), st.scale_modifier,
                                      sc.get("cov3D_precomp", empty), st.viewmatrix,
                                      st.projmatrix, st.prcppoint, st.patch_bbox, st.tanfovx, st.tanfovy,
-                                     st.image_height, st.image_width, sc["shs"], st.sh_degree, st.campos, False, False,
+                                     st.image_height, st.image_width, sc.get("shs", empty), st.sh_degree, st.campos, False, False,
                                      st.config)
         (R, color, normal, depth, opac, feat, vfeat, weights, radii, gb, bb, ib) = out
         res = dict(num_rendered=R, color=color, normal=normal, depth=depth, opacity=opac, feature=feat, vfeature=vfeat,
@@ -101,10 +102,10 @@ def forward_raw(sc, variant):
     else:
         from gaussian_renderer.rgss_rasterization import _C
         VS = 0
-        out = _C.rasterize_gaussians(st.bg, sc["means3D"], sc["features"], empty, sc["opacities"], sc.get("scales", empty),
+        out = _C.rasterize_gaussians(st.bg, sc["means3D"], sc["features"], sc.get("colors_precomp", empty), sc["opacities"], sc.get("scales", empty),
                                      sc.get("rotations", empty), st.scale_modifier, sc.get("cov3D_precomp", empty), st.viewmatrix,
                                      st.projmatrix,
-                                     st.tanfovx, st.tanfovy, st.cx, st.cy, st.image_height, st.image_width, sc["shs"],
+                                     st.tanfovx, st.tanfovy, st.cx, st.cy, st.image_height, st.image_width, sc.get("shs", empty),
                                      st.sh_degree, st.campos, False, False, False)
         (R, ncontrib, color, normal, opac, depth, feat, pn, sx, weights, radii, gb, bb, ib) = out
         res = dict(num_rendered=R, color=color, normal=normal, depth=depth, opacity=opac, feature=feat, weights=weights,
