@@ -6,10 +6,17 @@
 // measured): ONE wave issues one VALU instruction per ~8 cycles whether or not the instructions depend on each other, and a
 // SIMD only reaches its 2 cycles per wave64 instruction with >= 4-6 resident waves.  So instruction-level parallelism inside
 // a wave buys nothing, registers spent on it cost resident waves, and every instruction counts.  Hence:
-//   * one candidate at a time (no lock-step groups), <= 80 VGPRs and 5.1 KB of LDS per wave -> 6 waves per SIMD (was 3);
-//   * the per-candidate attributes are wave-uniform: they are fetched with SCALAR loads (constant address space, one
-//     candidate ahead) into SGPRs and enter the per-pixel math as scalar operands -- no LDS staging buffer, no broadcast
-//     ds_reads, no VGPRs for uniform data;
+//   * one candidate at a time (no lock-step groups); 10 112 B of LDS per wave keep 16 waves per CU (4 per SIMD, pinned by
+//     amdgpu_waves_per_eu) resident, which leaves each lane 128 VGPRs -- 102 to 119 are used, no scratch;
+//   * the per-candidate attributes are wave-uniform.  The records of a block of 8 candidates (float4 #0 .. #4 of each: 640 B)
+//     are copied global -> LDS by the DMA path (global_load_lds, no VGPRs), and phase A reads candidate k's values back with
+//     broadcast ds_read_b128 (every lane the same address) into VGPRs, which enter the per-pixel math as operands.  LDS
+//     returns in order, so the record of the next candidate is in flight behind a COUNTED lgkmcnt wait while this one is
+//     evaluated; no scalar memory load is left inside the candidate loop (scalar loads return out of order: every wait on one
+//     is lgkmcnt(0), and a record that misses the scalar cache had one candidate's work to arrive in -- DESIGN.md 4,
+//     profiles/bwd_lds_records_ab.txt).  ONE record buffer: the copy for block n + 1 is issued in phase B of block n, behind
+//     the last read of the buffer and in front of the moment MFMAs, and is waited for (vmcnt(0)) behind those MFMAs, in
+//     front of the block's first atomics;
 //   * all per-Gaussian sums over the 64 pixels run on the matrix pipe.  The blend weight w and ONE more per-(pixel,
 //     candidate) scalar v = G dL_dalpha go to an LDS panel (8 candidates per block); the w rows of TWO consecutive blocks x
 //     G[pixel][colour3 normal3 depth feature S] give the channel gradients of 16 candidates in one 16-row contraction (3 MFMAs per
@@ -29,9 +36,6 @@ namespace svgir {
 
 namespace {
 
-typedef const __attribute__((address_space(4))) float cfloat;      // constant address space: uniform loads become s_load
-typedef const __attribute__((address_space(4))) uint32_t cuint;
-
 #ifndef BWDP_GRID_MULT
 #define BWDP_GRID_MULT 4   // workgroups launched per resident wave slot
 #endif
@@ -40,6 +44,17 @@ typedef const __attribute__((address_space(4))) uint32_t cuint;
 #endif
 #ifndef BWDP_MFMA_ACC
 #define BWDP_MFMA_ACC 1   // accumulators per 16-long MFMA chain (2: even and odd steps apart, summed at the end -- profiles/bwd_rows_ab.txt)
+#endif
+#ifndef BWDP_AHEAD
+#define BWDP_AHEAD 1      // phase A reads the record of candidate k + BWDP_AHEAD from LDS while it evaluates candidate k (profiles/bwd_lds_records_ab.txt)
+#endif
+#ifndef BWDP_HOIST
+#define BWDP_HOIST 0      // 1: let the compiler keep the moment operands and lane-derived addresses in VGPRs across blocks (profiles/bwd_lds_records_ab.txt)
+#endif
+#if BWDP_HOIST
+#define BWDP_OPAQUE(x) ((void)0)
+#else
+#define BWDP_OPAQUE(x) asm volatile("" : "+v"(x))   // the value is re-derived behind this point, not carried in registers across it
 #endif
 
 template <int S>
@@ -50,11 +65,14 @@ struct PlainGeom {
     static constexpr int PS = 68;                // panel row stride (floats)
     static constexpr int PROWS = 32;             // panel rows: 2 x 8 blend weights w (a PAIR of blocks) | 8 v | 8 u (Q5 term) of the current block
     static constexpr size_t off_m = (size_t)PROWS * PS * 4;            // moments + Q5 sums [SB][8]
-    static constexpr size_t off_c = off_m + (size_t)SB * 8 * 4;        // per-candidate constants of the block [3][SB] float4 (LDS-DMA target)
-    static constexpr size_t off_q = off_c + (size_t)3 * SB * 16;       // the segment's {gid, slot} entries, deepest first
+    static constexpr int NCH = 5;                // record float4 #0 .. #4 of a candidate: everything phase A and the epilogue read
+    static constexpr size_t off_c = off_m + (size_t)SB * 8 * 4;        // the block's records [NCH][SB] float4 (LDS-DMA target)
+    static constexpr size_t off_q = off_c + (size_t)NCH * SB * 16;     // the segment's {gid, slot} entries, deepest first
     static constexpr size_t lds_bytes = off_q + (size_t)SEG * 8;
     static_assert(NC0 <= 16, "one 16-wide MFMA column tile");
     static_assert((size_t)64 * GROW * 4 <= off_m, "the G transposition tile aliases the panel");
+    static_assert(S == 0 || rec_embeds_features(S, 0), "phase A reads the feature row out of the staged record");
+    static_assert(lds_bytes <= 10240, "16 waves per CU (4 per SIMD) must stay resident: 160 KB of LDS");
 };
 
 template <int S, bool SVGSS>
@@ -68,7 +86,7 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
     float* sP = reinterpret_cast<float*>(smem);                    // [32][PS] rows 0..15: blend weights of two blocks, 16..23: v, 24..31: u
     float* sG = sP;                                                // [64][GROW] upstream gradients (transposition only)
     float* sM = reinterpret_cast<float*>(smem + PG::off_m);        // [SB][8] six moments, Q5 sum, pad
-    float4* sC = reinterpret_cast<float4*>(smem + PG::off_c);      // [3][SB] record float4 #0, #1, #3 of the block's candidates
+    float4* sC = reinterpret_cast<float4*>(smem + PG::off_c);      // [NCH][SB] record float4 #0 .. #4 of the block's candidates
     uint2* sQ = reinterpret_cast<uint2*>(smem + PG::off_q);        // [SEG] {gid, slot}, deepest first
 
     const int lane = threadIdx.x;
@@ -120,6 +138,7 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
         cu32* dsc = (cu32*)(uintptr_t)(a.seg_desc + item);
         d_sm = dsc[0]; d_r0 = dsc[1]; d_len = dsc[2]; d_count = dsc[3]; d_ndump = dsc[4]; d_sb = dsc[6];
     }
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): no LDS-DMA of the previous segment lands once this one's set-up has begun
     wave_lds_sync();   // the previous segment's LDS traffic is complete before its buffers are reused
     const uint32_t sm = d_sm, r0 = d_r0, tlen = d_len;
     const int count = (int)d_count, ndump = (int)d_ndump;
@@ -136,51 +155,34 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
     const uint2* __restrict__ sub_in = a.sub_list + (size_t)4 * r0 + (size_t)sub * tlen;
     const size_t pid = inside ? (size_t)a.W * py + px : 0;
     const int nent = seg_hi - seg_lo;
-    cuint* list_c = (cuint*)(uintptr_t)(sub_in + (seg_hi - 1));   // entry i of the walk = {list_c[-2 i], list_c[-2 i + 1]}
+    // the segment's list entries, deepest first: loaded here, stored to sQ behind the per-pixel loads
+    uint2 ent_in = make_uint2(0u, 0u);
+    if (lane < nent) ent_in = sub_in[seg_hi - 1 - lane];
 
-    // per-candidate attributes (wave-uniform -> SGPRs): list entries are fetched two candidates ahead, records one ahead
+    // Per-candidate attributes (wave-uniform).  The block's records lie in LDS (sC, copied there by the DMA path); candidate k's
+    // values come from broadcast ds_read_b128 -- every lane reads the same address -- and its slot from the sQ entry.  They stay in
+    // VGPRs and enter the per-pixel arithmetic as operands.  LDS returns in order, so the waits are counted: the record of
+    // candidate k + BWDP_AHEAD is in flight while candidate k is evaluated, and no scalar memory load is left inside the loop.
     struct Cand { float X, Y, cxx, cxy, cyy, op, dep, DA, DB, cr, cg, cb, nx, ny, nz, f[SS]; uint32_t slot; };
-    struct Entry { uint32_t gid, slot; };
-    typedef const __attribute__((address_space(4))) char cchar;
-    cchar* rec_b = (cchar*)(uintptr_t)a.rec;
-    cchar* feat_b = (cchar*)(uintptr_t)a.features;
-    auto fetch_entry = [&](int i) -> Entry {
-        const int ci = min(i, nent - 1);   // (uniform) clamped: slots beyond the list replay a real record with weight 0
-        Entry e;
-        e.gid = list_c[-2 * ci];
-        const uint32_t sl = list_c[-2 * ci + 1];
-        e.slot = i < nent ? sl : 0xffffffffu;   // (slot 2^32-1: never blends)
-        return e;
-    };
-    auto fetch_rec = [&](const Entry& e) -> Cand {
-        // 32-bit byte offsets: P * 96 B < 4 GiB (api.hip validate)
-        cfloat* r = (cfloat*)(rec_b + (uint32_t)(e.gid * (uint32_t)(REC * 4)));
+    auto read_cand = [&](int c0, int k) -> Cand {
+        const float4 q0 = sC[k], q1 = sC[SB + k], q3 = sC[3 * SB + k], q4 = sC[4 * SB + k];
         Cand c;
-        c.X = r[R_X]; c.Y = r[R_Y]; c.cxx = r[R_CX]; c.cxy = r[R_CY]; c.cyy = r[R_CZ]; c.op = r[R_OP]; c.dep = r[R_DEPTH]; c.DA = r[R_DA];
-        c.DB = r[R_DB]; c.cr = r[R_R]; c.cg = r[R_G]; c.cb = r[R_B]; c.nx = r[R_NX]; c.ny = r[R_NY]; c.nz = r[R_NZ];
-        if (rec_embeds_features(S, 0)) {   // the feature row rides in the record (preprocess; common.hpp rec_feature_slot)
+        c.X = q0.x; c.Y = q0.y; c.cxx = q0.z; c.cxy = q0.w; c.cyy = q1.x; c.op = q1.y; c.dep = q1.z; c.DA = q1.w;
+        c.DB = q3.x; c.cr = q3.y; c.cg = q3.z; c.cb = q3.w; c.nx = q4.x; c.ny = q4.y; c.nz = q4.z;
+        if (S > 0) {   // the feature row rides in the record (preprocess; common.hpp rec_feature_slot: float4 #2, then R_IU)
+            const float4 q2 = sC[2 * SB + k];
+            const float fv[5] = {q2.x, q2.y, q2.z, q2.w, q4.w};
 #pragma unroll
-            for (int ch = 0; ch < SS; ch++) c.f[ch] = ch < S ? r[rec_feature_slot(ch)] : 0.f;
+            for (int ch = 0; ch < SS; ch++) c.f[ch] = fv[ch];
         } else {
-            cfloat* f = (cfloat*)(feat_b + (uint32_t)(e.gid * (uint32_t)(S * 4)));
-            if (S >= 4) {   // (scalar loads only need dword alignment: one x4 + singles instead of S singles)
-                typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-                const f32x4u f4 = *reinterpret_cast<const __attribute__((address_space(4))) f32x4u*>(f);
-                c.f[0] = f4.x; c.f[1 % SS] = f4.y; c.f[2 % SS] = f4.z; c.f[3 % SS] = f4.w;
-    #pragma unroll
-                for (int ch = 4; ch < S; ch++) c.f[ch] = f[ch];
-            } else {
-    #pragma unroll
-                for (int ch = 0; ch < SS; ch++) c.f[ch] = ch < S ? f[ch] : 0.f;
-            }
+            c.f[0] = 0.f;
         }
-        c.slot = e.slot;
+        // (uniform select) slots beyond the list replay the record of the list's last entry and never blend: slot 2^32-1,
+        // whatever the staged record and the sQ entry hold
+        const uint32_t sl = sQ[c0 + k].y;
+        c.slot = c0 + k < nent ? sl : 0xffffffffu;
         return c;
     };
-    // speculative: the replay usually starts at entry 0 -- its record is fetched while the per-pixel loads are in flight
-    const Cand spec_cur = fetch_rec(fetch_entry(0));
-    const Entry spec_en1 = fetch_entry(1);
-    asm volatile("" :: "s"(spec_cur.X), "s"(spec_en1.gid));
 
     const float T_final = inside ? a.final_T[pid] : 0.f;
     const float D_final = (inside && normalize_depth) ? a.final_D[pid] : 0.f;
@@ -253,15 +255,11 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
 #pragma unroll
     for (int k = 0; k < SB; k++) sP[(SB + k) * PS + lane] = 0.f;
 
-    // The segment's list entries, deepest first (the replay walks back to front): LDS copy for the per-lane consumers
-    // (atomics of phase B); the per-candidate math reads them with scalar loads.
+    // The segment's list entries, deepest first (the replay walks back to front): gid for the DMA sources and the atomics of
+    // phase B, slot for phase A
     int nskip = 0;   // entries that lie behind every pixel of this wave (a prefix: slots descend)
-    {
-        uint2 e = make_uint2(0u, 0u);
-        if (lane < nent) e = sub_in[seg_hi - 1 - lane];
-        sQ[lane] = e;
-        nskip = __popcll(__ballot(lane < nent && e.y >= wmax));
-    }
+    sQ[lane] = ent_in;
+    nskip = __popcll(__ballot(lane < nent && ent_in.y >= wmax));
     // flags folded into the per-pixel factors: the replay itself is branch-free
     const float gNe0 = surface ? gN[0] : 0.f, gNe1 = surface ? gN[1] : 0.f, gNe2 = surface ? gN[2] : 0.f;
     float gFe[SS];
@@ -270,27 +268,24 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
     const float spf = sp ? 1.f : 0.f;
     const float gOT = gO_kbg * T_final;
 
-    const int cstart = (nskip / SB) * SB;
-    Cand cur = spec_cur;
-    Entry en1 = spec_en1;
-    if (cstart != 0) {   // (uniform) the deepest entries lie behind every pixel of the wave: start further in
-        cur = fetch_rec(fetch_entry(cstart));
-        en1 = fetch_entry(cstart + 1);
-    }
-    // Per-candidate constants of a block for its geometric epilogue (lane = (chunk, candidate)): copied global -> LDS by the
-    // DMA path (no VGPRs, nothing waits) one block ahead -- issued here for the first block, then at the end of every block
-    auto prefetch_consts = [&](int cb) {
+    const int cstart = (nskip / SB) * SB;   // (uniform) the deepest entries lie behind every pixel of the wave: start further in
+    // The records of a block (lane = (float4 of the record, candidate)): copied global -> LDS by the DMA path, no VGPRs.  ONE buffer:
+    // the copy for block n + 1 is issued once block n has read its last value out of it (phase B below), here for the first block.
+    // Slots beyond the list take the record of the list's last entry.  32-bit offsets: P * 96 B < 4 GiB (api.hip validate)
+    auto stage_records = [&](int cb) {
         int lC = lane;
-        asm volatile("" : "+v"(lC));
-        if (lC < 3 * SB) {
+        BWDP_OPAQUE(lC);
+        if (lC < PG::NCH * SB) {
             const int cq = lC & 7, chunk = lC >> 3;
-            const uint32_t gq = sQ[min(cb + cq, SEG - 1)].x;
-            const float* src = a.rec + (uint32_t)(gq * (uint32_t)REC + (uint32_t)(chunk == 2 ? 12 : 4 * chunk));
+            const uint32_t gq = sQ[min(cb + cq, nent - 1)].x;
+            const float* src = a.rec + (uint32_t)(gq * (uint32_t)REC + (uint32_t)(4 * chunk));
             __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(smem + PG::off_c), 16, 0, 0);
         }
     };
     wave_lds_sync();   // sQ visible
-    prefetch_consts(cstart);
+    stage_records(cstart);
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the first block's records have landed
+    wave_lds_sync();
     DEV_TRACE_MARK(0);   // segment setup
     dev_items++; dev_cands += (unsigned)nent;
     // Blocks are taken in PAIRS counted from cstart: the blend weights of both blocks fill the 16 rows of ONE channel contraction
@@ -301,14 +296,18 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
         const int par = ((c0 - cstart) / SB) & 1;   // (uniform) position of the block in its pair
         float* sPw = sP + par * (SB * PS) + lane;   // this block's weight rows
         uint32_t live = 0;  // bit k set: candidate c0+k has at least one blending pixel (wave-uniform)
-        // ---------------- phase A: lane = pixel, one candidate at a time, attributes in SGPRs ----------------
-        // (scalar loads and LDS stores share one completion counter: the panel stores of candidate k are issued right AFTER the
-        // wait for candidate k+1's attributes, so that wait never includes a fresh LDS store)
+        const bool more = c0 + SB < nent;           // (uniform) another block follows: its records are staged from phase B
+        // ---------------- phase A: lane = pixel, one candidate at a time, attributes broadcast from LDS into VGPRs ----------------
+        // (LDS reads and stores retire in order: the panel stores of candidate k are issued behind the reads of candidate
+        // k + BWDP_AHEAD, and every wait is a counted one)
         float hw = 0.f, hv = 0.f, hu = 0.f;
+        Cand cand[SB];
+#pragma unroll
+        for (int k = 0; k < BWDP_AHEAD; k++) cand[k] = read_cand(c0, k);
 #pragma unroll
         for (int k = 0; k < SB; k++) {
-            const Cand nxt = fetch_rec(en1);
-            en1 = fetch_entry(c0 + k + 2);
+            if (k + BWDP_AHEAD < SB) cand[k + BWDP_AHEAD] = read_cand(c0, k + BWDP_AHEAD);
+            const Cand& cur = cand[k];
             const float dx = cur.X - pxf, dy = cur.Y - pyf;
             if (k > 0) {
                 sPw[(k - 1) * PS] = hw; sP[(2 * SB + k - 1) * PS + lane] = hv; sP[(3 * SB + k - 1) * PS + lane] = hu;
@@ -318,9 +317,11 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
             const float al = fminf(0.99f, cur.op * Gs);
             const bool pre = cur.slot < last_contributor && pw <= 0.0f && al >= (1.0f / 255.0f);
             const float ioma = __builtin_amdgcn_rcpf(1.f - al);
-            float sd = cur.cr * gC[0] + cur.cg * gC[1] + cur.cb * gC[2];
-            sd += cur.nx * gNe0 + cur.ny * gNe1 + cur.nz * gNe2;
-            const float d_cur = cur.dep - spf * (dx * cur.DA + dy * cur.DB);   // depth differencing (common.hpp R_DA / R_DB)
+            // (a b + c d has two fused forms; which one is written out, so that the sums do not depend on where the compiler finds the
+            // operands -- the forms are those of the scalar-operand build this path was measured against, profiles/bwd_lds_records_ab.txt)
+            float sd = __builtin_fmaf(cur.cb, gC[2], __builtin_fmaf(cur.cr, gC[0], cur.cg * gC[1]));
+            sd += __builtin_fmaf(cur.nz, gNe2, __builtin_fmaf(cur.ny, gNe1, cur.nx * gNe0));
+            const float d_cur = cur.dep - spf * __builtin_fmaf(dy, cur.DB, dx * cur.DA);   // depth differencing (common.hpp R_DA / R_DB)
             sd += d_cur * gDn;
 #pragma unroll
             for (int ch = 0; ch < S; ch++) sd += cur.f[ch] * gFe[ch];
@@ -339,7 +340,6 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
             hv = pre ? Gs * dL_dalpha : 0.f;       // v
             hu = pre ? q5g : 0.f;                  // u: its pixel sum is the Q5 term (0 unless per-pixel depth is on)
             live |= (__builtin_amdgcn_ballot_w64(pre) != 0ull ? 1u : 0u) << k;
-            cur = nxt;
         }
         sPw[(SB - 1) * PS] = hw; sP[(3 * SB - 1) * PS + lane] = hv; sP[(4 * SB - 1) * PS + lane] = hu;
         DEV_TRACE_MARK(2);   // phase A
@@ -349,16 +349,26 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
         // D layout: lane l, register r -> row 4 (l >> 4) + r, column l & 15
         // (lane-derived addresses are re-derived here every block: hoisted out of the loop they would hold ~20 VGPRs across phase A)
         int lB = lane;
-        asm volatile("" : "+v"(lB));
+        BWDP_OPAQUE(lB);
         const int colB = lB & 15, grpB = lB >> 4;
+        const int cq = lB & 7, jq = lB >> 3;   // geometric epilogue: lane = (value j, candidate c)
         f32x4 accM = {0.f, 0.f, 0.f, 0.f};
+        float4 Aq, Bq;
+        float DBq;
         {   // rows (v | u) x Mom: lanes 0..31, columns 0..5 = the six pixel moments of v; lanes 32..63, column 0 = sum of u
             const float4* ap = reinterpret_cast<const float4*>(sP + (2 * SB + colB) * PS + 16 * grpB);
             const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3];
             const float av[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w,
                                   a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
+            // The epilogue's constants leave the record buffer now: behind these reads nothing of this block is left in it, and
+            // the copy of the next block's records runs under the MFMAs below
+            Aq = sC[cq]; Bq = sC[SB + cq]; DBq = sC[3 * SB + cq].x;
+            if (more) {
+                __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): every read of the buffer has returned
+                stage_records(c0 + SB);
+            }
             float c0l = cx0;
-            asm volatile("" : "+v"(c0l));   // (opaque: the 16 operand values are not hoisted out of the block loop into 16 VGPRs)
+            BWDP_OPAQUE(c0l);   // (opaque: the 16 operand values are not hoisted out of the block loop into 16 VGPRs)
             f32x4 accM2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 16; kk++) {
@@ -377,24 +387,24 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) sM[(4 * (grpB - 2) + rr) * 8 + 6] = accM[rr];
         }
-        __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the block's constants have landed in LDS (issued a whole block ago)
+        // vmcnt(0): the next block's records have landed in LDS (issued in front of the MFMAs), and no atomic younger than a whole
+        // phase is outstanding.  In FRONT of this block's atomics: vmcnt counts them too, and they do not retire in order with loads
+        __builtin_amdgcn_s_waitcnt(0x0f70);
         wave_lds_sync();
         DEV_TRACE_MARK(3);   // phase B (MFMA)
         // lane = (value j = lane >> 3, candidate c = lane & 7): the six geometric gradients from the moments
         {
-            const int cq = lB & 7, jq = lB >> 3;
             if (jq < 6 && ((live >> cq) & 1u)) {
                 const float4 m03 = *reinterpret_cast<const float4*>(sM + cq * 8);
                 const float4 m47 = *reinterpret_cast<const float4*>(sM + cq * 8 + 4);
-                const float4 Aq = sC[cq], Bq = sC[SB + cq];
-                const float DBq = sC[2 * SB + cq].x;
                 const float Xc = Aq.x - cxs, Yc = Aq.y - cys;       // mean relative to the sub-tile centre
                 const float M0 = m03.x, M1 = m03.y, M2 = m03.z, M3 = m03.w, M4 = m47.x, M5 = m47.y, Q = m47.z;
                 const float Sx = Xc * M0 - M1, Sy = Yc * M0 - M2;  // sum v dx, sum v dy
                 const float hf = Bq.y * -0.5f;                      // dL_ddist = v * hf
                 float ge;
-                if (jq == 0) ge = hf * 2.f * (Aq.z * Sx + Aq.w * Sy) * ddelx_dx + Q * Bq.w;
-                else if (jq == 1) ge = hf * 2.f * (Bq.x * Sy + Aq.w * Sx) * ddely_dy + Q * DBq;
+                // (the fused forms of a b + c d written out, as in phase A)
+                if (jq == 0) ge = __builtin_fmaf(Q, Bq.w, hf * 2.f * __builtin_fmaf(Aq.w, Sy, Aq.z * Sx) * ddelx_dx);
+                else if (jq == 1) ge = __builtin_fmaf(Q, DBq, hf * 2.f * __builtin_fmaf(Aq.w, Sx, Bq.x * Sy) * ddely_dy);
                 else if (jq == 2) ge = hf * (Xc * (Sx - M1) + M3);              // sum v dx^2
                 else if (jq == 3) ge = hf * ((Xc * Sy - Yc * M1) + M4);          // sum v dx dy
                 else if (jq == 4) ge = hf * (Yc * (Sy - M2) + M5);              // sum v dy^2
@@ -402,14 +412,19 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
                 if (ge != 0.f) atomic_add_f32(a.grad_rows + (uint32_t)(sQ[c0 + cq].x * (uint32_t)RS + (uint32_t)(GEO + jq)), ge);
             }
         }
-        wave_lds_sync();   // moments / constants / panel consumed before they are overwritten
+        wave_lds_sync();   // moments / panel consumed before they are overwritten
+        } else if (more) {   // nothing blends in this block: phase B is skipped, the next phase A still needs its records
+            __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
+            stage_records(c0 + SB);
+            __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
+            wave_lds_sync();
         }
         live16 = par ? (live16 | (live << SB)) : live;
         if ((par || c0 + SB >= nent) && live16 != 0) {   // (uniform) the pair is complete, or the segment ends on its first block
             wave_lds_sync();          // weight rows visible
             // ---------------- rows (w_a | w_b) x G: the channel gradients of the pair's 16 candidates, row = 8 (block of the pair) + k ----------------
             int lP = lane;
-            asm volatile("" : "+v"(lP));
+            BWDP_OPAQUE(lP);
             const int colP = lP & 15, grpP = lP >> 4;
             f32x4 accP = {0.f, 0.f, 0.f, 0.f};
             {
@@ -434,7 +449,6 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
             }
             wave_lds_sync();   // weight rows consumed before the next pair overwrites them
         }
-        if (c0 + SB < nent) prefetch_consts(c0 + SB);
         DEV_TRACE_MARK(1);   // geometric epilogue
     }
     }   // loop over live segments
