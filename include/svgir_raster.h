@@ -365,6 +365,59 @@ int svgir_shade_backward_view(const svgir_shade_params* p, const float* dL_dredu
                               float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
                               float* env_grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream);
 
+/* Spherical-Gaussian direct light (added within ABI 14: new entry points and one new struct, nothing existing changes).
+ * The reference's second learnable light, scene/direct_light_sg.py:DirectLightSG, is a mixture of M lobes evaluated exactly per incident
+ * direction (render_envmap_sg); train.py:65-66 switches between it and the lat-long texture.  The entry points below are
+ * svgir_shade_forward / svgir_shade_backward(_view) with that mixture as the global light: the M lobes replace the staging's four
+ * texture taps and the backward's texel scatter, nothing of the GGX / transport arithmetic changes.
+ *
+ * Raw parameters: `lobes` [M,7] fp32 row-major, row = (xi.x, xi.y, xi.z, lambda, mu.r, mu.g, mu.b), 1 <= M <= SVGIR_SG_MAX_LOBES.
+ * Light of a direction d -- used as given: NOT normalised, and no lookup transform (DirectLightSG.direct_light ignores its `transform`):
+ *     a_m = xi_m / |xi_m|                 (a plain sqrt of the sum of squares and a plain division, as torch.norm: no clamp)
+ *     e_m = expf(|lambda_m| (d.a_m - 1))  (the accurate expf, not the fast intrinsic: |lambda| is in the hundreds)
+ *     L_c(d) = sum_m |mu_mc| e_m          (fp32, m ascending)
+ * Shading: global = clamp(L, 0, 64) * visibility; everything downstream -- transport, GGX, the 70 reduced columns, the packing into
+ * features / vfeatures at training and eval widths, radiance_ratio, explicit directions and the in-kernel lattice -- is what the texture
+ * path does with its `global`.
+ * Gradients w.r.t. the raw lobes: with g_c the adjoint of L_c (= the adjoint of global_c x visibility x the clamp mask 0 <= L_c <= 64,
+ * which passes at equality as torch.clamp does) and s = sum_c |mu_c| e g_c, summed over all P Ns samples:
+ *     dmu_c = sign(mu_c) e g_c,   dlambda = sign(lambda) (d.a - 1) s,   dxi = |lambda| s (d - a (a.d)) / |xi|,   sign(0) = 0 (torch's abs).
+ * The gradients of base_color, roughness, normals, radiance / radiance_ratio and viewdirs are those of the texture path with this global.
+ * Non-finite lobes: a lobe with |xi| = 0 or a non-finite entry makes the light NaN for EVERY sample, as in torch (NaN * 0 = NaN): the
+ * forward returns NaN in the light-dependent columns; nothing faults or hangs; gradients are unspecified in that case.
+ *
+ * `work`: caller-provided, 16-byte aligned, 8 * count floats -- the prepared table a small prologue kernel builds on every call, per lobe
+ * {a.xyz, |lambda|} and {|mu|.rgb, 1 / |xi|} (the role env_work plays for the texture).
+ * Invalid input is rejected with SVGIR_ERR_INVALID and a message before any launch: count outside 1 ... SVGIR_SG_MAX_LOBES, NULL lobes /
+ * work, a misaligned work, a non-NULL subset / subset_count (subset shading belongs to the rasterizer-fused path).
+ * NOT provided (each would be new work, not a switch): the shading fused into svgir_forward / svgir_backward (svgir_fused_shade carries no
+ * light pointer: a struct change and an ABI bump), the eval backdrop and the fused radiance-consistency loss for an SG light, and a
+ * differentiable svgir_sg_eval. */
+#define SVGIR_SG_MAX_LOBES 128
+typedef struct svgir_sg_light {
+    int32_t count;        /* M */
+    const float* lobes;   /* [M,7] raw */
+    float* work;          /* [8 M] scratch, 16-byte aligned */
+} svgir_sg_light;
+
+/* out [n,3] = the UNCLAMPED L of dirs [n,3]: DirectLightSG.direct_light / render_envmap_sg.  Forward only. */
+int svgir_sg_eval(const svgir_sg_light* light, int64_t n, const float* dirs, float* out, void* stream);
+
+/* svgir_shade_forward with the SG light.  The env* fields of `p` (env, env_h, env_w, env_softplus, env_scale, env_work, env_transform) are
+ * ignored and may be NULL / 0; p->subset must be NULL. */
+int svgir_shade_forward_sg(const svgir_shade_params* p, const svgir_sg_light* light, float* reduced, float* features, float* vfeatures,
+                           void* stream);
+
+/* svgir_shade_backward (dL_dviewdirs != NULL: svgir_shade_backward_view) with the SG light: dL_dlobes [M,7] takes dL_denv's place, all
+ * outputs are overwritten.  dL_dradiance_ratio and dL_dviewdirs are optional (NULL) as there.  `grad_work`: scratch of
+ * svgir_sg_grad_work_bytes(count) bytes (the table-space sums + SVGIR_SHADE_RATIO_WORK floats).  The 7 M sums over all samples are
+ * accumulated per workgroup in LDS in fp64 and flushed once per workgroup with float atomics (dL_dlobes: the same sum in the order of the
+ * day, like dL_denv); a small epilogue kernel applies the normalisation's Jacobian and the signs. */
+size_t svgir_sg_grad_work_bytes(int32_t count);
+int svgir_shade_backward_sg(const svgir_shade_params* p, const svgir_sg_light* light, const float* dL_dreduced, const float* dL_dfeatures,
+                            const float* dL_dvfeatures, float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance,
+                            float* dL_dlobes, float* grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream);
+
 /* Shading fused into the rasterizer calls (svgir_params.shade; ABI 12).  The only consumers of the shading's outputs are the packed
  * `features` / `vfeatures` rows the svgss composite blends (gaussian_renderer/svgss.py:143-182), and it reads the rows of the surfels
  * that survive the view's culls only -- 44 % of the surfels pass the preprocess culls on the BASELINE scenes, ~30 % survive the per-tile

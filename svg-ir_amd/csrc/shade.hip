@@ -18,11 +18,17 @@
 // The backward re-runs phase 1/2 with the adjoint arithmetic; per-sample light gradients are exchanged between the
 // four corner rows through LDS, env-texel gradients are accumulated in a workgroup-private LDS image by persistent
 // workgroups and flushed with one global atomic per texel per workgroup.
+//
+// A second light kind (LIGHT_SG, sg_light.hpp): the reference's mixture of spherical-Gaussian lobes (scene/direct_light_sg.py) evaluated
+// per sample from a prepared table in LDS.  The global light of a sample is corner-independent, so the kind is a template parameter of
+// the three kernels that only replaces the staging's texture taps and the backward's texel scatter; the texture instantiations are the
+// code they were.
 #include <algorithm>
 
 #include "common.hpp"
 #include "env_lookup.hpp"
 #include "shade_tables.hpp"
+#include "sg_light.hpp"
 
 #include "dev_trace.hpp"
 
@@ -275,8 +281,12 @@ __device__ __forceinline__ RawSample load_raw(const svgir_shade_params& p, size_
 
 // phase 1 for one chunk of <= 64 samples [s0, s0+cnt) of one Gaussian: fills the wave's sample records (slot =
 // sample - s0) and adds this lane's sample to the per-lane light sums m[10].
+// (LIGHT: the kind of the global light -- the lat-long texture, or the spherical-Gaussian mixture whose prepared table `sgt` sits in
+// LDS, sg_light.hpp; a template parameter so that the texture kernels are exactly the code they were)
+template <int LIGHT>
 __device__ __forceinline__ void stage_samples(const svgir_shade_params& p, size_t g, int lane, const float* V,
-                                              float* __restrict__ sS, float* m, int s0, int cnt, const LatticeFrame& lf, const RadRatio& rr) {
+                                              float* __restrict__ sS, float* m, int s0, int cnt, const LatticeFrame& lf, const RadRatio& rr,
+                                              const float4* __restrict__ sgt) {
     const int Ns = p.Ns;
     if (lane < cnt) {
         const int s = s0 + lane;
@@ -294,6 +304,9 @@ __device__ __forceinline__ void stage_samples(const svgir_shade_params& p, size_
         H[0] *= ih; H[1] *= ih; H[2] *= ih;
         const float VoH = fminf(1.f, fmaxf(1e-6f, V[0] * H[0] + V[1] * H[1] + V[2] * H[2]));
         const float frac0 = 0.04f + (1.f - 0.04f) * __builtin_amdgcn_exp2f((-5.55473f * VoH - 6.98316f) * VoH);
+        float E[3] = {0.f, 0.f, 0.f};
+        if constexpr (LIGHT == LIGHT_SG) sg_eval(sgt, p.env_w, d, E);   // (env_w: the lobe count, see svgir_shade_forward_sg)
+        else {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
         EnvTap t;
         float dl[3] = {d[0], d[1], d[2]};
         if (p.env_transform) {
@@ -302,8 +315,6 @@ __device__ __forceinline__ void stage_samples(const svgir_shade_params& p, size_
             for (int j = 0; j < 3; j++) dl[j] = m[3 * j] * d[0] + m[3 * j + 1] * d[1] + m[3 * j + 2] * d[2];
         }
         env_taps(dl, p.env_h, p.env_w, t);
-        float E[3] = {0.f, 0.f, 0.f};
-        {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
             float tex[4][3];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -320,7 +331,7 @@ __device__ __forceinline__ void stage_samples(const svgir_shade_params& p, size_
         float* r = sS + lane * SREC;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            const float Lg = fminf(64.f, fmaxf(0.f, E[ch] * p.env_scale)) * vis;
+            const float Lg = (LIGHT == LIGHT_SG ? sg_clamp(E[ch]) : fminf(64.f, fmaxf(0.f, E[ch] * p.env_scale))) * vis;
             r[ch] = d[ch]; r[3 + ch] = L[ch]; r[6 + ch] = H[ch];
             r[10 + ch] = Lg; r[13 + ch] = rad[ch];
             m[3 + ch] += rad[ch]; m[6 + ch] += Lg;
@@ -350,10 +361,17 @@ __device__ __forceinline__ void zero_rest_rows(const ShadeArgs& a, size_t wave_i
 // One wave per Gaussian.  (A persistent variant that loads the next Gaussian's samples and corner data while the current one
 // is processed was built and measured: 282 us at 4 waves/SIMD, 332 us at 5 (spills) against 250 us for this one.)
 // (RATIO: svgir_shade_params.radiance_ratio is set -- a template parameter so that the plain kernels are exactly the code they were)
-template <bool RATIO>
+template <bool RATIO, int LIGHT = LIGHT_TEX>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHADE_FWPE, SHADE_FWPE))) shade_fwd_kernel(const ShadeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const svgir_shade_params& p = a.p;
+    const float4* sgt = nullptr;   // LIGHT_SG: the prepared lobe table, staged behind the waves' strips (2 float4 per lobe, 4 KB at 128)
+    if constexpr (LIGHT == LIGHT_SG) {
+        float4* st = reinterpret_cast<float4*>(smem + (size_t)4 * (64 * SREC + 80 + 32));
+        for (int i = threadIdx.x; i < 2 * p.env_w; i += BLOCK) st[i] = reinterpret_cast<const float4*>(p.env_work)[i];
+        __syncthreads();
+        sgt = st;
+    }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int Ns = p.Ns;
     const RadRatio rr = RATIO ? rad_ratio(p) : RadRatio{1.f, false};
@@ -396,7 +414,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
       const int cnt = min(64, Ns - s0);
       wave_lds_sync();   // previous chunk consumed
       DEV_TRACE_MARK(0);
-      stage_samples(p, gg, lane, V, sS, m, s0, cnt, lf, rr);
+      stage_samples<LIGHT>(p, gg, lane, V, sS, m, s0, cnt, lf, rr, sgt);
       wave_lds_sync();
       DEV_TRACE_MARK(1);
       for (int s = sg; s < cnt; s += 16) {
@@ -501,10 +519,17 @@ __device__ __forceinline__ float quad_bcast(float v) {   // value of lane (quad 
 
 struct FqSample { float d[3], il, ih, frac0, LgA[3], LlA[3]; };   // the staged, corner-independent part of one incident sample
 
-template <bool RATIO>
+template <bool RATIO, int LIGHT = LIGHT_TEX>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHADE_FQ_WPE_LO, SHADE_FQ_WPE))) shade_fwd_quad_kernel(const ShadeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const svgir_shade_params& p = a.p;
+    const float4* sgt = nullptr;   // LIGHT_SG: the prepared lobe table, staged behind the waves' strips (see shade_fwd_kernel)
+    if constexpr (LIGHT == LIGHT_SG) {
+        float4* st = reinterpret_cast<float4*>(smem + (size_t)4 * (FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF));
+        for (int i = threadIdx.x; i < 2 * p.env_w; i += BLOCK) st[i] = reinterpret_cast<const float4*>(p.env_work)[i];
+        __syncthreads();
+        sgt = st;
+    }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int Ns = p.Ns;
     float* sOut = smem + (size_t)wave * (FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF);
@@ -583,6 +608,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
             const float ih = inv_norm(H[0] * H[0] + H[1] * H[1] + H[2] * H[2]);   // = 1 / max(|.|, 1e-12)
             const float VoH = fminf(1.f, fmaxf(1e-6f, (V[0] * H[0] + V[1] * H[1] + V[2] * H[2]) * ih));
             f.frac0 = 0.04f + (1.f - 0.04f) * __builtin_amdgcn_exp2f((-5.55473f * VoH - 6.98316f) * VoH);
+            float E[3] = {0.f, 0.f, 0.f};
+            if constexpr (LIGHT == LIGHT_SG) sg_eval(sgt, p.env_w, d, E);   // the M lobes in place of the texture's taps
+            else {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
             EnvTap t;
             float dl[3] = {d[0], d[1], d[2]};
             if (p.env_transform) {
@@ -591,8 +619,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
                 for (int j = 0; j < 3; j++) dl[j] = mt[3 * j] * d[0] + mt[3 * j + 1] * d[1] + mt[3 * j + 2] * d[2];
             }
             env_taps(dl, p.env_h, p.env_w, t);
-            float E[3] = {0.f, 0.f, 0.f};
-            {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
                 float tex[4][3];
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
@@ -609,7 +635,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
             const float area = act ? x.area : 0.f;   // samples beyond Ns (Ns not a multiple of 4) carry weight 0
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) {
-                const float Lg = fminf(64.f, fmaxf(0.f, E[ch] * p.env_scale)) * x.vis;
+                const float Lg = (LIGHT == LIGHT_SG ? sg_clamp(E[ch]) : fminf(64.f, fmaxf(0.f, E[ch] * p.env_scale))) * x.vis;
                 f.d[ch] = d[ch];
                 f.LgA[ch] = Lg * area; f.LlA[ch] = x.rad[ch] * area;
                 if (act) { m[ch] += x.rad[ch]; m[3 + ch] += Lg; }
@@ -751,8 +777,11 @@ constexpr int BREC = 20;
 constexpr int BWAVES = SHADE_BWAVES;   // waves per backward workgroup
 constexpr int KB_G = SHADE_KB_G, KREC = 52;   // Gaussians prepared per batch; floats per (Gaussian, corner) record (13 float4)
 
+// LIGHT_SG: the record's footprint slots are free -- [16] carries the clamp flags alone, and [16..18] later receive the adjoint of the
+// sample's unclamped light (shade_bwd_kernel); ve = visibility.
+template <int LIGHT>
 __device__ __forceinline__ void stage_raw_bwd(const svgir_shade_params& p, const RawSample& x, int lane, const float* V,
-                                              float* __restrict__ sS, const RadRatio& rr) {
+                                              float* __restrict__ sS, const RadRatio& rr, const float4* __restrict__ sgt) {
     const float* d = x.d;
     const float il = inv_norm(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // = 1 / max(|.|, 1e-12)
     const float L[3] = {d[0] * il, d[1] * il, d[2] * il};
@@ -761,6 +790,31 @@ __device__ __forceinline__ void stage_raw_bwd(const svgir_shade_params& p, const
     H[0] *= ih; H[1] *= ih; H[2] *= ih;
     const float VoH = fminf(1.f, fmaxf(1e-6f, V[0] * H[0] + V[1] * H[1] + V[2] * H[2]));
     const float frac0 = 0.04f + (1.f - 0.04f) * __builtin_amdgcn_exp2f((-5.55473f * VoH - 6.98316f) * VoH);
+    if constexpr (LIGHT == LIGHT_SG) {
+        float E[3];
+        sg_eval(sgt, p.env_w, d, E);
+        float r[BREC];
+        uint32_t flags = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            r[ch] = d[ch]; r[4 + ch] = H[ch];
+            r[8 + ch] = sg_clamp(E[ch]) * x.vis; r[12 + ch] = incident_of(x.rad[ch], rr);
+            flags |= (E[ch] >= 0.f && E[ch] <= 64.f) ? (1u << ch) : 0u;   // (torch.clamp passes its gradient at the bounds; NaN: none)
+        }
+        r[3] = il; r[7] = frac0; r[11] = x.area; r[15] = x.vis;
+        r[16] = __builtin_bit_cast(float, flags << 28);
+        r[17] = 0.f; r[18] = 0.f;
+        uint32_t nf = 0;
+        if (rr.on) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) nf |= ratio_finite(x.rad[ch], rr) ? 0u : (1u << ch);
+        }
+        r[19] = __builtin_bit_cast(float, nf);
+        float4* o = reinterpret_cast<float4*>(sS + lane * BREC);
+#pragma unroll
+        for (int i = 0; i < BREC / 4; i++) o[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+        return;
+    }
     // bilinear footprint (same arithmetic as env_taps)
     const int He = p.env_h, We = p.env_w;
     float dl[3] = {d[0], d[1], d[2]};
@@ -831,6 +885,43 @@ __device__ __forceinline__ float stride4_sum(float v) {
     return v;
 }
 
+// LIGHT_SG, the lobes' share of a chunk of <= 64 samples.  When the corner x sample loop is through, every record of the chunk holds the
+// direction d in [0..2] and the adjoint g of the sample's unclamped light L in [16..18] (upstream x visibility x clamp mask).  Here
+// lane = (sample group, lobe): the wave's 64 lanes are split into groups of `1 << lpg_shift` >= min(M, 64) lanes, lane % group = the lobe
+// (two lobes per lane above 64), and group j walks samples j, j + ngroups, ... -- records are read as LDS broadcasts, e is recomputed, and
+// the seven table-space sums of a lobe
+//     d|mu|_c = sum e g_c,   d|lambda| = sum (d.a - 1) s,   G = sum s d      with s = sum_c |mu_c| e g_c   (dL/da = |lambda| G)
+// are private to the lane for the chunk: no cross-lane reduction.  They then go to the workgroup's fp64 accumulator with seven ds_add_f64
+// per lobe and chunk (against 12 per 16 samples for the texture's taps).  Samples without an adjoint (occluded, clamped) are skipped.
+__device__ __forceinline__ void sg_chunk_adjoint(const float* __restrict__ sS, int cnt, const float4* __restrict__ sgt, double* __restrict__ acc,
+                                                 int M, int lane) {
+    const int lpg_shift = M > 32 ? 6 : 32 - __builtin_clz((unsigned)max(M, 2) - 1u);   // lanes per sample group: the power of two >= min(M, 64)
+    const int lpg = 1 << lpg_shift, lm = lane & (lpg - 1), grp = lane >> lpg_shift, ngrp = 64 >> lpg_shift;
+    for (int m = lm; m < M; m += lpg) {
+        const float4 al = sgt[2 * m], mu = sgt[2 * m + 1];
+        float gm[3] = {0.f, 0.f, 0.f}, ga[3] = {0.f, 0.f, 0.f}, gl = 0.f;
+        for (int s = grp; s < cnt; s += ngrp) {
+            const float4 dq = *reinterpret_cast<const float4*>(sS + s * BREC), gq = *reinterpret_cast<const float4*>(sS + s * BREC + 16);
+            if (gq.x == 0.f && gq.y == 0.f && gq.z == 0.f) continue;
+            const float d[3] = {dq.x, dq.y, dq.z};
+            float t;
+            const float e = sg_lobe(al, d, t);
+            const float e0 = e * gq.x, e1 = e * gq.y, e2 = e * gq.z;
+            const float sv = mu.x * e0 + mu.y * e1 + mu.z * e2;
+            gm[0] += e0; gm[1] += e1; gm[2] += e2;
+            gl += t * sv;
+            ga[0] += sv * d[0]; ga[1] += sv * d[1]; ga[2] += sv * d[2];
+        }
+        double* o = acc + 8 * m;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            if (ga[j] != 0.f) atomicAdd(&o[j], (double)ga[j]);        // ds_add_f64
+            if (gm[j] != 0.f) atomicAdd(&o[4 + j], (double)gm[j]);
+        }
+        if (gl != 0.f) atomicAdd(&o[3], (double)gl);
+    }
+}
+
 // Persistent workgroups of BWAVES waves; every wave owns one Gaussian at a time and never synchronises with the other
 // waves (its sample records are wave-private LDS).  Lane = (sample group sg = lane / 4, corner k = lane % 4): the
 // four corners of one incident sample sit in one DPP quad, so the per-sample light gradients are summed with two
@@ -850,18 +941,30 @@ __device__ __forceinline__ float stride4_sum(float v) {
 // for everything was built first: with the extra lines in it the instruction selector fused the multiplies and adds of the OTHER
 // gradients differently, a few ulp on ~10 % of the rows, and a view_gradient call must return their bits unchanged.)
 // A template parameter so that the VIEW = false kernels are exactly the code they were.
-template <bool RATIO, bool VIEW = false>
+// LIGHT (LIGHT_SG: svgir_shade_backward_sg): the light kind, as in the forward.  The staging evaluates the M lobes instead of the four
+// taps, the quad parks the adjoint of the sample's light in its record instead of scattering it, and sg_chunk_adjoint (above) turns a
+// chunk's parked adjoints into the lobes' table-space sums; the fp64 LDS image is those 8 M sums and the prepared table sits behind it.
+template <bool RATIO, bool VIEW = false, int LIGHT = LIGHT_TEX>
 __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_eu(SHADE_BWPE, SHADE_BWPE))) shade_bwd_kernel(const ShadeBwdArgs a, int env_in_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const svgir_shade_params& p = a.p;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int Ns = p.Ns, We = p.env_w, He = p.env_h;
-    const int ntex = He * We * 3;
+    const int ntex = LIGHT == LIGHT_SG ? 8 * We : He * We * 3;   // (LIGHT_SG: env_w = the lobe count, env_in_lds = 1)
     float* sS = smem + (size_t)wave * (64 * BREC);
     float* sK = smem + (size_t)BWAVES * (64 * BREC) + (size_t)wave * (4 * KB_G * KREC);   // this wave's batch of per-(Gaussian, corner) records
     double* sEnv = reinterpret_cast<double*>(smem + (size_t)BWAVES * (64 * BREC + 4 * KB_G * KREC));   // [ntex] (only when env_in_lds)
     if (!VIEW && env_in_lds) {
         for (int i = threadIdx.x; i < ntex; i += BWAVES * 64) sEnv[i] = 0.0;
+    }
+    // LIGHT_SG: the lobe count and the table's place are derived where they are used instead of being named across the kernel
+    auto sg_count = [&]() -> int { return p.env_w; };
+    auto sg_tab = [&]() -> const float4* {
+        return LIGHT == LIGHT_SG ? reinterpret_cast<const float4*>(smem + (size_t)BWAVES * (64 * BREC + 4 * KB_G * KREC)) + 4 * sg_count() : nullptr;
+    };
+    if constexpr (LIGHT == LIGHT_SG) {
+        float4* st = reinterpret_cast<float4*>(sEnv + 8 * We);
+        for (int i = threadIdx.x; i < 2 * We; i += BWAVES * 64) st[i] = reinterpret_cast<const float4*>(p.env_work)[i];
     }
     __syncthreads();
     const float inv_ns = 1.f / (float)Ns;
@@ -999,21 +1102,23 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
         [[maybe_unused]] float inv_v = 0.f;            // VIEW: 1 / max(|v|, 1e-12) of the raw view direction
         [[maybe_unused]] float d_V[3] = {0, 0, 0};     // VIEW: this lane's share of dL/dV (V the unit view vector)
         GaussConst c;
-        {
-            const float4* q = reinterpret_cast<const float4*>(sK + (jb * 4 + k) * KREC);
-            const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6], q7 = q[7], q8 = q[8], q9 = q[9], q10 = q[10],
-                         q11 = q[11], q12 = q[12];
-            V[0] = q0.x; V[1] = q0.y; V[2] = q0.z; c.nraw[0] = q0.w; c.nraw[1] = q1.x; c.nraw[2] = q1.y;
-            c.Nh[0] = q1.z; c.Nh[1] = q1.w; c.Nh[2] = q2.x; c.a2 = q2.y; c.kk = q2.z; c.nom1 = q2.w;
-            c.fd[0] = q3.x; c.fd[1] = q3.y; c.fd[2] = q3.z; c.r = q3.w; c.sgn = q4.x; c.inv_len = q4.y; c.NoV_raw = q4.z; dir_r = q4.w;
-            kAd[0] = q5.x; kAd[1] = q5.y; kAd[2] = q5.z; kAl[0] = q5.w; kAl[1] = q6.x; kAl[2] = q6.y;
-            kBd[0] = q6.z; kBd[1] = q6.w; kBd[2] = q7.x; kBl[0] = q7.y; kBl[1] = q7.z; kBl[2] = q7.w;
-            qd[0] = q8.x; qd[1] = q8.y; qd[2] = q8.z; ql[0] = q8.w; ql[1] = q9.x; ql[2] = q9.y;
-            gmig[0] = q9.z; gmig[1] = q9.w; gmig[2] = q10.x;
-            grad_const = k == 0 ? q10.y : (k == 1 ? q10.z : q10.w);   // lane k owns channel k (< 3) of dL/dradiance
-            dir_b[0] = q11.x; dir_b[1] = q11.y; dir_b[2] = q11.z; dir_n[0] = q11.w; dir_n[1] = q12.x; dir_n[2] = q12.y; c.n2c = q12.z;
-            if (VIEW) inv_v = q12.w;
+#define SHADE_LOAD_REC()  /* the (Gaussian, corner) record of this lane, from the wave's batch in LDS */ \
+        { \
+            const float4* q = reinterpret_cast<const float4*>(sK + (jb * 4 + k) * KREC);                                                             \
+            const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6], q7 = q[7], q8 = q[8], q9 = q[9], q10 = q[10],  \
+                         q11 = q[11], q12 = q[12];                                                                                                   \
+            V[0] = q0.x; V[1] = q0.y; V[2] = q0.z; c.nraw[0] = q0.w; c.nraw[1] = q1.x; c.nraw[2] = q1.y;                                             \
+            c.Nh[0] = q1.z; c.Nh[1] = q1.w; c.Nh[2] = q2.x; c.a2 = q2.y; c.kk = q2.z; c.nom1 = q2.w;                                                 \
+            c.fd[0] = q3.x; c.fd[1] = q3.y; c.fd[2] = q3.z; c.r = q3.w; c.sgn = q4.x; c.inv_len = q4.y; c.NoV_raw = q4.z; dir_r = q4.w;              \
+            kAd[0] = q5.x; kAd[1] = q5.y; kAd[2] = q5.z; kAl[0] = q5.w; kAl[1] = q6.x; kAl[2] = q6.y;                                                \
+            kBd[0] = q6.z; kBd[1] = q6.w; kBd[2] = q7.x; kBl[0] = q7.y; kBl[1] = q7.z; kBl[2] = q7.w;                                                \
+            qd[0] = q8.x; qd[1] = q8.y; qd[2] = q8.z; ql[0] = q8.w; ql[1] = q9.x; ql[2] = q9.y;                                                      \
+            gmig[0] = q9.z; gmig[1] = q9.w; gmig[2] = q10.x;                                                                                         \
+            grad_const = k == 0 ? q10.y : (k == 1 ? q10.z : q10.w);   /* lane k owns channel k (< 3) of dL/dradiance */                              \
+            dir_b[0] = q11.x; dir_b[1] = q11.y; dir_b[2] = q11.z; dir_n[0] = q11.w; dir_n[1] = q12.x; dir_n[2] = q12.y; c.n2c = q12.z;               \
+            if (VIEW) inv_v = q12.w;                                                                                                                 \
         }
+        SHADE_LOAD_REC()
         DEV_TRACE_MARK(0);   // inputs -> per-(Gaussian, corner) constants
         dev_n++;
         float d_fd[3] = {0, 0, 0}, d_n[3] = {0, 0, 0}, d_Nh[3] = {0, 0, 0};
@@ -1023,7 +1128,7 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
         for (int s0 = 0; s0 < Ns; s0 += 64) {
             const int cnt = min(64, Ns - s0);
             wave_lds_sync();   // previous chunk consumed
-            if (lane < cnt) stage_raw_bwd(p, raw, lane, V, sS, ratio_now());
+            if (lane < cnt) stage_raw_bwd<LIGHT>(p, raw, lane, V, sS, ratio_now(), sg_tab());
             {   // prefetch the next chunk (of this Gaussian or of the wave's next one)
                 const bool more = s0 + 64 < Ns;
                 const int gn = more ? g : g + gstep;
@@ -1134,6 +1239,12 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
                         }
                         sS[s * BREC + (k < 3 ? 12 + k : BREC - 1)] = gk;
                     }
+                    if constexpr (LIGHT == LIGHT_SG) {   // the adjoint of L_k of this sample, parked for sg_chunk_adjoint
+                        const uint32_t fl = __builtin_bit_cast(uint32_t, r[16]);
+                        const float xk = k == 0 ? xg[0] + gmig[0] : (k == 1 ? xg[1] + gmig[1] : xg[2] + gmig[2]);
+                        if (k < 3) sS[s * BREC + 16 + k] = ((fl >> (28 + k)) & 1u) ? xk * r[15] : 0.f;
+                        continue;
+                    }
                     const uint32_t xy = __builtin_bit_cast(uint32_t, r[16]);
                     const int tx = (int)(xy & 0x3fffu) - 1 + (k & 1), ty = (int)((xy >> 14) & 0x3fffu) - 1 + (k >> 1);
                     const float fx = r[17], fy = r[18];
@@ -1177,6 +1288,13 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
                     const int i = lane + 64 * j;
                     if (i < 3 * cnt) out[i] = RATIO ? sS[(i / 3) * BREC + 12 + (i % 3)] * rsc : sS[(i / 3) * BREC + 12 + (i % 3)];
                 }
+            }
+            // (the surfel's ~50 constants are picked up from its LDS record again behind the lobe loop instead of being carried across it:
+            // with them live the loop does not fit the kernel's 168 registers)
+            if constexpr (LIGHT == LIGHT_SG) {
+                sg_chunk_adjoint(sS, cnt, sg_tab(), sEnv, sg_count(), lane);
+                wave_lds_sync();
+                SHADE_LOAD_REC()
             }
         }
         // per-Gaussian chain rule of the sums: a2 = r^4, kk = (r^2 + 2r + 1)/8 (through nom1 and nom2), NoV -> Nh
@@ -1238,13 +1356,22 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
         }
         __syncthreads();
     }
-    if (!VIEW && env_in_lds) {
+    if constexpr (LIGHT == LIGHT_SG) {   // (from the top down: the zeroing loop's address is not worth a register across the kernel)
+        if (!VIEW) {
+            for (int i = 8 * sg_count() - 1 - (int)threadIdx.x; i >= 0; i -= BWAVES * 64) {
+                const float v = (float)sEnv[i];
+                if (v != 0.f) atomic_add_f32(&a.d_envtab[i], v);
+            }
+        }
+    } else if (!VIEW && env_in_lds) {
         for (int i = threadIdx.x; i < ntex; i += BWAVES * 64) {
             const float v = (float)sEnv[i];
             if (v != 0.f) atomic_add_f32(&a.d_envtab[i], v);
         }
     }
 }
+
+#undef SHADE_LOAD_REC
 
 // dL/d env_raw = dL/d f(env) * f'(env);  softplus' = sigmoid
 __global__ void __launch_bounds__(BLOCK) env_grad_kernel(const float* __restrict__ env, const float* __restrict__ dtab,
@@ -1266,7 +1393,103 @@ __global__ void __launch_bounds__(BLOCK) env_grad_kernel(const float* __restrict
     denv[i] = softplus ? dtab[i] * (x > 20.f ? 1.f : 1.f / (1.f + expf(-x))) : dtab[i];
 }
 
+// ---- spherical-Gaussian light: the small kernels around the LIGHT_SG instantiations (sg_light.hpp) ----------------------------------
+// prologue (one launch, the role shade_prologue_kernel plays for the texture): the prepared lobe table, the lattice table when the
+// directions are generated in-kernel (t.env == nullptr: shade_table_entry builds the lattice part only) and the clear of the backward's
+// table-space gradient accumulator
+__global__ void __launch_bounds__(BLOCK) sg_prologue_kernel(const float* __restrict__ lobes, int M, float4* __restrict__ tab, const ShadeTables t) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < M) sg_table_entry(lobes, i, tab);
+    shade_table_entry(t, i);
+    for (int j = i; j < t.nzero; j += gridDim.x * BLOCK) t.zero[j] = 0.f;
+}
+
+// svgir_sg_eval: DirectLightSG.direct_light for n directions, one per thread, the table in LDS
+__global__ void __launch_bounds__(BLOCK) sg_eval_kernel(const float4* __restrict__ tab, int M, size_t n, const float* __restrict__ dirs,
+                                                        float* __restrict__ out) {
+    __shared__ float4 st[2 * SVGIR_SG_MAX_LOBES];
+    for (int i = threadIdx.x; i < 2 * M; i += BLOCK) st[i] = tab[i];
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float d[3] = {dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]};
+    float L[3];
+    sg_eval(st, M, d, L);
+    out[i * 3] = L[0]; out[i * 3 + 1] = L[1]; out[i * 3 + 2] = L[2];
+}
+
+// The counterpart of env_grad_kernel: the table-space sums {G.xyz, d|lambda|, d|mu|.rgb, -} per lobe (shade_bwd_kernel) pulled back to the
+// raw [M,7]:  a = xi / |xi|  =>  dxi = |lambda| (G - a (a.G)) / |xi|;  |.|  =>  the sign of the raw value, sign(0) = 0 as for torch's abs
+__global__ void __launch_bounds__(BLOCK) sg_grad_kernel(const float* __restrict__ lobes, const float4* __restrict__ tab, const float* __restrict__ dtab,
+                                                        float* __restrict__ dlobes, int M, const float* __restrict__ ratio_part, int nparts,
+                                                        float* __restrict__ d_ratio) {
+    if (d_ratio) {   // dL/d(radiance_ratio): the workgroups' partial sums (<= 256), a fixed tree (as env_grad_kernel; one block)
+        __shared__ float part[BLOCK];
+        part[threadIdx.x] = (int)threadIdx.x < nparts ? ratio_part[threadIdx.x] : 0.f;
+        __syncthreads();
+        for (int h = BLOCK / 2; h >= 1; h >>= 1) {
+            if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) *d_ratio = part[0];
+    }
+    const int m = threadIdx.x;
+    if (m >= M) return;
+    auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); };
+    const float4 al = tab[2 * m], mu = tab[2 * m + 1];
+    const float* g = dtab + 8 * m;
+    const float* l = lobes + 7 * m;
+    const float ag = al.x * g[0] + al.y * g[1] + al.z * g[2];
+    const float sc = al.w * mu.w;   // |lambda| / |xi|
+    float* o = dlobes + 7 * m;
+    o[0] = sc * (g[0] - al.x * ag); o[1] = sc * (g[1] - al.y * ag); o[2] = sc * (g[2] - al.z * ag);
+    o[3] = sgn(l[3]) * g[3];
+    o[4] = sgn(l[4]) * g[4]; o[5] = sgn(l[5]) * g[5]; o[6] = sgn(l[6]) * g[6];
+}
+
+static_assert(SVGIR_SG_MAX_LOBES <= BLOCK, "sg_grad_kernel: one thread per lobe, one block");
+
+template <int LIGHT>
+void launch_shade_fwd(const ShadeArgs& a, size_t light_lds, hipStream_t s) {
+    const svgir_shade_params* p = &a.p;
+#ifndef SHADE_FWD_QUAD
+#define SHADE_FWD_QUAD 1
+#endif
+#ifndef SHADE_FWD_QUAD_MAX_NS
+#define SHADE_FWD_QUAD_MAX_NS 128
+#endif
+    // The quad layout removes the per-surfel fixed costs (250 -> 202 us at P = 200 k, Ns = 64); with hundreds of samples per surfel
+    // those are amortised anyway and the one-wave-per-surfel kernel streams the samples better (lane = sample: 768 contiguous bytes
+    // per load; 771 us against 1 001 us at Ns = 384)
+    if (SHADE_FWD_QUAD && p->Ns <= SHADE_FWD_QUAD_MAX_NS) {
+        const size_t lds = (size_t)4 * (FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF) * 4 + light_lds;
+        if (p->radiance_ratio) hipLaunchKernelGGL((shade_fwd_quad_kernel<true, LIGHT>), dim3((p->P + 4 * FQ_SURF - 1) / (4 * FQ_SURF)), dim3(BLOCK), lds, s, a);
+        else hipLaunchKernelGGL((shade_fwd_quad_kernel<false, LIGHT>), dim3((p->P + 4 * FQ_SURF - 1) / (4 * FQ_SURF)), dim3(BLOCK), lds, s, a);
+    } else {
+        const size_t lds = (size_t)4 * (64 * SREC + 80 + 32) * 4 + light_lds;
+        if (p->radiance_ratio) hipLaunchKernelGGL((shade_fwd_kernel<true, LIGHT>), dim3((p->P + 3) / 4), dim3(BLOCK), lds, s, a);
+        else hipLaunchKernelGGL((shade_fwd_kernel<false, LIGHT>), dim3((p->P + 3) / 4), dim3(BLOCK), lds, s, a);
+    }
+}
+
+// > 64 KB of dynamic LDS needs the opt-in, once per device and light kind (idempotent, so races are harmless)
+template <int LIGHT>
+int shade_bwd_lds_opt_in() {
+    static bool attr_set[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return SVGIR_ERR_HIP;
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        for (const void* f : {reinterpret_cast<const void*>(shade_bwd_kernel<false, false, LIGHT>), reinterpret_cast<const void*>(shade_bwd_kernel<true, false, LIGHT>),
+                              reinterpret_cast<const void*>(shade_bwd_kernel<false, true, LIGHT>), reinterpret_cast<const void*>(shade_bwd_kernel<true, true, LIGHT>)})
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SVGIR_ERR_HIP;
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    return 0;
+}
+
 }  // namespace
+
+int report_error(int code, const char* fmt, ...);   // api.hip (it owns the per-thread message behind svgir_last_error): records it, returns `code`
 
 }  // namespace svgir
 
@@ -1312,27 +1535,129 @@ int svgir::shade_forward_impl(const svgir_shade_params* p, float* reduced, float
     ShadeArgs a;
     a.p = *p; a.reduced = reduced; a.features = features; a.vfeatures = vfeatures;
     // (subset launches: the rows of the surfels outside the subset are zero-filled by the shading kernel's own waves)
-#ifndef SHADE_FWD_QUAD
-#define SHADE_FWD_QUAD 1
-#endif
-#ifndef SHADE_FWD_QUAD_MAX_NS
-#define SHADE_FWD_QUAD_MAX_NS 128
-#endif
-    // The quad layout removes the per-surfel fixed costs (250 -> 202 us at P = 200 k, Ns = 64); with hundreds of samples per surfel
-    // those are amortised anyway and the one-wave-per-surfel kernel streams the samples better (lane = sample: 768 contiguous bytes
-    // per load; 771 us against 1 001 us at Ns = 384)
-    if (SHADE_FWD_QUAD && p->Ns <= SHADE_FWD_QUAD_MAX_NS) {
-        const size_t lds = (size_t)4 * (FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF) * 4;
-        if (p->radiance_ratio) hipLaunchKernelGGL(shade_fwd_quad_kernel<true>, dim3((p->P + 4 * FQ_SURF - 1) / (4 * FQ_SURF)), dim3(BLOCK), lds, s, a);
-        else hipLaunchKernelGGL(shade_fwd_quad_kernel<false>, dim3((p->P + 4 * FQ_SURF - 1) / (4 * FQ_SURF)), dim3(BLOCK), lds, s, a);
-    } else {
-        const size_t lds = (size_t)4 * (64 * SREC + 80 + 32) * 4;
-        if (p->radiance_ratio) hipLaunchKernelGGL(shade_fwd_kernel<true>, dim3((p->P + 3) / 4), dim3(BLOCK), lds, s, a);
-        else hipLaunchKernelGGL(shade_fwd_kernel<false>, dim3((p->P + 3) / 4), dim3(BLOCK), lds, s, a);
-    }
+    launch_shade_fwd<LIGHT_TEX>(a, 0, s);
     stage_mark(tm, "shade_fwd");
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
+
+// ---- spherical-Gaussian light (include/svgir_raster.h "Spherical-Gaussian direct light") --------------------------------------------
+namespace {
+
+int sg_light_check(const svgir_sg_light* l, const char* who) {
+    if (!l) return report_error(SVGIR_ERR_INVALID, "%s: light is NULL", who);
+    if (l->count < 1 || l->count > SVGIR_SG_MAX_LOBES)
+        return report_error(SVGIR_ERR_INVALID, "%s: light.count = %d, 1 ... %d lobes", who, l->count, SVGIR_SG_MAX_LOBES);
+    if (!l->lobes || !l->work) return report_error(SVGIR_ERR_INVALID, "%s: light.lobes / light.work is NULL", who);
+    if ((uintptr_t)l->work & 15) return report_error(SVGIR_ERR_INVALID, "%s: light.work must be 16-byte aligned (read as float4)", who);
+    return 0;
+}
+
+// what the two shading entry points ask of svgir_shade_params (the env* fields are not read)
+int sg_params_check(const svgir_shade_params* p, const char* who) {
+    if (!p || p->P < 0 || p->Ns <= 0) return report_error(SVGIR_ERR_INVALID, "%s: bad P / Ns", who);
+    if (p->subset || p->subset_count)
+        return report_error(SVGIR_ERR_INVALID, "%s: subset shading belongs to the rasterizer-fused path, which has no SG light", who);
+    if (p->P > 0 && (!p->base_color || !p->roughness || !p->normals || !p->viewdirs || !p->radiance || !p->visibility))
+        return report_error(SVGIR_ERR_INVALID, "%s: a material / incident input is NULL", who);
+    if (p->P > 0 && !p->incident_dirs && !(p->lattice_normals && p->lattice_work))
+        return report_error(SVGIR_ERR_INVALID, "%s: neither incident_dirs nor the lattice inputs are given", who);
+    if (p->lattice_work && ((uintptr_t)p->lattice_work & 15)) return report_error(SVGIR_ERR_INVALID, "%s: lattice_work must be 16-byte aligned", who);
+    return 0;
+}
+
+// the kernels' view of the call: the light travels in the (otherwise unread) env fields of the kernels' private copy of the parameters
+svgir_shade_params sg_kernel_params(const svgir_shade_params* p, const svgir_sg_light* l) {
+    svgir_shade_params q = *p;
+    q.env = l->lobes; q.env_work = l->work; q.env_h = 1; q.env_w = l->count; q.env_softplus = 0; q.env_scale = 1.f; q.env_transform = nullptr;
+    return q;
+}
+
+void launch_sg_prologue(const svgir_sg_light* l, const svgir_shade_params* p, float* zero, int nzero, hipStream_t s) {
+    ShadeTables t;
+    if (p) { t.Ns = p->Ns; t.lat_tab = p->incident_dirs ? (float4*)nullptr : (float4*)p->lattice_work; }
+    t.zero = zero; t.nzero = nzero;
+    const int n = std::max(l->count, t.lat_tab ? t.Ns : 0);
+    hipLaunchKernelGGL(sg_prologue_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, l->lobes, l->count, (float4*)l->work, t);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t svgir_sg_grad_work_bytes(int32_t count) {
+    return count > 0 ? ((size_t)8 * (size_t)count + SVGIR_SHADE_RATIO_WORK) * sizeof(float) : 0;
+}
+
+int svgir_sg_eval(const svgir_sg_light* light, int64_t n, const float* dirs, float* out, void* stream) {
+    if (int rc = sg_light_check(light, "sg_eval")) return rc;
+    if (n < 0 || (n > 0 && (!dirs || !out))) return report_error(SVGIR_ERR_INVALID, "sg_eval: bad n / NULL dirs or out");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    launch_sg_prologue(light, nullptr, nullptr, 0, s);
+    hipLaunchKernelGGL(sg_eval_kernel, dim3((unsigned)(((size_t)n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const float4*)light->work, light->count,
+                       (size_t)n, dirs, out);
+    return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+}
+
+int svgir_shade_forward_sg(const svgir_shade_params* p, const svgir_sg_light* light, float* reduced, float* features, float* vfeatures,
+                           void* stream) {
+    if (int rc = sg_params_check(p, "shade_forward_sg")) return rc;
+    if (int rc = sg_light_check(light, "shade_forward_sg")) return rc;
+    if (vfeatures && !p->viewmatrix) return report_error(SVGIR_ERR_INVALID, "shade_forward_sg: vfeatures needs viewmatrix");
+    if (p->P == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    StageMarks tm = stage_begin(s);
+    launch_sg_prologue(light, p, nullptr, 0, s);
+    stage_mark(tm, "shade_sg_table");
+    ShadeArgs a;
+    a.p = sg_kernel_params(p, light); a.reduced = reduced; a.features = features; a.vfeatures = vfeatures;
+    launch_shade_fwd<LIGHT_SG>(a, (size_t)8 * light->count * sizeof(float), s);
+    stage_mark(tm, "shade_fwd_sg");
+    return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+}
+
+int svgir_shade_backward_sg(const svgir_shade_params* p, const svgir_sg_light* light, const float* dL_dreduced, const float* dL_dfeatures,
+                            const float* dL_dvfeatures, float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance,
+                            float* dL_dlobes, float* grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream) {
+    if (int rc = sg_params_check(p, "shade_backward_sg")) return rc;
+    if (int rc = sg_light_check(light, "shade_backward_sg")) return rc;
+    if ((!dL_dreduced && !dL_dfeatures && !dL_dvfeatures) || (dL_dvfeatures && !p->viewmatrix) || !dL_dbase_color || !dL_droughness || !dL_dnormals ||
+        !dL_dlobes || !grad_work)
+        return report_error(SVGIR_ERR_INVALID, "shade_backward_sg: an upstream gradient, an output or grad_work is missing");
+    if ((!dL_dradiance && !p->radiance_ratio) || (dL_dradiance_ratio && !p->radiance_ratio))
+        return report_error(SVGIR_ERR_INVALID, "shade_backward_sg: dL_dradiance / dL_dradiance_ratio do not match radiance_ratio");
+    hipStream_t s = (hipStream_t)stream;
+    const int M = light->count, ntab = 8 * M;
+    StageMarks tm = stage_begin(s);
+    launch_sg_prologue(light, p, grad_work, ntab, s);   // (also when P == 0: dL_dlobes is then all zeros)
+    ShadeBwdArgs a;
+    a.p = sg_kernel_params(p, light); a.g_red = dL_dreduced; a.g_feat = dL_dfeatures; a.g_vfeat = dL_dvfeatures; a.d_base = dL_dbase_color;
+    a.d_rough = dL_droughness; a.d_normals = dL_dnormals; a.d_radiance = dL_dradiance; a.d_envtab = grad_work; a.d_viewdirs = dL_dviewdirs;
+    a.ratio_part = dL_dradiance_ratio ? grad_work + ntab : nullptr;   // (SVGIR_SHADE_RATIO_WORK floats behind the table-space sums)
+    a.zero_rest = 0;
+    const bool ratio = p->radiance_ratio != nullptr;
+    // the waves' records, the fp64 sums (8 M doubles) and the prepared table (8 M floats): 110 KB at M = 128, one workgroup per CU
+    const size_t lds = BWAVES * (size_t)(64 * BREC + 4 * KB_G * KREC) * 4 + (size_t)ntab * 8 + (size_t)ntab * 4;
+    if (int rc = shade_bwd_lds_opt_in<LIGHT_SG>()) return rc;
+    const int blocks = std::max(1, std::min((p->P + BWAVES - 1) / BWAVES, 256 * std::max(1, SHADE_BWPE * 4 / BWAVES)));
+    stage_mark(tm, "shade_bwd_sg_prologue");
+    if (p->P > 0) {
+        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, false, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 1);
+        else hipLaunchKernelGGL((shade_bwd_kernel<false, false, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 1);
+    }
+    stage_mark(tm, "shade_bwd_sg");
+    hipLaunchKernelGGL(sg_grad_kernel, dim3(1), dim3(BLOCK), 0, s, light->lobes, (const float4*)light->work, grad_work, dL_dlobes, M,
+                       a.ratio_part, p->P > 0 ? blocks : 0, dL_dradiance_ratio);   // (P == 0: the scalar's gradient is 0 too)
+    stage_mark(tm, "shade_sg_grad");
+    if (dL_dviewdirs && p->P > 0) {   // the view-direction pass: the same grid and LDS layout (the sums' slots stay unused)
+        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, true, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 0);
+        else hipLaunchKernelGGL((shade_bwd_kernel<false, true, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 0);
+        stage_mark(tm, "shade_bwd_view_sg");
+    }
+    return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+}
+
+}  // extern "C"
 
 extern "C" {
 

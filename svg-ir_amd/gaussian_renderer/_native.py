@@ -71,6 +71,14 @@ class ShadeParams(C.Structure):
                 ("subset", C.c_void_p), ("subset_count", C.c_void_p), ("radiance_ratio", C.c_void_p)]
 
 
+class SgLight(C.Structure):
+    """svgir_sg_light: the spherical-Gaussian direct light of svgir_sg_eval / svgir_shade_forward_sg / svgir_shade_backward_sg."""
+    _fields_ = [("count", C.c_int32), ("lobes", C.c_void_p), ("work", C.c_void_p)]
+
+
+SG_MAX_LOBES = 128   # SVGIR_SG_MAX_LOBES
+
+
 class FusedShade(C.Structure):
     """svgir_fused_shade: the shading of a view run inside svgir_forward / svgir_backward for the view's working set."""
     _fields_ = [("sp", ShadeParams), ("reduced", C.c_void_p), ("all_surfels", C.c_int32)]
@@ -202,6 +210,15 @@ def _load():
     lib.svgir_albedo_scale_partials.argtypes = [C.c_int32] * 2
     lib.svgir_albedo_scale.restype = C.c_int
     lib.svgir_albedo_scale.argtypes = [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 4
+    # the spherical-Gaussian direct light (gaussian_renderer/shading.py): the light block, device pointers, stream
+    lib.svgir_sg_grad_work_bytes.restype = C.c_size_t
+    lib.svgir_sg_grad_work_bytes.argtypes = [C.c_int32]
+    lib.svgir_sg_eval.restype = C.c_int
+    lib.svgir_sg_eval.argtypes = [C.POINTER(SgLight), C.c_int64] + [C.c_void_p] * 3
+    lib.svgir_shade_forward_sg.restype = C.c_int
+    lib.svgir_shade_forward_sg.argtypes = [C.POINTER(ShadeParams), C.POINTER(SgLight)] + [C.c_void_p] * 4
+    lib.svgir_shade_backward_sg.restype = C.c_int
+    lib.svgir_shade_backward_sg.argtypes = [C.POINTER(ShadeParams), C.POINTER(SgLight)] + [C.c_void_p] * 12
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -224,7 +241,8 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_geometry_loss_forward", "svgir_geometry_loss_backward", "svgir_smooth_loss_partials", "svgir_smooth_loss_forward",
            "svgir_smooth_loss_backward", "svgir_env_backdrop", "svgir_radiance_loss_work_bytes", "svgir_radiance_loss_forward",
            "svgir_radiance_loss_backward", "svgir_activate_partials", "svgir_activate_forward", "svgir_activate_backward",
-           "svgir_view_metrics_partials", "svgir_view_metrics", "svgir_capture_u8", "svgir_albedo_scale_partials", "svgir_albedo_scale")
+           "svgir_view_metrics_partials", "svgir_view_metrics", "svgir_capture_u8", "svgir_albedo_scale_partials", "svgir_albedo_scale",
+           "svgir_sg_grad_work_bytes", "svgir_sg_eval", "svgir_shade_forward_sg", "svgir_shade_backward_sg")
 
 
 _scope = threading.local()

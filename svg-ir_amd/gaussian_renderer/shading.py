@@ -9,6 +9,10 @@ right before the svgss rasterizer call:
 `shade_and_pack(...)` additionally fuses the packing and returns the rasterizer's `features` / `vfeatures`.
 The compute is `svgir_shade_forward` / `svgir_shade_backward` of libsvgir_raster.so (csrc/shade.hip); there is no
 PyTorch fallback.
+
+The direct light is one of the reference's three classes: `DirectLightMap` (`.env`) and `EnvLight` (`.envmap`), lat-long textures, or
+`DirectLightSG` (`.lgtSGs` [M,7], scene/direct_light_sg.py), a mixture of spherical-Gaussian lobes evaluated per sample inside the
+kernels (`svgir_shade_forward_sg` / `svgir_shade_backward_sg`); `sg_direct_light` / `compute_envmap` are that light on its own.
 """
 import ctypes as C
 
@@ -97,14 +101,14 @@ def _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs
                                       None if lattice else dirs, areas, env, viewmatrix, env_transform)]
     bc, ro, nr, vd, ra, vi, di, ar, en, vm, et = keep
     P, Ns = ra.shape[0], ra.shape[1]
-    env_h, env_w = en.shape[-3], en.shape[-2]
+    env_h, env_w = (en.shape[-3], en.shape[-2]) if en is not None else (0, 0)   # (no texture: the SG light, _sg_light)
     work = torch.empty(env_h * env_w * 4, dtype=torch.float32, device=dev)   # f(env), one float4 per texel
     p = ShadeParams()
     p.P, p.Ns, p.env_h, p.env_w = P, Ns, env_h, env_w
     p.env_softplus, p.training, p.env_scale = int(bool(softplus)), int(bool(training)), float(scale)
     p.base_color, p.roughness, p.normals, p.viewdirs = N.ptr(bc), N.ptr(ro), N.ptr(nr), N.ptr(vd)
     p.radiance, p.visibility, p.incident_dirs, p.incident_areas = N.ptr(ra), N.ptr(vi), N.ptr(di), N.ptr(ar)
-    p.env, p.viewmatrix, p.env_work, p.env_transform = N.ptr(en), N.ptr(vm), work.data_ptr(), N.ptr(et)
+    p.env, p.viewmatrix, p.env_work, p.env_transform = N.ptr(en), N.ptr(vm), N.ptr(work), N.ptr(et)
     keep.append(work)
     if ratio is not None:   # get_radiances = nan_to_num(_radiances.detach() * _radiance_ratio) inside the kernels (gaussian_model.py:323-324)
         if ratio.numel() != 1:
@@ -223,6 +227,120 @@ class _ShadePack(torch.autograd.Function):
         return (d_base, d_rough, d_norm, d_view, d_rad, None, None, None, d_env, None, None, None, None, None, d_ratio, None)
 
 
+# ---- spherical-Gaussian direct light (scene/direct_light_sg.py:DirectLightSG; include/svgir_raster.h) ---------------------------------
+
+class SGLobes:
+    """The checked raw lobes of a light object exposing `.lgtSGs`: [M, 7] = (axis, sharpness, amplitude), 1 <= M <= SVGIR_SG_MAX_LOBES."""
+
+    def __init__(self, lgtSGs):
+        if lgtSGs.dim() != 2 or lgtSGs.shape[1] != 7 or not 1 <= lgtSGs.shape[0] <= N.SG_MAX_LOBES:
+            raise RuntimeError(f"lgtSGs must be [M, 7] with 1 <= M <= {N.SG_MAX_LOBES}, got {tuple(lgtSGs.shape)}")
+        self.lobes = lgtSGs
+
+
+def _is_sg(light):
+    return hasattr(light, "lgtSGs")
+
+
+def _no_sg(light, what):
+    if _is_sg(light):
+        raise TypeError(f"{what} has no spherical-Gaussian (lgtSGs) light path: it needs the lat-long texture of DirectLightMap / EnvLight "
+                        f"(with an SG light use the unfused calls: shade_and_pack + the rasterizer, sg_direct_light)")
+
+
+def _sg_light(lobes, dev):
+    """(svgir_sg_light, keep-alive list) of raw lobes [M, 7]."""
+    lb = N.f32c(lobes.detach(), dev)
+    work = torch.empty(8 * lb.shape[0], dtype=torch.float32, device=dev)
+    lt = N.SgLight()
+    lt.count, lt.lobes, lt.work = lb.shape[0], lb.data_ptr(), work.data_ptr()
+    return lt, [lb, work]
+
+
+def sg_direct_light(lgtSGs, dirs):
+    """DirectLightSG.direct_light / render_envmap_sg (scene/direct_light_sg.py:10-46): the unclamped light [..., 3] of the directions
+    `dirs` [..., 3] (used as given, not normalised).  Forward only: no gradient reaches `lgtSGs` or `dirs` through this call."""
+    dev = lgtSGs.device
+    if dev.type != "cuda":
+        raise RuntimeError("sg_direct_light: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
+    lt, keep = _sg_light(SGLobes(lgtSGs).lobes, dev)
+    d = N.f32c(dirs.detach(), dev)
+    out = N.out_tensor(d.shape, torch.float32, dev)
+    n = d.numel() // 3
+    if n:
+        N.check(N.lib.svgir_sg_eval(lt, n, d.data_ptr(), out.data_ptr(), N.stream_ptr(dev)), "sg_eval")
+    return out
+
+
+def compute_envmap(lgtSGs, H, W, upper_hemi=False):
+    """scene/direct_light_sg.py:66-80: the light on the reference's [H, W] grid of directions (the Blender convention), [H, W, 3]."""
+    dev = lgtSGs.device
+    phi, theta = torch.meshgrid([torch.linspace(0., torch.pi / 2. if upper_hemi else torch.pi, H), torch.linspace(1.0 * torch.pi, -1.0 * torch.pi, W)],
+                                indexing="ij")
+    viewdirs = torch.stack([torch.cos(theta) * torch.sin(phi), torch.sin(theta) * torch.sin(phi), torch.cos(phi)], dim=-1)
+    return sg_direct_light(lgtSGs, viewdirs.to(dev))
+
+
+class _ShadeSG(torch.autograd.Function):
+    """_Shade / _ShadePack with the SG light (svgir_shade_forward_sg / svgir_shade_backward_sg): returns reduced [P,70], or with `pack`
+    (features, vfeatures, reduced); differentiable w.r.t. base_color, roughness, normals, radiance, the raw lobes, the ratio (and
+    viewdirs: view_gradient)."""
+
+    @staticmethod
+    def forward(ctx, base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, lobes, viewmatrix, pack, training,
+                ratio=None, view_gradient=False):
+        p, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, None, False, 1.0,
+                                            viewmatrix=viewmatrix, training=training, ratio=ratio)
+        lt, lkeep = _sg_light(lobes, dev)
+        S, VS = (4, 52) if training else (7, 64)
+        red = N.out_tensor((P, NRED), torch.float32, dev)
+        feats = N.out_tensor((P, S), torch.float32, dev) if pack else None
+        vfeats = N.out_tensor((P, VS), torch.float32, dev) if pack else None
+        if P:
+            N.check(N.lib.svgir_shade_forward_sg(p, lt, red.data_ptr(), N.ptr(feats), N.ptr(vfeats), N.stream_ptr(dev)), "shade_forward_sg")
+        lat = dirs if isinstance(dirs, FibonacciLattice) else None
+        ctx.save_for_backward(base_color, roughness, normals, viewdirs, radiance, visibility, None if lat else dirs, areas, lobes,
+                              viewmatrix, ratio)
+        ctx.cfg = (pack, training, lat, bool(view_gradient))
+        if pack:
+            ctx.set_materialize_grads(False)
+            return feats, vfeats, red
+        return red
+
+    @staticmethod
+    def backward(ctx, *gs):
+        base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, lobes, viewmatrix, ratio = ctx.saved_tensors
+        pack, training, lat, view = ctx.cfg
+        g_feat, g_vfeat, g_red = gs if pack else (None, None, gs[0])
+        if g_feat is None and g_vfeat is None and g_red is None:
+            return (None,) * 14
+        view = view and ctx.needs_input_grad[3]
+        p, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, lat if lat is not None else dirs,
+                                            areas, None, False, 1.0, viewmatrix=viewmatrix, training=training, ratio=ratio)
+        lt, lkeep = _sg_light(lobes, dev)
+        gr, gf, gv = (N.f32c(t, dev) for t in (g_red, g_feat, g_vfeat))
+        d_base, d_rough, d_norm = (N.out_tensor(keep[i].shape, torch.float32, dev) for i in (0, 1, 2))
+        d_lobes = N.out_tensor(lkeep[0].shape, torch.float32, dev)
+        want_ratio = ratio is not None and ctx.needs_input_grad[12]
+        want_rad = ratio is None or ctx.needs_input_grad[4]
+        d_ratio = N.out_tensor((1,), torch.float32, dev) if want_ratio else None
+        d_rad = N.out_tensor(keep[4].shape, torch.float32, dev) if want_rad else None
+        d_view = N.out_tensor(keep[3].shape, torch.float32, dev) if view else None
+        gwork = torch.empty(N.lib.svgir_sg_grad_work_bytes(lt.count) // 4, dtype=torch.float32, device=dev)
+        if P:
+            N.check(N.lib.svgir_shade_backward_sg(p, lt, N.ptr(gr), N.ptr(gf), N.ptr(gv), d_base.data_ptr(), d_rough.data_ptr(),
+                                                  d_norm.data_ptr(), N.ptr(d_rad), d_lobes.data_ptr(), gwork.data_ptr(), N.ptr(d_ratio),
+                                                  N.ptr(d_view), N.stream_ptr(dev)), "shade_backward_sg")
+        else:
+            d_lobes.zero_()
+            if d_ratio is not None:
+                d_ratio.zero_()
+        return (d_base.reshape(base_color.shape), d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape),
+                None if d_view is None else d_view.reshape(viewdirs.shape), None if d_rad is None else d_rad.reshape(radiance.shape),
+                None, None, None, d_lobes.reshape(lobes.shape), None, None, None,
+                None if d_ratio is None else d_ratio.reshape(ratio.shape), None)
+
+
 def _env_of(light):
     """(env texture [.., He, We, 3], softplus flag, scale, lookup transform [3,3] or None) for the reference's two
     light classes."""
@@ -234,7 +352,7 @@ def _env_of(light):
         N.check(N.lib.svgir_resample_bilinear(src.data_ptr(), src.shape[0], src.shape[1], src.shape[2], env.data_ptr(), 32, 64,
                                               N.stream_ptr(src.device)), "resample_bilinear")
         return env, False, 1.0, getattr(light, "transform", None)   # lookup direction = dirs @ transform.T
-    raise TypeError("direct_light_env_light must expose .env (DirectLightMap) or .envmap (EnvLight)")
+    raise TypeError("direct_light_env_light must expose .env (DirectLightMap), .envmap (EnvLight) or .lgtSGs (DirectLightSG)")
 
 
 def rendering_equation4(base_color, roughness, normals, viewdirs, radiance, direct_light_env_light=None,
@@ -248,9 +366,13 @@ def rendering_equation4(base_color, roughness, normals, viewdirs, radiance, dire
     _radiance_ratio) (gaussian_model.py:323-324); pass the RAW cache as `radiance` and the scalar here and the kernels form the product
     themselves -- no [n, Ns, 3] temporaries, and the backward returns the scalar's gradient directly."""
     dirs, areas = incident_dirs_precompute, incident_areas_precompute
-    env, softplus, scale, transform = _env_of(direct_light_env_light)
-    red = _Shade.apply(base_color, roughness, normals, viewdirs, radiance, visibility_precompute, dirs, areas, env,
-                       softplus, scale, transform, radiance_ratio, bool(view_gradient))
+    if _is_sg(direct_light_env_light):   # scene/direct_light_sg.py: the mixture of lobes, evaluated per sample inside the kernels
+        red = _ShadeSG.apply(base_color, roughness, normals, viewdirs, radiance, visibility_precompute, dirs, areas,
+                             SGLobes(direct_light_env_light.lgtSGs).lobes, None, False, True, radiance_ratio, bool(view_gradient))
+    else:
+        env, softplus, scale, transform = _env_of(direct_light_env_light)
+        red = _Shade.apply(base_color, roughness, normals, viewdirs, radiance, visibility_precompute, dirs, areas, env,
+                           softplus, scale, transform, radiance_ratio, bool(view_gradient))
     extra_results = {
         # (with a FibonacciLattice the [n, Ns, 3] tensor is never built: an empty stand-in keeps the chunk loop's
         #  torch.cat over every key working, `incident_dirs_precompute.dirs()` materialises the real thing)
@@ -276,6 +398,10 @@ def shade_and_pack(base_color, roughness, normals, viewdirs, radiance, direct_li
     """Shading + the packing of svgss.py:143-166: returns (features [n,S], vfeatures [n,VS], reduced [n,70]).
     The packing and its adjoint are done inside the kernels in both the no-grad and the autograd path.
     `view_gradient`: see rendering_equation4."""
+    if _is_sg(direct_light_env_light):
+        return _ShadeSG.apply(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas,
+                              SGLobes(direct_light_env_light.lgtSGs).lobes, viewmatrix, True, bool(is_training), radiance_ratio,
+                              bool(view_gradient))
     env, softplus, scale, transform = _env_of(direct_light_env_light)
     return _ShadePack.apply(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, viewmatrix,
                             softplus, scale, bool(is_training), transform, radiance_ratio, bool(view_gradient))
@@ -380,6 +506,7 @@ def fused_shade(base_color, roughness, normals, viewdirs, radiance, direct_light
                 is_training, reduced=None, all_surfels=False, radiance_ratio=None):
     """(`_native.FusedShade`, keep-alive list) for the `shade=` keyword of `_C.rasterize_gaussians{,_backward}`: the binding-level
     form of render_shaded (no autograd)."""
+    _no_sg(direct_light_env_light, "fused_shade (the shading inside svgir_forward / svgir_backward)")
     env, softplus, scale, transform = _env_of(direct_light_env_light)
     sp, keep, *_ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, softplus, scale,
                            viewmatrix=viewmatrix, training=bool(is_training), env_transform=transform, ratio=radiance_ratio)
@@ -393,7 +520,16 @@ def render_shaded(raster_settings, means3D, means2D, opacities, shs, scales, rot
     surfels the view reads.  Returns the rasterizer's 9-tuple (num_rendered, color, normal, opacity, depth, feature, vfeature,
     weights, radii) and `reduced` [P,70] (rows of unshaded surfels zero; an empty tensor unless want_reduced).
     all_surfels=True shades every surfel (needed when a loss reads `reduced` directly: the reference's lambda_light term,
-    svgss.py:359-364).  `view_gradient`: see rendering_equation4 (svgir_grads.dL_dviewdirs)."""
+    svgss.py:359-364).  `view_gradient`: see rendering_equation4 (svgir_grads.dL_dviewdirs).
+    With a spherical-Gaussian light (`.lgtSGs`) the unfused sequence runs -- shade_and_pack over all P surfels, then the rasterizer --
+    whose results the fused one reproduces bit for bit (include/svgir_raster.h): svgir_fused_shade carries no SG light."""
+    if _is_sg(direct_light_env_light):
+        from .svgss_rasterization import GaussianRasterizer
+        feats, vfeats, red = shade_and_pack(base_color, roughness, normals, viewdirs, radiance, direct_light_env_light, visibility, dirs,
+                                            areas, raster_settings.viewmatrix, is_training, radiance_ratio, view_gradient=view_gradient)
+        out = GaussianRasterizer(raster_settings)(means3D=means3D, means2D=means2D, opacities=opacities, shs=shs, scales=scales,
+                                                  rotations=rotations, features=feats, vfeatures=vfeats)
+        return tuple(out), (red if want_reduced else torch.empty(0, dtype=torch.float32, device=means3D.device))
     env, softplus, scale, transform = _env_of(direct_light_env_light)
     out = _ShadedRasterize.apply(means3D, means2D, shs, opacities, scales, rotations, base_color, roughness, normals, viewdirs,
                                  radiance, visibility, dirs, areas, env, raster_settings, softplus, scale, bool(is_training),

@@ -164,6 +164,7 @@ def fused_radiance_loss(renderer, xyz, camera_center, geo_normal, incident_dirs,
     A row whose radiance or target is not finite makes the loss NaN, as in torch, but contributes to no gradient
     (include/svgir_raster.h)."""
     from gaussian_renderer import shading
+    shading._no_sg(light, "fused_radiance_loss")   # (radiance_loss with envmap = sg_direct_light(lgtSGs, dirs) * areas serves an SG light)
     env, softplus, scale, transform = shading._env_of(light)
     out = renderer.radiance_consistency(xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, env, softplus, scale,
                                         transform, normals12, albedos, roughnesses, radiances, radiance_ratio)

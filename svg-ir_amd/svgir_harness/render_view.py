@@ -206,6 +206,7 @@ def environment_backdrop(light, intrinsics, c2w, image, opacity, vfeature):
     the host; image [3,H,W], opacity [1,H,W], vfeature [>= 3,H,W]: the rasterizer's raw outputs (its first three vfeature planes are
     the pbr).  Returns {env_only, render_env, pbr_env}: [3,H,W] views of one buffer; they never require grad (the reference runs
     this tail under no_grad)."""
+    shading._no_sg(light, "environment_backdrop")   # (the backdrop kernel samples the lat-long texture; an SG light has none)
     dev = image.device
     if dev.type != "cuda" or opacity.device.type != "cuda" or vfeature.device.type != "cuda":
         raise RuntimeError("environment_backdrop: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")

@@ -14,6 +14,20 @@ class Light:
         self.env = env
 
 
+class SGLight:
+    """Minimal stand-in with the attribute the shading binding reads from scene.direct_light_sg.DirectLightSG: the raw lobes [M, 7]."""
+
+    def __init__(self, lgtSGs):
+        self.lgtSGs = lgtSGs
+
+
+def sg_lobes(M, seed=3, device="cpu"):
+    """DirectLightSG.__init__ (scene/direct_light_sg.py:87-88): randn [M, 7] with the sharpness column multiplied by 100."""
+    l = torch.randn(M, 7, generator=torch.Generator().manual_seed(seed))
+    l[:, 3] *= 100.0
+    return l.to(device)
+
+
 def fibonacci_dirs(normals, Ns):
     """Hemisphere directions around `normals` [P,3] -> [P,Ns,3] (z clamped to sin(10 deg) like the reference)."""
     dev = normals.device

@@ -46,13 +46,16 @@ class TrainStep:
     RAW = ("xyz", "scaling", "rotation", "opacity", "normal", "base_color", "roughness")
 
     def __init__(self, dev, seed=5, name="cfg3_train", Ns=64, fused=True, scene=None, radiance_grad=False, raw_params=False, activate=None, *,
-                 view_gradient=False):
+                 view_gradient=False, sg_lobes=0):
         from gaussian_renderer import shading
         from gaussian_renderer.svgss_rasterization import GaussianRasterizer
         from . import losses, optim, render_view
         self.shading, self.render_view, self.losses, self.optim = shading, render_view, losses, optim
         self.GaussianRasterizer = GaussianRasterizer
-        self.dev, self.name, self.Ns, self.fused = dev, name, Ns, fused
+        # sg_lobes > 0: the direct light is the reference's DirectLightSG with that many lobes (train.py:65-66) instead of the texture --
+        # the parameter of optimizer group 'env' is lgtSGs [sg_lobes, 7], and the step takes the unfused path (svgir_fused_shade has no SG light)
+        self.sg_lobes = int(sg_lobes)
+        self.dev, self.name, self.Ns, self.fused = dev, name, Ns, bool(fused) and not self.sg_lobes
         # The reference shades with pc.get_radiances = nan_to_num(_radiances.detach() * _radiance_ratio, nan=0) (gaussian_model.py:323-324):
         # the cache sits in the optimizer (group 'radiances', :527) but never receives a gradient; what learns is the scalar ratio
         # (lr 0.01, :526-528).  radiance_grad=True is the earlier rounds' form (the [P, Ns, 3] cache itself is a differentiated leaf).
@@ -82,6 +85,8 @@ class TrainStep:
         par = {"xyz": sct["means3D"], "scaling": sct["scales"], "rotation": sct["rotations"], "opacity": sct["opacities"],
                "shs": sct["shs"], "base_color": sd["base_color"], "roughness": sd["roughness"], "normal": sd["normals"],
                "radiance": sd["radiance"], "env": sd["env"]}
+        if self.sg_lobes:
+            par["env"] = shade_inputs.sg_lobes(self.sg_lobes, seed=seed + 2, device=dev)
         if raw_params:   # the inverse activations of the scene's values (scene/gaussian_model.py:113, 118, 125); zero normal offsets
             logit = lambda y: torch.log(y / (1 - y))  # noqa: E731
             par.update(scaling=torch.log(par["scaling"]), opacity=logit(par["opacity"]), base_color=logit((par["base_color"] - 0.03) / 0.77),
@@ -100,7 +105,7 @@ class TrainStep:
         self.weights_accum = torch.zeros(P, 1, device=dev)
         self.denom = torch.zeros(P, 1, device=dev)
         self.gt = torch.rand(3, self.H, self.W, generator=torch.Generator().manual_seed(seed + 1)).to(dev)
-        self.light = shade_inputs.Light(self.params["env"])
+        self.light = shade_inputs.SGLight(self.params["env"]) if self.sg_lobes else shade_inputs.Light(self.params["env"])
         self.marks = None   # optional: list of (name, torch.cuda.Event) filled by step() when set to []
 
     def _mark(self, name):
