@@ -127,7 +127,7 @@ __device__ __forceinline__ void pack12(float4* __restrict__ p, size_t row, const
 
 __global__ void __launch_bounds__(AT) activate_fwd_kernel(const ActArgs A) {
     __shared__ float sXyz[AT3], sScl[AT3], sOut[3][AT3];   // in: xyz, scaling; out: scales, geo_normal, viewdirs
-    __shared__ double sRed[AT / 64];
+    __shared__ double sRed[1][AT / 64];
     const svgir_activation& a = A.a;
     const int t = threadIdx.x;
     const size_t p0 = (size_t)blockIdx.x * AT, p = p0 + t, base3 = 3 * p0;
@@ -215,26 +215,21 @@ __global__ void __launch_bounds__(AT) activate_fwd_kernel(const ActArgs A) {
     tile_store3(a.geo_normal, base3, n3, sOut[1]);
     tile_store3(a.viewdirs, base3, n3, sOut[2]);
     if (a.normal_reg) {   // (workgroup-uniform)
-        const double s = wave_reduce_add(reg);
-        if ((t & 63) == 0) sRed[t >> 6] = s;
-        __syncthreads();
-        if (t == 0) a.partial[blockIdx.x] = (sRed[0] + sRed[1]) + (sRed[2] + sRed[3]);
+        double s[1] = {wave_reduce_add(reg)};
+        block_sum_ordered(s, sRed);
+        if (t == 0) a.partial[blockIdx.x] = s[0];
     }
 }
 
 // the workgroups' partial sums -> the double sum and the fp32 mean: one workgroup, fixed order
 __global__ void __launch_bounds__(256) activate_reduce_kernel(const double* __restrict__ partial, int nblk, double count,
                                                               double* __restrict__ sum, float* __restrict__ mean) {
-    __shared__ double red[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
-    s = wave_reduce_add(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    __shared__ double red[1][4];
+    double tot[1];
+    block_reduce_records(partial, nblk, 1, tot, red);
     if (threadIdx.x == 0) {
-        const double tot = (red[0] + red[1]) + (red[2] + red[3]);
-        *sum = tot;
-        *mean = (float)(tot / count);
+        *sum = tot[0];
+        *mean = (float)(tot[0] / count);
     }
 }
 

@@ -165,22 +165,18 @@ __global__ void __launch_bounds__(GT_THREADS) geom_loss_fwd_kernel(const GeomLos
         __syncthreads();
         if (valid) v[4] = (double)(a.opacity[i] * (1.f - pool_cols(sPool, ty, tx)));
     }
-    // workgroup sums in a fixed order: xor butterflies inside the waves, then the four waves in order (wave-uniform branches)
+    // workgroup sums in a fixed order: xor butterflies (wave-uniform branches: a term that is off is 0.0 in every lane), then the four waves in order
 #pragma unroll
     for (int q = 0; q < 6; q++) {
         const bool on = q < 2 ? surface : (q < 4 ? target : (q == 4 ? maskt : entropy));
-        if (!on) continue;
-        const double s = wave_reduce_add(v[q]);
-        if ((t & 63) == 0) sRed[q][t >> 6] = s;
+        if (on) v[q] = wave_reduce_add(v[q]);
     }
-    __syncthreads();
-    if (t < 6) {
-        const bool on = t < 2 ? surface : (t < 4 ? target : (t == 4 ? maskt : entropy));
-        const double s = on ? (sRed[t][0] + sRed[t][1]) + (sRed[t][2] + sRed[t][3]) : 0.0;
-        const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        const int slot = t < 5 ? t : 6;
-        a.partial[8 * blk + slot] = s;
-        if (t >= 4) a.partial[8 * blk + slot + 1] = 0.0;
+    block_sum_ordered(v, sRed);
+    if (t == 0) {
+        double* rec = a.partial + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+#pragma unroll
+        for (int q = 0; q < 5; q++) rec[q] = v[q];
+        rec[5] = 0.0; rec[6] = v[5]; rec[7] = 0.0;
     }
 }
 
@@ -188,22 +184,14 @@ __global__ void __launch_bounds__(GT_THREADS) geom_loss_fwd_kernel(const GeomLos
 __global__ void __launch_bounds__(256) geom_loss_reduce_kernel(const double* __restrict__ partial, int nblk, int terms, double npix,
                                                                double* __restrict__ stats, float* __restrict__ losses) {
     __shared__ double red[8][4];
-    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nblk; i += 256) {
+    double s[8];
+    block_reduce_records(partial, nblk, 8, s, red);
 #pragma unroll
-        for (int q = 0; q < 8; q++) s[q] += partial[8 * (size_t)i + q];
-    }
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        s[q] = wave_reduce_add(s[q]);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int k = threadIdx.x;
+    for (int k = 0; k < 4; k++) {   // thread k writes term k (k is a constant per copy of the body: s[] stays in registers)
+        if ((int)threadIdx.x != k) continue;
         const bool on = (terms >> k) & 1;
-        const double sum = (red[2 * k][0] + red[2 * k][1]) + (red[2 * k][2] + red[2 * k][3]);
-        const double cnt = k < 2 ? (red[2 * k + 1][0] + red[2 * k + 1][1]) + (red[2 * k + 1][2] + red[2 * k + 1][3]) : npix;
+        const double sum = s[2 * k];
+        const double cnt = k < 2 ? s[2 * k + 1] : npix;
         stats[2 * k] = on ? sum : 0.0;
         stats[2 * k + 1] = on ? cnt : 0.0;
         losses[k] = on ? (float)(sum / cnt) : 0.f;   // (an empty selection: 0 / 0 = NaN, torch's mean of nothing)

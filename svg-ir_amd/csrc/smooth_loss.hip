@@ -139,12 +139,12 @@ __global__ void __launch_bounds__(ST_THREADS) smooth_loss_fwd_kernel(const Smoot
             va = tm.kind == KIND_FIRST ? edge_value<1>(tm, sD, sI, ty + SF_H, tx + SF_H, 1.0) : edge_value<2>(tm, sD, sI, ty + SF_H, tx + SF_H, 10.0);
     }
     // workgroup sums in a fixed order: xor butterflies inside the waves, then the four waves in order
-    va = wave_reduce_add(va); vb = wave_reduce_add(vb);
-    if ((t & 63) == 0) { sRed[0][t >> 6] = va; sRed[1][t >> 6] = vb; }
-    __syncthreads();
-    if (t < 2) {
+    double s[2] = {wave_reduce_add(va), wave_reduce_add(vb)};
+    block_sum_ordered(s, sRed);
+    if (t == 0) {
         const size_t nblk = (size_t)gridDim.x * gridDim.y, blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        a.partial[2 * (blockIdx.z * nblk + blk) + t] = (sRed[t][0] + sRed[t][1]) + (sRed[t][2] + sRed[t][3]);
+        a.partial[2 * (blockIdx.z * nblk + blk)] = s[0];
+        a.partial[2 * (blockIdx.z * nblk + blk) + 1] = s[1];
     }
 }
 
@@ -153,17 +153,10 @@ __global__ void __launch_bounds__(256) smooth_loss_reduce_kernel(const SmoothArg
     __shared__ double red[2][4];
     const int k = blockIdx.x;
     const svgir_smooth_term& tm = a.t[k];
-    const double* rec = a.partial + 2 * (size_t)k * nblk;
-    double s[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < nblk; i += 256) { s[0] += rec[2 * (size_t)i]; s[1] += rec[2 * (size_t)i + 1]; }
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        s[q] = wave_reduce_add(s[q]);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s[q];
-    }
-    __syncthreads();
+    double s[2];
+    block_reduce_records(a.partial + 2 * (size_t)k * nblk, nblk, 2, s, red);
     if (threadIdx.x == 0) {
-        const double sa = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), sb = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        const double sa = s[0], sb = s[1];
         const double W = a.W, H = a.H, C = tm.C, Cb = tm.C > tm.Ci ? tm.C : tm.Ci;
         const bool tv = tm.kind == KIND_TV;
         const double ca = tv ? C * (H - 1.0) * W : Cb * H * W, cb = tv ? C * H * (W - 1.0) : 0.0;

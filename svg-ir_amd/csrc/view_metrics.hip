@@ -9,9 +9,9 @@
 //   svgir_view_metrics : up to 4 operand pairs of one image size per call.  The operands are PLANE OPERANDS (include/svgir_raster.h):
 //                        src, optional affine, optional mask composite over a constant or a fill plane, optional sRGB, composed ON LOAD in
 //                        fp32 without contraction, so no composed plane ever exists in HBM and the value has the bits torch would hold.
-//                        Terms with SSIM use the tiling and the SSIM arithmetic of csrc/loss.hip's ssim_fwd_kernel (16 x 16 tile, 26 x 26
-//                        halo tile that is zero padding applied after composition); terms without are another instantiation that loads no
-//                        halo and runs no LDS passes.  d = a - b in fp32; d^2 (exact in double) and |d| are summed in double per
+//                        Terms with SSIM share the tiling and the SSIM arithmetic of csrc/loss.hip's ssim_fwd_kernel (csrc/ssim_tile.hpp:
+//                        16 x 16 tile, 26 x 26 halo tile that is zero padding applied after composition); terms without are another
+//                        instantiation that loads no halo and runs no LDS passes.  d = a - b in fp32; d^2 (exact in double) and |d| are summed in double per
 //                        workgroup (wave reduction, then the four waves in order); one workgroup per term adds the records in a fixed order
 //                        and writes the row of 10 doubles.
 //   svgir_capture_u8   : up to 16 operands -> [n,H,W,3] bytes, (uint8) clamp((x * 255) + 0.5, 0, 255).  A thread owns 12 consecutive bytes
@@ -22,6 +22,7 @@
 // No atomics, no host wait.
 #include "common.hpp"
 #include "srgb.hpp"
+#include "ssim_tile.hpp"
 
 namespace svgir {
 
@@ -29,18 +30,7 @@ int report_error(int code, const char* fmt, ...);   // api.hip
 
 namespace {
 
-constexpr int LT = 16, LR = 5, LW = LT + 2 * LR;   // output tile, window radius, input tile with halo (as csrc/loss.hip)
 constexpr int VM_REC = 3;                             // doubles per workgroup record: sum d^2, sum |d|, sum of the SSIM map
-
-struct SsimWindow { float g[11]; };
-inline SsimWindow ssim_window() {
-    // utils/loss_utils.py:21-23: fp32 tensor of exp(-(x - 5)^2 / (2 * 1.5^2)), divided by its fp32 sum (the lines of csrc/loss.hip)
-    SsimWindow w;
-    float s = 0.f;
-    for (int i = 0; i < 11; i++) { w.g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += w.g[i]; }
-    for (int i = 0; i < 11; i++) w.g[i] /= s;
-    return w;
-}
 
 // element i of channel c of a plane operand; N = H W.  No contraction: plain operators under the pragma (__fmul_rn / __fadd_rn are
 // operators in a header to the compiler and are fused like any other, csrc/knn.hip); srgb() keeps the arithmetic it has everywhere else.  SRGB = false: for callers
@@ -68,10 +58,10 @@ struct MetricArgs {
 
 template <bool SSIM>
 __global__ void __launch_bounds__(LT * LT) view_metrics_kernel(const MetricArgs a, const SsimWindow win) {
-    __shared__ float sA[SSIM ? LW : 1][LW + 1], sB[SSIM ? LW : 1][LW + 1];
+    __shared__ float sT[2][SSIM ? LW : 1][LW + 1];   // a, b
     __shared__ float sH[SSIM ? 5 : 1][SSIM ? LW : 1][LT + 1];
     __shared__ double sRed[2][4];
-    __shared__ float sRedS[4];
+    __shared__ float sRedS[1][4];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, t = threadIdx.x;
     const int slot = blockIdx.z / 3, ch = blockIdx.z - 3 * slot;
     const int k = a.term[slot];
@@ -82,81 +72,42 @@ __global__ void __launch_bounds__(LT * LT) view_metrics_kernel(const MetricArgs 
     const bool valid = x < W && y < H;
     float u = 0.f, v = 0.f, ssim = 0.f;
     if constexpr (SSIM) {
-        const int x0 = blockIdx.x * LT - LR, y0 = blockIdx.y * LT - LR;
-        for (int i = t; i < LW * LW; i += LT * LT) {
-            const int r = i / LW, c = i - r * LW;
-            const int yy = y0 + r, xx = x0 + c;
-            const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;   // zero padding of the COMPOSED operand (loss_utils.py:45)
-            sA[r][c] = in ? compose(T.a, ch, N, (size_t)yy * W + xx) : 0.f;
-            sB[r][c] = in ? compose(T.b, ch, N, (size_t)yy * W + xx) : 0.f;
-        }
+        // (the zero padding is that of the COMPOSED operand)
+        ssim_load_halo<2>(sT, H, W, [&](int q, size_t i) { return compose(q ? T.b : T.a, ch, N, i); });
         __syncthreads();
-        for (int i = t; i < LW * LT; i += LT * LT) {   // horizontal pass: rows of the halo tile, 16 output columns
-            const int r = i / LT, c = i - r * LT;
-            float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-            for (int q = 0; q < 11; q++) {
-                const float p = sA[r][c + q], w = sB[r][c + q], g = win.g[q];
-                m1 += g * p; m2 += g * w; e11 += g * (p * p); e22 += g * (w * w); e12 += g * (p * w);
-            }
-            sH[0][r][c] = m1; sH[1][r][c] = m2; sH[2][r][c] = e11; sH[3][r][c] = e22; sH[4][r][c] = e12;
-        }
-        __syncthreads();
-        float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-        for (int q = 0; q < 11; q++) {
-            const float g = win.g[q];
-            mu1 += g * sH[0][ty + q][tx]; mu2 += g * sH[1][ty + q][tx];
-            e11 += g * sH[2][ty + q][tx]; e22 += g * sH[3][ty + q][tx]; e12 += g * sH[4][ty + q][tx];
-        }
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const float s1 = e11 - mu1 * mu1, s2 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
-        const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2, B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
-        const float iB1 = 1.f / B1, iB2 = 1.f / B2;
-        ssim = valid ? (A1 * A2) * (iB1 * iB2) : 0.f;
-        u = sA[ty + LR][tx + LR]; v = sB[ty + LR][tx + LR];
+        float m[5];
+        ssim_moments(win, sT, sH, m);
+        ssim = valid ? ssim_pixel(m).S : 0.f;
+        u = sT[0][ty + LR][tx + LR]; v = sT[1][ty + LR][tx + LR];
     } else if (valid) {
         u = compose(T.a, ch, N, (size_t)y * W + x);
         v = compose(T.b, ch, N, (size_t)y * W + x);
     }
     const float d = valid ? u - v : 0.f;
-    double sq = (double)d * (double)d, ab = (double)fabsf(d);
-    // workgroup sums in a fixed order: the wave butterfly, then the four waves in order
-    sq = wave_reduce_add(sq); ab = wave_reduce_add(ab);
-    if constexpr (SSIM) ssim = wave_sum(ssim);
-    if ((t & 63) == 0) { sRed[0][t >> 6] = sq; sRed[1][t >> 6] = ab; sRedS[t >> 6] = ssim; }
-    __syncthreads();
+    // workgroup sums in a fixed order: the wave butterfly (the SSIM float: the DPP sum, as ssim_fwd_kernel), then the four waves in order
+    double s[2] = {wave_reduce_add((double)d * (double)d), wave_reduce_add((double)fabsf(d))};
+    float ss[1] = {ssim};
+    if constexpr (SSIM) ss[0] = wave_sum(ssim);
+    block_sum_ordered(s, sRed, ss, sRedS);
     if (t == 0) {
         const size_t tiles = (size_t)gridDim.x * gridDim.y;
         double* rec = a.partial + (((size_t)k * 3 + ch) * tiles + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * VM_REC;
-        rec[0] = (sRed[0][0] + sRed[0][1]) + (sRed[0][2] + sRed[0][3]);
-        rec[1] = (sRed[1][0] + sRed[1][1]) + (sRed[1][2] + sRed[1][3]);
-        rec[2] = SSIM ? (double)((sRedS[0] + sRedS[1]) + (sRedS[2] + sRedS[3])) : 0.0;
+        rec[0] = s[0]; rec[1] = s[1];
+        rec[2] = SSIM ? (double)ss[0] : 0.0;
     }
-}
-
-// sum of v over the 256 threads, in thread 0 (wave butterfly, then the four waves in order).  red[4]: one barrier in front of the reads,
-// one behind them, so the next call may write it again
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-    v = wave_reduce_add(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return s;
 }
 
 // one workgroup per term: the records of its three channels in a fixed order, then the row
 __global__ void __launch_bounds__(256) view_metrics_reduce_kernel(const double* __restrict__ partial, int tiles, double HW, int ssim_bits,
                                                                   double* __restrict__ rows) {
-    __shared__ double red[4];
+    __shared__ double red[VM_REC][4];
     const int k = blockIdx.x;
     double sq[3], ab[3], ss[3];
     for (int c = 0; c < 3; c++) {
-        const double* rec = partial + ((size_t)k * 3 + c) * (size_t)tiles * VM_REC;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        for (int i = threadIdx.x; i < tiles; i += 256) { s0 += rec[(size_t)i * VM_REC]; s1 += rec[(size_t)i * VM_REC + 1]; s2 += rec[(size_t)i * VM_REC + 2]; }
-        sq[c] = block_sum_f64(s0, red); ab[c] = block_sum_f64(s1, red); ss[c] = block_sum_f64(s2, red);
+        double s[VM_REC];
+        if (c) __syncthreads();   // (red is written again)
+        block_reduce_records(partial + ((size_t)k * 3 + c) * (size_t)tiles * VM_REC, tiles, VM_REC, s, red);
+        sq[c] = s[0]; ab[c] = s[1]; ss[c] = s[2];
     }
     if (threadIdx.x == 0) {
         double* row = rows + (size_t)k * SVGIR_METRIC_COLS;
@@ -226,7 +177,7 @@ constexpr int AS_REC = 4;                                           // doubles p
 
 __global__ void __launch_bounds__(BLOCK) albedo_scale_kernel(const float* __restrict__ render, const float* __restrict__ gt, size_t N, int gt_srgb,
                                                              double* __restrict__ partial) {
-    __shared__ double red[4];
+    __shared__ double red[AS_REC][4];
     double s[3] = {0.0, 0.0, 0.0}, n = 0.0;
     for (int q = 0; q < AS_PER_THREAD; q++) {
         const size_t i = (size_t)blockIdx.x * AS_TILE + (size_t)q * BLOCK + threadIdx.x;
@@ -242,19 +193,17 @@ __global__ void __launch_bounds__(BLOCK) albedo_scale_kernel(const float* __rest
             s[c] += (double)(ratio < 1e-6f ? 1e-6f : (ratio > 1.f ? 1.f : ratio));   // clamp(1e-6, 1), NaN passes
         }
     }
-    double v[AS_REC] = {s[0], s[1], s[2], n};
-    for (int c = 0; c < AS_REC; c++) v[c] = block_sum_f64(v[c], red);
+    double v[AS_REC] = {wave_reduce_add(s[0]), wave_reduce_add(s[1]), wave_reduce_add(s[2]), wave_reduce_add(n)};
+    block_sum_ordered(v, red);
     if (threadIdx.x == 0)
         for (int c = 0; c < AS_REC; c++) partial[(size_t)blockIdx.x * AS_REC + c] = v[c];
 }
 
 __global__ void __launch_bounds__(256) albedo_scale_reduce_kernel(const double* __restrict__ partial, int nblk, float* __restrict__ scale3,
                                                                   int32_t* __restrict__ count) {
-    __shared__ double red[4];
-    double v[AS_REC] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nblk; i += 256)
-        for (int c = 0; c < AS_REC; c++) v[c] += partial[(size_t)i * AS_REC + c];
-    for (int c = 0; c < AS_REC; c++) v[c] = block_sum_f64(v[c], red);
+    __shared__ double red[AS_REC][4];
+    double v[AS_REC];
+    block_reduce_records(partial, nblk, AS_REC, v, red);
     if (threadIdx.x == 0) {
         for (int c = 0; c < 3; c++) scale3[c] = (float)(v[c] / v[3]);   // empty selection: 0 / 0 = NaN, torch's mean of nothing
         count[0] = (int32_t)v[3];

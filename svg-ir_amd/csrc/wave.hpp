@@ -93,6 +93,49 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {
     for (int w = 0; w < WAVES; w++) s += lds[w];
     return s;
 }
+// THE fixed-order floating-point sum over the four waves of a 256-thread workgroup, N quantities at once, in every thread: w[q] comes in as
+// the caller's own per-wave total (wave_sum or wave_reduce_add: the two give different float bits, so the wave step stays the caller's) and
+// goes out as (wave 0 + wave 1) + (wave 2 + wave 3).  lds[N][4]: see BARRIERS.  The losses' bit-reproducibility rests on this one tree.
+// (csrc/irradiance.hip's radiance loss keeps its own orders -- a 1024-thread halving tree and a serial wave loop: moving it here changes its bits.)
+template <int N, class T>
+__device__ __forceinline__ void block_sum_put(const T (&w)[N], T (*lds)[4]) {
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < N; q++) lds[q][threadIdx.x >> 6] = w[q];
+    }
+}
+template <int N, class T>
+__device__ __forceinline__ void block_sum_get(T (&w)[N], const T (*lds)[4]) {
+#pragma unroll
+    for (int q = 0; q < N; q++) w[q] = (lds[q][0] + lds[q][1]) + (lds[q][2] + lds[q][3]);
+}
+template <int N, class T>
+__device__ __forceinline__ void block_sum_ordered(T (&w)[N], T (*lds)[4]) {
+    block_sum_put(w, lds);
+    __syncthreads();
+    block_sum_get(w, lds);
+}
+// (quantities of two types behind the same single barrier)
+template <int N, class T, int M, class U>
+__device__ __forceinline__ void block_sum_ordered(T (&w)[N], T (*lds)[4], U (&u)[M], U (*ldu)[4]) {
+    block_sum_put(w, lds); block_sum_put(u, ldu);
+    __syncthreads();
+    block_sum_get(w, lds); block_sum_get(u, ldu);
+}
+// The record reduction of ONE 256-thread workgroup: s[q] = the sum of column q of the n records rec[i * stride + q] (float or double), in
+// every thread.  Thread t adds records t, t + 256, ... in double, then the xor butterfly, then the tree above.  lds[N][4]: see BARRIERS.
+template <int N, class T>
+__device__ __forceinline__ void block_reduce_records(const T* __restrict__ rec, int n, size_t stride, double (&s)[N], double (*lds)[4]) {
+#pragma unroll
+    for (int q = 0; q < N; q++) s[q] = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+#pragma unroll
+        for (int q = 0; q < N; q++) s[q] += (double)rec[(size_t)i * stride + q];
+    }
+#pragma unroll
+    for (int q = 0; q < N; q++) s[q] = wave_reduce_add(s[q]);
+    block_sum_ordered(s, lds);
+}
 // sum of block_sums[0 .. nbefore) -- the totals of the workgroups in front of this one -- in every thread
 template <int WAVES>
 __device__ __forceinline__ uint32_t blocks_before(const uint32_t* __restrict__ block_sums, int nbefore, uint32_t* lds) {
