@@ -390,9 +390,10 @@ int svgir_shade_backward_view(const svgir_shade_params* p, const float* dL_dredu
  * {a.xyz, |lambda|} and {|mu|.rgb, 1 / |xi|} (the role env_work plays for the texture).
  * Invalid input is rejected with SVGIR_ERR_INVALID and a message before any launch: count outside 1 ... SVGIR_SG_MAX_LOBES, NULL lobes /
  * work, a misaligned work, a non-NULL subset / subset_count (subset shading belongs to the rasterizer-fused path).
- * NOT provided (each would be new work, not a switch): the shading fused into svgir_forward / svgir_backward (svgir_fused_shade carries no
- * light pointer: a struct change and an ABI bump), the eval backdrop and the fused radiance-consistency loss for an SG light, and a
- * differentiable svgir_sg_eval. */
+ * The bare light's gradient (svgir_sg_eval_backward), the eval backdrop (svgir_env_backdrop_sg) and the fused radiance-consistency loss
+ * (svgir_radiance_loss_forward_sg / _backward_sg) follow below and next to their texture counterparts.
+ * NOT provided (new work, not a switch): the shading fused into svgir_forward / svgir_backward (svgir_fused_shade carries no light
+ * pointer: a struct change and an ABI bump). */
 #define SVGIR_SG_MAX_LOBES 128
 typedef struct svgir_sg_light {
     int32_t count;        /* M */
@@ -400,8 +401,24 @@ typedef struct svgir_sg_light {
     float* work;          /* [8 M] scratch, 16-byte aligned */
 } svgir_sg_light;
 
-/* out [n,3] = the UNCLAMPED L of dirs [n,3]: DirectLightSG.direct_light / render_envmap_sg.  Forward only. */
+/* out [n,3] = the UNCLAMPED L of dirs [n,3]: DirectLightSG.direct_light / render_envmap_sg. */
 int svgir_sg_eval(const svgir_sg_light* light, int64_t n, const float* dirs, float* out, void* stream);
+
+/* The gradient of svgir_sg_eval (added within ABI 14).  With a, e, |mu|, |lambda| as above, g = dL_dout [n,3] of one direction (no clamp:
+ * the light is the unclamped L) and s_m = e_m sum_c |mu_mc| g_c:
+ *     dmu_mc = sign(mu_mc) sum_n e_m g_c,   dlambda_m = sign(lambda_m) sum_n (d.a_m - 1) s_m,
+ *     dxi_m = |lambda_m| (G_m - a_m (a_m.G_m)) / |xi_m|  with  G_m = sum_n s_m d,   sign(0) = 0
+ *     dL_ddirs[n] = sum_m |lambda_m| s_m a_m      (fp32, m ascending; no atomics: the same bits on every run)
+ * dL_dlobes [M,7] and dL_ddirs [n,3] are each optional (NULL), not both; every element of a requested output is written.  The 7 M sums
+ * are accumulated per workgroup in LDS in fp64, flushed once per workgroup with float atomics into `grad_work`
+ * (svgir_sg_grad_work_bytes(count) bytes, cleared by the call; the layout svgir_shade_backward_sg uses) and pulled back by a one-block
+ * kernel: dL_dlobes is repeatable only up to the order of those adds.  light->work is built by the call.  n = 0 writes zeros to
+ * dL_dlobes and launches nothing else.
+ * Rejected with SVGIR_ERR_INVALID and a message before any HIP call: count outside 1 ... SVGIR_SG_MAX_LOBES, NULL lobes / work /
+ * grad_work, a misaligned work, n < 0, both outputs NULL, NULL dirs or dL_dout with n > 0.  Non-finite lobes: outputs are unspecified;
+ * nothing faults or hangs. */
+int svgir_sg_eval_backward(const svgir_sg_light* light, int64_t n, const float* dirs, const float* dL_dout, float* dL_dlobes,
+                           float* dL_ddirs, float* grad_work, void* stream);
 
 /* svgir_shade_forward with the SG light.  The env* fields of `p` (env, env_h, env_w, env_softplus, env_scale, env_work, env_transform) are
  * ignored and may be NULL / 0; p->subset must be NULL. */
@@ -512,6 +529,15 @@ int svgir_depth2normal_backward(int32_t W, int32_t H, const float* depth, const 
 int svgir_env_backdrop(int32_t W, int32_t H, const float* intr, const float* c2w_rot, const float* env_transform, const float* env,
                        int32_t env_h, int32_t env_w, int32_t env_softplus, float env_scale, float* env_work, const float* image,
                        const float* opacity, const float* vfeature, float* out, void* stream);
+
+/* svgir_env_backdrop under a spherical-Gaussian light (added within ABI 14).  The pixel directions are exactly those above -- the camera
+ * direction, normalised, rotated by c2w[:3,:3] -- and are used as they are: DirectLightSG.direct_light ignores a lookup transform, and
+ * there is no latitude to clamp.  env = L(d), the UNCLAMPED fp32 light of svgir_sg_eval (m ascending), and the three images are composed
+ * from it exactly as above (the same sRGB, the same max(o, 1e-5)); every element of out [9,H,W] is written.  light->work (8 * count
+ * floats, 16-byte aligned) is built by this call.  Invalid arguments -- those of svgir_env_backdrop and those of a svgir_sg_light -- are
+ * rejected with SVGIR_ERR_INVALID and a message before any HIP call. */
+int svgir_env_backdrop_sg(int32_t W, int32_t H, const float* intr, const float* c2w_rot, const svgir_sg_light* light,
+                          const float* image, const float* opacity, const float* vfeature, float* out, void* stream);
 
 /* Image losses behind render_view: L1 and SSIM with the reference's 11 x 11 Gaussian window
  * (`F.l1_loss(image, gt)` and `ssim(image, gt)`, gaussian_renderer/svgss.py:281-289, render.py:150-151;
@@ -923,6 +949,24 @@ int svgir_radiance_loss_forward(const svgir_radiance_loss_params* p, int32_t* sa
 int svgir_radiance_loss_backward(const svgir_radiance_loss_params* p, const int32_t* sample_indices, const float* radiance,
                                  const float* d_loss, float* d_env, float* d_albedos, float* d_roughnesses, float* d_radiance_ratio,
                                  void* stream);
+
+/* The fused radiance-consistency loss under a spherical-Gaussian light (added within ABI 14; GaussianModel.get_radiance_loss with
+ * train.py:65-66's DirectLightSG).  The env* fields of `p` are ignored; p->work has svgir_radiance_loss_sg_work_bytes(N, count) bytes,
+ * 16-byte aligned (the lobes' table-space sums and the partial sums; 0 for N < 0 or a count outside 1 ... SVGIR_SG_MAX_LOBES);
+ * light->work is built by each call.  Everything above holds word for word -- the selection (it does not see the light), the hit rules,
+ * the four irradiance decisions, the target, the loss sum's order, the per-element non-finite rule, complete writes, N = 0 -- except
+ *     envmap[h,s,c] = L_c(ray_d[h,s]) * areas[h,s],   L the unclamped fp32 light of svgir_sg_eval on the raw direction (m ascending).
+ * Backward: the adjoint of L_c at (h,s) is g_c = d_R[i,c] irr_c / S * areas[h,s] (a channel without upstream is skipped, not multiplied
+ * by 0); it feeds the seven sums per lobe of svgir_sg_eval_backward -- fp64 in LDS per workgroup, one float-atomic flush, the pull-back
+ * -- and d_lobes [M,7] (may be null: not wanted) is written completely.  d_lobes, like d_env, is repeatable only up to the order of
+ * those adds; d_albedos / d_roughnesses / d_radiance_ratio are as above.  An invalid light or parameter block is rejected with
+ * SVGIR_ERR_INVALID and a message before any HIP call. */
+size_t svgir_radiance_loss_sg_work_bytes(int32_t N, int32_t count);
+int svgir_radiance_loss_forward_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* light, int32_t* sample_indices,
+                                   float* radiance, double* loss_sum, float* loss, void* stream);
+int svgir_radiance_loss_backward_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* light, const int32_t* sample_indices,
+                                    const float* radiance, const float* d_loss, float* d_lobes, float* d_albedos, float* d_roughnesses,
+                                    float* d_radiance_ratio, void* stream);
 
 /* Exact k-nearest-neighbour search over a point cloud: simple_knn's `distCUDA2` (submodules/simple-knn/simple_knn.cu:147-221; the initial
  * scales of GaussianModel.create_from_pcd) and custom_knn's `topKdistCUDA2` (no source upstream; get_knn_loss,

@@ -16,6 +16,10 @@
 // grid_sample's two corner rules spelled out: a tap outside the map contributes exactly 0 whatever the map holds, a tap inside it is
 // multiplied even when its weight is 0 (inf * 0 = NaN, as in grid_sample).
 //
+// A spherical-Gaussian light (DirectLightSG; svgir_env_backdrop_sg, backdrop_kernel<LIGHT_SG>) has no texture: its M lobes are evaluated
+// along the same pixel direction (sg_light.hpp: sg_eval, the prepared table in LDS), without a lookup transform, and the three images are
+// composed by the same function.
+//
 // ONE DELIBERATE DEPARTURE from the reference: d.z is clamped to [-1, 1] before the acos.  The rotation of a unit vector can round to
 // |z| = 1 + ulp, where the reference's arccos returns NaN and the pixel turns NaN; that NaN is not reproduced, the pixel looks up the
 // pole.  (A NaN direction -- from a NaN camera -- stays NaN.)
@@ -23,6 +27,7 @@
 
 #include "common.hpp"
 #include "env_lookup.hpp"
+#include "sg_light.hpp"
 #include "srgb.hpp"
 
 namespace svgir {
@@ -44,13 +49,50 @@ struct BackdropArgs {
     float* out;
 };
 
+// the three images of pixel i from its light E (x scale): svgss.py:188-189, 258-260
+__device__ __forceinline__ void backdrop_compose(const BackdropArgs& a, size_t N, size_t i, const float* E, float scale) {
+    const float o = a.opacity[i];
+    const float om = 1.f - o;
+    const float oc = clamp_min_nan(o, 1e-5f);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const float env = E[ch] * scale;
+        const float s = srgb(env);
+        const float pbr = a.pbr[(size_t)ch * N + i] / oc;
+        a.out[(size_t)ch * N + i] = s;
+        a.out[(size_t)(3 + ch) * N + i] = a.image[(size_t)ch * N + i] + om * s;
+        a.out[(size_t)(6 + ch) * N + i] = srgb(pbr * o + om * env);
+    }
+}
+
 __global__ void __launch_bounds__(BLOCK) backdrop_table_kernel(const ShadeTables t) {
     shade_table_entry(t, blockIdx.x * BLOCK + threadIdx.x);
 }
 
+// LIGHT (LIGHT_SG: svgir_env_backdrop_sg): the light kind, a template parameter so that the texture kernel is exactly the code it was.
+// The SG light travels in the otherwise unread env fields: env_tab = the prepared lobe table (copied to LDS: every lane reads the same
+// entry, a broadcast), env_w = the lobe count.  It has no lookup transform and no latitude, so neither the transform nor the clamp of
+// d.z applies: env = the unclamped L(d) (sg_eval, m ascending); the composition below is shared.
+template <int LIGHT>
 __global__ void __launch_bounds__(BLOCK) backdrop_kernel(const BackdropArgs a) {
     const size_t N = (size_t)a.W * a.H;
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if constexpr (LIGHT == LIGHT_SG) {
+        __shared__ float4 st[2 * SVGIR_SG_MAX_LOBES];
+        for (int k = threadIdx.x; k < 2 * a.env_w; k += BLOCK) st[k] = a.env_tab[k];
+        __syncthreads();
+        if (i >= N) return;
+        const int u = (int)(i % (size_t)a.W), v = (int)(i / (size_t)a.W);
+        const float x = ((float)u - a.cx) / a.fx, y = ((float)v - a.cy) / a.fy;
+        const float nrm = fmaxf(sqrtf(x * x + y * y + 1.f), 1e-12f);
+        const float c[3] = {x / nrm, y / nrm, 1.f / nrm};
+        float d[3], E[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) d[j] = a.R[3 * j] * c[0] + a.R[3 * j + 1] * c[1] + a.R[3 * j + 2] * c[2];
+        sg_eval(st, a.env_w, d, E);
+        backdrop_compose(a, N, i, E, 1.f);
+        return;
+    }
     if (i >= N) return;
     const int u = (int)(i % (size_t)a.W), v = (int)(i / (size_t)a.W);
     // scene/cameras.py:102-106
@@ -81,18 +123,11 @@ __global__ void __launch_bounds__(BLOCK) backdrop_kernel(const BackdropArgs a) {
             E[2] += ok ? t.w[j] * tex[j].z : 0.f;
         }
     }
-    const float o = a.opacity[i];
-    const float om = 1.f - o;
-    const float oc = clamp_min_nan(o, 1e-5f);
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const float env = E[ch] * a.env_scale;
-        const float s = srgb(env);
-        const float pbr = a.pbr[(size_t)ch * N + i] / oc;
-        a.out[(size_t)ch * N + i] = s;
-        a.out[(size_t)(3 + ch) * N + i] = a.image[(size_t)ch * N + i] + om * s;
-        a.out[(size_t)(6 + ch) * N + i] = srgb(pbr * o + om * env);
-    }
+    backdrop_compose(a, N, i, E, a.env_scale);
+}
+
+__global__ void __launch_bounds__(BLOCK) backdrop_sg_table_kernel(const float* __restrict__ lobes, int M, float4* __restrict__ tab) {
+    sg_table_build(lobes, M, tab, nullptr, 0);
 }
 
 }  // namespace
@@ -130,8 +165,35 @@ extern "C" int svgir_env_backdrop(int32_t W, int32_t H, const float* intr, const
     StageMarks tm = stage_begin(s);
     hipLaunchKernelGGL(backdrop_table_kernel, dim3((t.ntexel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, t);
     stage_mark(tm, "backdrop_env_table");
-    hipLaunchKernelGGL(backdrop_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(backdrop_kernel<LIGHT_TEX>, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
     stage_mark(tm, "backdrop");
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SVGIR_OK : report_error(SVGIR_ERR_HIP, "env_backdrop launch failed: %s", hipGetErrorString(e));
+}
+
+extern "C" int svgir_env_backdrop_sg(int32_t W, int32_t H, const float* intr, const float* c2w_rot, const svgir_sg_light* light,
+                                     const float* image, const float* opacity, const float* vfeature, float* out, void* stream) {
+    if (W < 1 || H < 1) return report_error(SVGIR_ERR_INVALID, "env_backdrop_sg: bad image size W=%d H=%d", W, H);
+    if (int rc = sg_light_valid(light, "env_backdrop_sg")) return rc;
+    if (!intr || !c2w_rot) return report_error(SVGIR_ERR_INVALID, "env_backdrop_sg: the intrinsics and the camera rotation must be provided");
+    if (!image || !opacity || !vfeature || !out)
+        return report_error(SVGIR_ERR_INVALID, "env_backdrop_sg: image, opacity, vfeature and out must be provided");
+    if (!std::isfinite(intr[0]) || !std::isfinite(intr[1]) || intr[0] == 0.f || intr[1] == 0.f)
+        return report_error(SVGIR_ERR_INVALID, "env_backdrop_sg: the focal lengths must be finite and non-zero (fx=%g fy=%g)", (double)intr[0],
+                            (double)intr[1]);
+    const size_t N = (size_t)W * H, blocks = (N + BLOCK - 1) / BLOCK;
+    if (blocks > 0x7fffffffu) return report_error(SVGIR_ERR_INVALID, "env_backdrop_sg: image %d x %d exceeds the supported size", W, H);
+    BackdropArgs a{};
+    a.W = W; a.H = H; a.fx = intr[0]; a.fy = intr[1]; a.cx = intr[2]; a.cy = intr[3];
+    for (int j = 0; j < 9; j++) a.R[j] = c2w_rot[j];
+    a.env_h = 1; a.env_w = light->count; a.env_scale = 1.f; a.env_tab = (const float4*)light->work;
+    a.image = image; a.opacity = opacity; a.pbr = vfeature; a.out = out;
+    hipStream_t s = (hipStream_t)stream;
+    StageMarks tm = stage_begin(s);
+    hipLaunchKernelGGL(backdrop_sg_table_kernel, dim3(1), dim3(BLOCK), 0, s, light->lobes, light->count, (float4*)light->work);
+    stage_mark(tm, "backdrop_sg_table");
+    hipLaunchKernelGGL(backdrop_kernel<LIGHT_SG>, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    stage_mark(tm, "backdrop_sg");
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SVGIR_OK : report_error(SVGIR_ERR_HIP, "env_backdrop_sg launch failed: %s", hipGetErrorString(e));
 }

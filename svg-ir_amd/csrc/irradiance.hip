@@ -25,11 +25,14 @@
 // (svgir_radiance_loss_forward / _backward; GaussianModel.get_radiance_loss, scene/gaussian_model.py:544-575): the selection of the
 // sample, the light of the hit surfel's escaped samples looked up in the kernel (env_lookup.hpp, the f(env) table of the shading
 // kernels) and the L1 against the cached radiance.  It shares irr_load_corners / irr_light / irr_spec with the kernels above; no
-// [N,S,3] light tensor and no [N,S,3] gradient exist on that path.  See the comment in front of radiance_loss_fwd_kernel.
+// [N,S,3] light tensor and no [N,S,3] gradient exist on that path.  See the comment in front of radiance_loss_fwd_kernel.  Both kernels
+// are instantiated for the lat-long texture and for the spherical-Gaussian light (sg_light.hpp; svgir_radiance_loss_forward_sg /
+// _backward_sg): the light of a sample and the scatter of its adjoint are the only light-specific parts.
 #include <cmath>
 
 #include "common.hpp"
 #include "env_lookup.hpp"
+#include "sg_light.hpp"
 
 namespace svgir {
 
@@ -356,6 +359,15 @@ __device__ __forceinline__ void rl_light(const RadLossArgs& a, const RlTransform
     for (int ch = 0; ch < 3; ch++) env[ch] = nan ? NAN : (E[ch] * a.env_scale) * area;
 }
 
+// LIGHT_SG (svgir_radiance_loss_forward_sg / _backward_sg): envmap[h,s,c] = L_c(ray_d[h,s]) * areas[h,s] with L the unclamped fp32 SG light
+// of the raw direction (sg_eval, m ascending; the prepared table in LDS).  No latitude, no transform: nothing to range-check.
+__device__ __forceinline__ void rl_light_sg(const float4* __restrict__ st, int M, const float* ld, float area, float* env) {
+    float L[3];
+    sg_eval(st, M, ld, L);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) env[ch] = L[ch] * area;
+}
+
 // torch.argmax's order on (value, index) pairs: does (nv, ni) come before (bv, bi)?  An index < 0 is "no element".
 __device__ __forceinline__ bool rl_before(float nv, int ni, float bv, int bi) {
     if (ni < 0) return false;
@@ -379,8 +391,18 @@ __global__ void __launch_bounds__(BLOCK) radiance_loss_table_kernel(const ShadeT
     if (i < n1) z1[i] = 0.f;
 }
 
+// LIGHT: the light kind (sg_light.hpp), a template parameter so that the texture kernels are the code they were.  The SG light travels in the
+// otherwise unread env fields of RadLossArgs: env_tab = the prepared lobe table, env_w = the lobe count, d_envtab = the table-space sums.
+template <int LIGHT>
 __global__ void __launch_bounds__(BLOCK) radiance_loss_fwd_kernel(const RadLossArgs a) {
     __shared__ double wsum[IRR_WAVES];
+    const float4* sgt = nullptr;
+    if constexpr (LIGHT == LIGHT_SG) {
+        __shared__ float4 st[2 * SVGIR_SG_MAX_LOBES];
+        for (int k = threadIdx.x; k < 2 * a.env_w; k += BLOCK) st[k] = a.env_tab[k];
+        __syncthreads();
+        sgt = st;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t i = (size_t)blockIdx.x * IRR_WAVES + wave;
     const int S = a.S;
@@ -427,7 +449,8 @@ __global__ void __launch_bounds__(BLOCK) radiance_loss_fwd_kernel(const RadLossA
                 irr_light(q, c, ld, a.uvs[hs * 2], a.uvs[hs * 2 + 1]);
                 EnvTap tp;
                 float env[3];
-                rl_light(a, T, ld, a.area[hs], tp, env);
+                if constexpr (LIGHT == LIGHT_SG) rl_light_sg(sgt, a.env_w, ld, a.area[hs], env);
+                else rl_light(a, T, ld, a.area[hs], tp, env);
                 float b[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) b[k] = irr_spec<false>(c, q, k, nullptr);
@@ -484,11 +507,23 @@ __global__ void __launch_bounds__(RL_FINAL) radiance_loss_final_kernel(const dou
     }
 }
 
+// LIGHT_SG: sEnv holds the lobes' 8 M table-space sums (ntex3 = 8 M, env_in_lds = 1), behind it the prepared table (8 M floats) and every
+// wave's 64 parked samples (direction, adjoint of L: two float4 each).  The sample loop runs in wave-uniform passes of 64: a lane parks the
+// adjoint g_c = d_R[i,c] * irr_c / S * areas[h,s] of its sample's light (zeros for an occluded or absent sample, and for a channel without
+// upstream) and the wave turns the pass into the lobes' sums with sg_adjoint_accumulate (sg_light.hpp).
+template <int LIGHT>
 __global__ void __launch_bounds__(RLB_WAVES * 64) radiance_loss_bwd_kernel(const RadLossArgs a) {
-    extern __shared__ double rl_smem[];   // [RLB_WAVES] the waves' d_ratio sums, then the env-gradient table [ntex3] (env_in_lds)
+    extern __shared__ __attribute__((aligned(16))) double rl_smem[];   // [RLB_WAVES] the waves' d_ratio sums, then the env-gradient table [ntex3] (env_in_lds)
     double* sEnv = rl_smem + RLB_WAVES;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int S = a.S, N = a.N;
+    float4 *sgt = nullptr, *recD = nullptr, *recG = nullptr;
+    if constexpr (LIGHT == LIGHT_SG) {
+        sgt = reinterpret_cast<float4*>(sEnv + a.ntex3);
+        recD = sgt + 2 * a.env_w + wave * 128;
+        recG = recD + 64;
+        for (int k = threadIdx.x; k < 2 * a.env_w; k += RLB_WAVES * 64) sgt[k] = a.env_tab[k];
+    }
     if (a.env_in_lds) {
         for (int k = threadIdx.x; k < a.ntex3; k += RLB_WAVES * 64) sEnv[k] = 0.0;
         __syncthreads();
@@ -527,8 +562,46 @@ __global__ void __launch_bounds__(RLB_WAVES * 64) radiance_loss_bwd_kernel(const
         IrrCorners c;
         irr_load_corners<false>(c, vdir, h, a.normals, a.albedos, a.roughnesses);
         float dalb[3][4] = {}, drough = 0.f;
-        for (int s = lane; s < S; s += IRR_WAVE) {
+        for (int s = lane; (LIGHT == LIGHT_SG ? s - lane : s) < S; s += IRR_WAVE) {   // (LIGHT_SG: whole passes, the wave stays together)
             const size_t hs = h * (size_t)S + s;
+            if constexpr (LIGHT == LIGHT_SG) {
+                float4 pd = make_float4(0.f, 0.f, 0.f, 0.f), pg = pd;
+                if (s < S && a.hit[hs] == -1) {
+                    const float ld[3] = {a.ray_d[hs * 3], a.ray_d[hs * 3 + 1], a.ray_d[hs * 3 + 2]};
+                    IrrLight q;
+                    irr_light(q, c, ld, a.uvs[hs * 2], a.uvs[hs * 2 + 1]);
+                    const float area = a.area[hs];
+                    float env[3];
+                    rl_light_sg(sgt, a.env_w, ld, area, env);
+                    float b[4], ds[4], gl[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int k = 0; k < 4; k++) b[k] = irr_spec<true>(c, q, k, &ds[k]);
+                    const float dq = ((q.w[0] * ds[0] + q.w[1] * ds[1]) + q.w[2] * ds[2]) + q.w[3] * ds[3];
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) {
+                        float t[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            t[k] = b[k] + c.alb[ch][k] * IRR_1_PI;
+                            if (g[ch] != 0.f) dalb[ch][k] += (((g[ch] * q.w[k]) * env[ch]) * IRR_1_PI) / fs;   // (skipped, not multiplied by 0: see below)
+                        }
+                        const float irr = ((q.w[0] * t[0] + q.w[1] * t[1]) + q.w[2] * t[2]) + q.w[3] * t[3];
+                        if (g[ch] != 0.f) gl[ch] = ((g[ch] * irr) / fs) * area;   // d L / d L_ch(ray_d[h,s])
+                    }
+                    const float ge[3] = {g[0] != 0.f ? (g[0] * env[0]) / fs : 0.f, g[1] != 0.f ? (g[1] * env[1]) / fs : 0.f,
+                                         g[2] != 0.f ? (g[2] * env[2]) / fs : 0.f};
+                    drough += ((ge[0] + ge[1]) + ge[2]) * dq;
+                    pd = make_float4(ld[0], ld[1], ld[2], 0.f);
+                    pg = make_float4(gl[0], gl[1], gl[2], 0.f);
+                }
+                if (a.d_envtab) {   // (uniform)
+                    recD[lane] = pd; recG[lane] = pg;
+                    wave_lds_sync();
+                    sg_adjoint_accumulate(recD, recG, min(IRR_WAVE, S - (s - lane)), sgt, sEnv, a.env_w, lane, IRR_WAVE);
+                    wave_lds_sync();
+                }
+                continue;
+            }
             if (a.hit[hs] != -1) continue;
             const float ld[3] = {a.ray_d[hs * 3], a.ray_d[hs * 3 + 1], a.ray_d[hs * 3 + 2]};
             IrrLight q;
@@ -633,13 +706,93 @@ RlWork rl_work(int32_t N, int32_t env_h, int32_t env_w) {
     return w;
 }
 
-bool rl_args_ok(const svgir_radiance_loss_params* p) {
-    if (!p || p->N < 0 || p->S < 1 || p->env_h < 1 || p->env_w < 1) return false;
-    if ((size_t)p->N * (size_t)p->S > ((size_t)1 << 31) - 1 || (int64_t)p->env_h * p->env_w > (int64_t)1 << 26) return false;
+// (sg: the _sg entry points, which do not read the env* fields)
+bool rl_args_ok(const svgir_radiance_loss_params* p, bool sg = false) {
+    if (!p || p->N < 0 || p->S < 1 || (!sg && (p->env_h < 1 || p->env_w < 1))) return false;
+    if ((size_t)p->N * (size_t)p->S > ((size_t)1 << 31) - 1 || (!sg && (int64_t)p->env_h * p->env_w > (int64_t)1 << 26)) return false;
     if (p->N == 0) return true;
     return p->xyz && p->camera_center && p->geo_normal && p->ray_d && p->areas && p->visibility && p->normals && p->albedos && p->roughnesses &&
-           p->hit_indices && p->uvs && p->radiances && p->radiance_ratio && p->env && p->work && !((uintptr_t)p->work & 15);
+           p->hit_indices && p->uvs && p->radiances && p->radiance_ratio && (sg || p->env) && p->work && !((uintptr_t)p->work & 15);
 }
+
+// The backward's persistent grid: as many workgroups as are resident at once (registers and the LDS table both bound the workgroups per
+// CU: one at ~230 VGPRs whatever the table), RLB_MAX_BLOCKS at most -- every further workgroup would zero and flush a table of its own for
+// nothing.  Per device and light kind: the opt-in for > 64 KB of dynamic LDS, set once, and the resident count of the last LDS size asked
+// for (a training run has one map size; both are idempotent, so races are harmless).  0: a HIP call failed.
+template <int LIGHT>
+size_t rl_resident(size_t lds) {
+    struct DevState { bool attr_set; size_t lds, resident; };
+    static DevState state[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    const bool slot = dev >= 0 && dev < 64;
+    if (!slot || !state[dev].attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(radiance_loss_bwd_kernel<LIGHT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)RL_LDS_BYTES) != hipSuccess)
+            return 0;
+        if (slot) state[dev].attr_set = true;
+    }
+    if (slot && state[dev].resident != 0 && state[dev].lds == lds) return state[dev].resident;
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(radiance_loss_bwd_kernel<LIGHT>), RLB_WAVES * 64, lds) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return 0;
+    const size_t resident = (size_t)std::max(per_cu, 1) * (size_t)std::max(cus, 1);
+    if (slot) { state[dev].resident = 0; state[dev].lds = lds; state[dev].resident = resident; }
+    return resident;
+}
+
+// ---- the SG light's host side: p->work = [table-space sums, 8 M floats | partial sums, doubles]; the prepared table is light->work
+struct RlSgWork { size_t dtab, part, bytes, nparts; };
+RlSgWork rl_sg_work(int32_t N, int32_t count) {
+    RlSgWork w;
+    w.dtab = 0;
+    w.part = (size_t)8 * count * sizeof(float);
+    w.nparts = std::max(((size_t)N + IRR_WAVES - 1) / IRR_WAVES, (size_t)RLB_MAX_BLOCKS);
+    w.bytes = w.part + w.nparts * 8;
+    return w;
+}
+
+RadLossArgs rl_args_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* l) {
+    RadLossArgs a{};
+    a.N = p->N; a.S = p->S;
+    a.xyz = p->xyz; a.cam = p->camera_center; a.geo = p->geo_normal; a.ray_d = p->ray_d; a.area = p->areas; a.vis = p->visibility;
+    a.normals = p->normals; a.albedos = p->albedos; a.roughnesses = p->roughnesses; a.uvs = p->uvs; a.radiances = p->radiances;
+    a.ratio = p->radiance_ratio; a.hit = p->hit_indices;
+    a.env_tab = (const float4*)l->work; a.env_h = 1; a.env_w = l->count; a.env_scale = 1.f;
+    return a;
+}
+
+// prologue of both SG calls: the prepared table; backward: the clear of the table-space sums and of the two per-surfel gradients
+__global__ void __launch_bounds__(BLOCK) radiance_loss_sg_table_kernel(const float* __restrict__ lobes, int M, float4* __restrict__ tab,
+                                                                       float* __restrict__ zero, int nzero, float* z0, size_t n0, float* z1, size_t n1) {
+    sg_table_build(lobes, M, tab, zero, nzero);
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n0) z0[i] = 0.f;
+    if (i < n1) z1[i] = 0.f;
+}
+
+// epilogue of the SG backward (one workgroup): the pull-back of the table-space sums to d_lobes [M,7] and d_ratio = the workgroups' partial
+// sums in radiance_loss_env_grad_kernel's fixed tree
+__global__ void __launch_bounds__(BLOCK) radiance_loss_sg_grad_kernel(const float* __restrict__ lobes, const float4* __restrict__ tab,
+                                                                      const float* __restrict__ dtab, float* __restrict__ dlobes, int M,
+                                                                      const double* __restrict__ ratio_part, int nparts, float* __restrict__ d_ratio) {
+    if (d_ratio) {
+        __shared__ double part[BLOCK];
+        double t = 0.0;
+        for (int k = threadIdx.x; k < nparts; k += BLOCK) t += ratio_part[k];
+        part[threadIdx.x] = t;
+        __syncthreads();
+        for (int h = BLOCK / 2; h >= 1; h >>= 1) {
+            if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) *d_ratio = (float)part[0];
+    }
+    if (dlobes && (int)threadIdx.x < M) sg_pullback(lobes, tab, dtab, threadIdx.x, dlobes);
+}
+
+static_assert(SVGIR_SG_MAX_LOBES <= BLOCK, "radiance_loss_sg_grad_kernel: one thread per lobe, one block");
 
 RadLossArgs rl_args(const svgir_radiance_loss_params* p, const RlWork& w) {
     RadLossArgs a{};
@@ -683,7 +836,7 @@ int svgir_radiance_loss_forward(const svgir_radiance_loss_params* p, int32_t* sa
     const size_t blocks = ((size_t)p->N + IRR_WAVES - 1) / IRR_WAVES;
     hipLaunchKernelGGL(radiance_loss_table_kernel, dim3((t.ntexel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, t, (float*)nullptr, (size_t)0,
                        (float*)nullptr, (size_t)0);
-    hipLaunchKernelGGL(radiance_loss_fwd_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(radiance_loss_fwd_kernel<LIGHT_TEX>, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
     hipLaunchKernelGGL(radiance_loss_final_kernel, dim3(1), dim3(RL_FINAL), 0, s, (const double*)a.partial, blocks, 3.0 * (double)p->N, loss_sum,
                        loss);
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
@@ -702,33 +855,8 @@ int svgir_radiance_loss_backward(const svgir_radiance_loss_params* p, const int3
     a.ratio_part = (double*)((char*)p->work + w.part);
     size_t lds = (size_t)RLB_WAVES * 8;
     if (d_env && lds + (size_t)a.ntex3 * 8 <= RL_LDS_BYTES) { a.env_in_lds = 1; lds += (size_t)a.ntex3 * 8; }
-    // persistent workgroups: as many as are resident at once (registers and the LDS table both bound the workgroups per CU: one at
-    // ~230 VGPRs whatever the table), RLB_MAX_BLOCKS at most -- every further workgroup would zero and flush a table of its own for nothing.
-    // Per device: the opt-in for > 64 KB of dynamic LDS, set once, and the resident count of the last LDS size asked for (a training run
-    // has one map size; both are idempotent, so races are harmless).
-    size_t resident = 0;
-    {
-        struct DevState { bool attr_set; size_t lds, resident; };
-        static DevState state[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return SVGIR_ERR_HIP;
-        const bool slot = dev >= 0 && dev < 64;
-        if (!slot || !state[dev].attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(radiance_loss_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)RL_LDS_BYTES) != hipSuccess)
-                return SVGIR_ERR_HIP;
-            if (slot) state[dev].attr_set = true;
-        }
-        if (slot && state[dev].resident != 0 && state[dev].lds == lds) resident = state[dev].resident;
-        else {
-            int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(radiance_loss_bwd_kernel), RLB_WAVES * 64, lds) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-                return SVGIR_ERR_HIP;
-            resident = (size_t)std::max(per_cu, 1) * (size_t)std::max(cus, 1);
-            if (slot) { state[dev].resident = 0; state[dev].lds = lds; state[dev].resident = resident; }
-        }
-    }
+    const size_t resident = rl_resident<LIGHT_TEX>(lds);   // (persistent workgroups)
+    if (!resident) return SVGIR_ERR_HIP;
     const int blocks = (int)std::min<size_t>(((size_t)p->N + RLB_WAVES - 1) / RLB_WAVES, std::min<size_t>(resident, RLB_MAX_BLOCKS));
     ShadeTables t = rl_tables(p, w);
     t.zero = a.d_envtab; t.nzero = a.d_envtab ? a.ntex3 : 0;
@@ -736,11 +864,67 @@ int svgir_radiance_loss_backward(const svgir_radiance_loss_params* p, const int3
     const size_t items = std::max(std::max((size_t)t.ntexel, (size_t)t.nzero), n_alb);
     hipLaunchKernelGGL(radiance_loss_table_kernel, dim3((unsigned)((items + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, t, d_albedos, n_alb,
                        d_roughnesses, n_rough);
-    hipLaunchKernelGGL(radiance_loss_bwd_kernel, dim3(blocks), dim3(RLB_WAVES * 64), lds, s, a);
+    hipLaunchKernelGGL(radiance_loss_bwd_kernel<LIGHT_TEX>, dim3(blocks), dim3(RLB_WAVES * 64), lds, s, a);
     if (d_env || d_radiance_ratio)
         hipLaunchKernelGGL(radiance_loss_env_grad_kernel, dim3(d_env ? (a.ntex3 + BLOCK - 1) / BLOCK : 1), dim3(BLOCK), 0, s, p->env,
                            (const float*)a.d_envtab, d_env, a.ntex3, p->env_softplus, (const double*)a.ratio_part, blocks, d_radiance_ratio);
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+}
+
+size_t svgir_radiance_loss_sg_work_bytes(int32_t N, int32_t count) {
+    if (N < 0 || count < 1 || count > SVGIR_SG_MAX_LOBES) return 0;
+    return svgir::rl_sg_work(N, count).bytes;
+}
+
+int svgir_radiance_loss_forward_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* light, int32_t* sample_indices, float* radiance,
+                                   double* loss_sum, float* loss, void* stream) {
+    using namespace svgir;
+    if (int rc = sg_light_valid(light, "radiance_loss_forward_sg")) return rc;
+    if (!rl_args_ok(p, true) || (p->N > 0 && (!sample_indices || !radiance || !loss_sum || !loss)))
+        return report_error(SVGIR_ERR_INVALID, "radiance_loss_forward_sg: bad N / S, a NULL input or output, or a NULL / misaligned work");
+    if (p->N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const RlSgWork w = rl_sg_work(p->N, light->count);
+    RadLossArgs a = rl_args_sg(p, light);
+    a.sample_out = sample_indices; a.R_out = radiance; a.partial = (double*)((char*)p->work + w.part);
+    const size_t blocks = ((size_t)p->N + IRR_WAVES - 1) / IRR_WAVES;
+    hipLaunchKernelGGL(radiance_loss_sg_table_kernel, dim3(1), dim3(BLOCK), 0, s, light->lobes, light->count, (float4*)light->work, (float*)nullptr, 0,
+                       (float*)nullptr, (size_t)0, (float*)nullptr, (size_t)0);
+    hipLaunchKernelGGL(radiance_loss_fwd_kernel<LIGHT_SG>, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(radiance_loss_final_kernel, dim3(1), dim3(RL_FINAL), 0, s, (const double*)a.partial, blocks, 3.0 * (double)p->N, loss_sum,
+                       loss);
+    return hipGetLastError() == hipSuccess ? 0 : report_error(SVGIR_ERR_HIP, "radiance_loss_forward_sg: launch failed");
+}
+
+int svgir_radiance_loss_backward_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* light, const int32_t* sample_indices,
+                                    const float* radiance, const float* d_loss, float* d_lobes, float* d_albedos, float* d_roughnesses,
+                                    float* d_radiance_ratio, void* stream) {
+    using namespace svgir;
+    if (int rc = sg_light_valid(light, "radiance_loss_backward_sg")) return rc;
+    if (!rl_args_ok(p, true) || (p->N > 0 && (!sample_indices || !radiance || !d_loss || !d_albedos || !d_roughnesses)))
+        return report_error(SVGIR_ERR_INVALID, "radiance_loss_backward_sg: bad N / S, a NULL input or output, or a NULL / misaligned work");
+    if (p->N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int M = light->count;
+    const RlSgWork w = rl_sg_work(p->N, M);
+    RadLossArgs a = rl_args_sg(p, light);
+    a.sample_in = sample_indices; a.R_in = radiance; a.g = d_loss; a.d_albedos = d_albedos; a.d_roughnesses = d_roughnesses;
+    a.d_envtab = d_lobes ? (float*)((char*)p->work + w.dtab) : nullptr;
+    a.ratio_part = (double*)((char*)p->work + w.part);
+    a.env_in_lds = 1; a.ntex3 = d_lobes ? 8 * M : 0;
+    // the waves' d_ratio sums, the fp64 sums, the prepared table, the waves' parked samples (two float4 per lane): 29 KB at M = 128
+    const size_t lds = (size_t)RLB_WAVES * 8 + (size_t)a.ntex3 * 8 + (size_t)8 * M * 4 + (size_t)RLB_WAVES * 128 * 16;
+    const size_t resident = rl_resident<LIGHT_SG>(lds);
+    if (!resident) return report_error(SVGIR_ERR_HIP, "radiance_loss_backward_sg: querying the device failed");
+    const int blocks = (int)std::min<size_t>(((size_t)p->N + RLB_WAVES - 1) / RLB_WAVES, std::min<size_t>(resident, RLB_MAX_BLOCKS));
+    const size_t n_alb = (size_t)p->N * 12, n_rough = (size_t)p->N * 4;
+    hipLaunchKernelGGL(radiance_loss_sg_table_kernel, dim3((unsigned)((n_alb + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, light->lobes, M,
+                       (float4*)light->work, a.d_envtab, a.ntex3, d_albedos, n_alb, d_roughnesses, n_rough);
+    hipLaunchKernelGGL(radiance_loss_bwd_kernel<LIGHT_SG>, dim3(blocks), dim3(RLB_WAVES * 64), lds, s, a);
+    if (d_lobes || d_radiance_ratio)
+        hipLaunchKernelGGL(radiance_loss_sg_grad_kernel, dim3(1), dim3(BLOCK), 0, s, light->lobes, (const float4*)light->work, (const float*)a.d_envtab,
+                           d_lobes, M, (const double*)a.ratio_part, blocks, d_radiance_ratio);
+    return hipGetLastError() == hipSuccess ? 0 : report_error(SVGIR_ERR_HIP, "radiance_loss_backward_sg: launch failed");
 }
 
 int svgir_pbgi_irradiance_sample(int32_t N, int32_t S, const int32_t* sample_indices, const float* ray_d, const float* envmap,

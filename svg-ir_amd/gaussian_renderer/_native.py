@@ -72,7 +72,8 @@ class ShadeParams(C.Structure):
 
 
 class SgLight(C.Structure):
-    """svgir_sg_light: the spherical-Gaussian direct light of svgir_sg_eval / svgir_shade_forward_sg / svgir_shade_backward_sg."""
+    """svgir_sg_light: the spherical-Gaussian direct light of svgir_sg_eval(_backward), svgir_shade_forward_sg / _backward_sg,
+    svgir_env_backdrop_sg and svgir_radiance_loss_forward_sg / _backward_sg."""
     _fields_ = [("count", C.c_int32), ("lobes", C.c_void_p), ("work", C.c_void_p)]
 
 
@@ -219,6 +220,16 @@ def _load():
     lib.svgir_shade_forward_sg.argtypes = [C.POINTER(ShadeParams), C.POINTER(SgLight)] + [C.c_void_p] * 4
     lib.svgir_shade_backward_sg.restype = C.c_int
     lib.svgir_shade_backward_sg.argtypes = [C.POINTER(ShadeParams), C.POINTER(SgLight)] + [C.c_void_p] * 12
+    lib.svgir_sg_eval_backward.restype = C.c_int
+    lib.svgir_sg_eval_backward.argtypes = [C.POINTER(SgLight), C.c_int64] + [C.c_void_p] * 6
+    lib.svgir_env_backdrop_sg.restype = C.c_int
+    lib.svgir_env_backdrop_sg.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 2 + [C.POINTER(SgLight)] + [C.c_void_p] * 5
+    lib.svgir_radiance_loss_sg_work_bytes.restype = C.c_size_t
+    lib.svgir_radiance_loss_sg_work_bytes.argtypes = [C.c_int32] * 2
+    lib.svgir_radiance_loss_forward_sg.restype = C.c_int
+    lib.svgir_radiance_loss_forward_sg.argtypes = [C.POINTER(RadianceLossParams), C.POINTER(SgLight)] + [C.c_void_p] * 5
+    lib.svgir_radiance_loss_backward_sg.restype = C.c_int
+    lib.svgir_radiance_loss_backward_sg.argtypes = [C.POINTER(RadianceLossParams), C.POINTER(SgLight)] + [C.c_void_p] * 8
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -242,7 +253,9 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_smooth_loss_backward", "svgir_env_backdrop", "svgir_radiance_loss_work_bytes", "svgir_radiance_loss_forward",
            "svgir_radiance_loss_backward", "svgir_activate_partials", "svgir_activate_forward", "svgir_activate_backward",
            "svgir_view_metrics_partials", "svgir_view_metrics", "svgir_capture_u8", "svgir_albedo_scale_partials", "svgir_albedo_scale",
-           "svgir_sg_grad_work_bytes", "svgir_sg_eval", "svgir_shade_forward_sg", "svgir_shade_backward_sg")
+           "svgir_sg_grad_work_bytes", "svgir_sg_eval", "svgir_shade_forward_sg", "svgir_shade_backward_sg",
+           "svgir_sg_eval_backward", "svgir_env_backdrop_sg", "svgir_radiance_loss_sg_work_bytes", "svgir_radiance_loss_forward_sg",
+           "svgir_radiance_loss_backward_sg")
 
 
 _scope = threading.local()

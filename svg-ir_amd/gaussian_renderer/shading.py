@@ -12,7 +12,8 @@ PyTorch fallback.
 
 The direct light is one of the reference's three classes: `DirectLightMap` (`.env`) and `EnvLight` (`.envmap`), lat-long textures, or
 `DirectLightSG` (`.lgtSGs` [M,7], scene/direct_light_sg.py), a mixture of spherical-Gaussian lobes evaluated per sample inside the
-kernels (`svgir_shade_forward_sg` / `svgir_shade_backward_sg`); `sg_direct_light` / `compute_envmap` are that light on its own.
+kernels (`svgir_shade_forward_sg` / `svgir_shade_backward_sg`); `sg_direct_light` / `compute_envmap` are that light on its own,
+differentiable (`svgir_sg_eval` / `svgir_sg_eval_backward`).
 """
 import ctypes as C
 
@@ -245,7 +246,8 @@ def _is_sg(light):
 def _no_sg(light, what):
     if _is_sg(light):
         raise TypeError(f"{what} has no spherical-Gaussian (lgtSGs) light path: it needs the lat-long texture of DirectLightMap / EnvLight "
-                        f"(with an SG light use the unfused calls: shade_and_pack + the rasterizer, sg_direct_light)")
+                        f"(with an SG light use shade_and_pack + the rasterizer, sg_direct_light, render_view.sg_environment_backdrop, "
+                        f"losses.fused_radiance_loss_sg)")
 
 
 def _sg_light(lobes, dev):
@@ -257,19 +259,51 @@ def _sg_light(lobes, dev):
     return lt, [lb, work]
 
 
+class _SGEval(torch.autograd.Function):
+    """svgir_sg_eval / svgir_sg_eval_backward: the unclamped light of `dirs` [..., 3], differentiable w.r.t. the raw lobes and the
+    directions (each only when it requires grad)."""
+
+    @staticmethod
+    def forward(ctx, lobes, dirs):
+        dev = lobes.device
+        lt, keep = _sg_light(lobes, dev)
+        d = N.f32c(dirs.detach(), dev)
+        out = N.out_tensor(d.shape, torch.float32, dev)
+        n = d.numel() // 3
+        if n:
+            N.check(N.lib.svgir_sg_eval(lt, n, d.data_ptr(), out.data_ptr(), N.stream_ptr(dev)), "sg_eval")
+        ctx.save_for_backward(lobes, dirs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lobes, dirs = ctx.saved_tensors
+        want_lobes, want_dirs = ctx.needs_input_grad
+        if not (want_lobes or want_dirs):
+            return None, None
+        dev = lobes.device
+        lt, keep = _sg_light(lobes, dev)
+        d, g = N.f32c(dirs.detach(), dev), N.f32c(g, dev)
+        d_lobes = N.out_tensor(keep[0].shape, torch.float32, dev) if want_lobes else None
+        d_dirs = N.out_tensor(d.shape, torch.float32, dev) if want_dirs else None
+        gwork = torch.empty(N.lib.svgir_sg_grad_work_bytes(lt.count) // 4, dtype=torch.float32, device=dev)
+        if d.numel():
+            N.check(N.lib.svgir_sg_eval_backward(lt, d.numel() // 3, d.data_ptr(), g.data_ptr(), N.ptr(d_lobes), N.ptr(d_dirs), gwork.data_ptr(),
+                                                 N.stream_ptr(dev)), "sg_eval_backward")
+        elif d_lobes is not None:   # (no direction: the library would be asked for an empty dL_ddirs alone)
+            d_lobes.zero_()
+        return (None if d_lobes is None else d_lobes.reshape(lobes.shape).to(lobes.dtype),
+                None if d_dirs is None else d_dirs.reshape(dirs.shape).to(device=dirs.device, dtype=dirs.dtype))
+
+
 def sg_direct_light(lgtSGs, dirs):
     """DirectLightSG.direct_light / render_envmap_sg (scene/direct_light_sg.py:10-46): the unclamped light [..., 3] of the directions
-    `dirs` [..., 3] (used as given, not normalised).  Forward only: no gradient reaches `lgtSGs` or `dirs` through this call."""
+    `dirs` [..., 3] (used as given, not normalised).  Differentiable: the gradient reaches `lgtSGs` and `dirs`, each when it requires grad
+    (svgir_sg_eval_backward)."""
     dev = lgtSGs.device
     if dev.type != "cuda":
         raise RuntimeError("sg_direct_light: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
-    lt, keep = _sg_light(SGLobes(lgtSGs).lobes, dev)
-    d = N.f32c(dirs.detach(), dev)
-    out = N.out_tensor(d.shape, torch.float32, dev)
-    n = d.numel() // 3
-    if n:
-        N.check(N.lib.svgir_sg_eval(lt, n, d.data_ptr(), out.data_ptr(), N.stream_ptr(dev)), "sg_eval")
-    return out
+    return _SGEval.apply(SGLobes(lgtSGs).lobes, dirs)
 
 
 def compute_envmap(lgtSGs, H, W, upper_hemi=False):

@@ -150,6 +150,73 @@ class _RadianceConsistency(torch.autograd.Function):
                 None if d_ratio is None else d_ratio.reshape(ratio_shape)) + (None,) * 11
 
 
+class _RadianceConsistencySG(torch.autograd.Function):
+    """svgir_radiance_loss_forward_sg / _backward_sg: _RadianceConsistency under a spherical-Gaussian light, the raw lobes [M,7] in the
+    texture's place.  Differentiable in the lobes, albedos, roughnesses and radiance_ratio."""
+
+    @staticmethod
+    def forward(ctx, lobes, albedos, roughnesses, radiance_ratio, xyz, camera_center, geo_normal, ray_directions, areas, visibility, normals,
+                radiances, hit, uvs):
+        from gaussian_renderer import shading
+        what = "radiance_consistency_sg"
+        N, S = int(ray_directions.shape[0]), int(ray_directions.shape[1])
+        for t in (lobes, xyz, camera_center, geo_normal, areas, visibility, radiances, radiance_ratio):
+            if not t.is_cuda:
+                raise RuntimeError(f"{what} needs CUDA/HIP tensors (there is no CPU path)")
+        dev, t = _irradiance_inputs(what, N, S, hit, uvs, None, ray_directions, normals, albedos, roughnesses)
+        f = lambda x, shape, name: _rows(what, _native.f32c(x.detach(), dev), shape, name)
+        lt, lkeep = shading._sg_light(shading.SGLobes(lobes).lobes, dev)
+        p = _native.RadianceLossParams()
+        keep = dict(xyz=f(xyz, (N, 3), "xyz"), camera_center=f(camera_center, (3,), "camera_center"), geo_normal=f(geo_normal, (N, 3), "geo_normal"),
+                    ray_d=t[0], areas=f(areas, (N, S), "incident_areas"), visibility=f(visibility, (N, S), "visibility"), normals=t[2],
+                    albedos=t[3], roughnesses=t[4], hit_indices=t[5], uvs=t[6], radiances=f(radiances, (N, S, 3), "radiances"),
+                    radiance_ratio=f(radiance_ratio, (1,), "radiance_ratio"))
+        with torch.cuda.device(dev):
+            keep["work"] = torch.empty(max(_lib.svgir_radiance_loss_sg_work_bytes(N, lt.count), 16), dtype=torch.uint8, device=dev)
+            p.N, p.S = N, S
+            for k, v in keep.items():
+                setattr(p, k, _native.ptr(v))
+            idx = _native.out_tensor((N,), torch.int32, dev)
+            R = _native.out_tensor((N, 3), torch.float32, dev)
+            total = _native.out_tensor((), torch.float64, dev)
+            loss = _native.out_tensor((), torch.float32, dev)
+            if N == 0:   # nothing is launched: the mean of no rows is NaN, as torch's
+                total.zero_()
+                loss.fill_(float("nan"))
+            _native.check(_lib.svgir_radiance_loss_forward_sg(p, lt, _native.ptr(idx), _native.ptr(R), total.data_ptr(), loss.data_ptr(),
+                                                              _native.stream_ptr(dev)), "radiance_loss_forward_sg")
+        # (as _RadianceConsistency: the backward reads the inputs through the raw pointers of `p` and `lt`; `keep` holds the tensors)
+        ctx.p, ctx.lt, ctx.keep = p, lt, (keep, lkeep)
+        ctx.save_for_backward(idx, R)
+        ctx.shapes = (lobes.shape, albedos.shape, roughnesses.shape, radiance_ratio.shape)
+        ctx.mark_non_differentiable(idx, R, total)
+        return loss, idx, R, total
+
+    @staticmethod
+    def backward(ctx, g, _gi, _gr, _gt):
+        idx, R = ctx.saved_tensors
+        p, lt = ctx.p, ctx.lt
+        N = p.N
+        dev = idx.device
+        need_lobes, _, _, need_ratio = ctx.needs_input_grad[:4]
+        with torch.cuda.device(dev):
+            d_lobes = _native.out_tensor((lt.count, 7), torch.float32, dev) if need_lobes else None
+            d_alb = _native.out_tensor((N, 12), torch.float32, dev)
+            d_rough = _native.out_tensor((N, 4), torch.float32, dev)
+            d_ratio = _native.out_tensor((1,), torch.float32, dev) if need_ratio else None
+            if N == 0:
+                for t in (d_lobes, d_ratio):
+                    if t is not None:
+                        t.zero_()
+            gdev = _native.f32c(g.detach(), dev).reshape(1).contiguous()   # the upstream scalar stays on the device
+            _native.check(_lib.svgir_radiance_loss_backward_sg(p, lt, _native.ptr(idx), _native.ptr(R), gdev.data_ptr(), _native.ptr(d_lobes),
+                                                               _native.ptr(d_alb), _native.ptr(d_rough), _native.ptr(d_ratio),
+                                                               _native.stream_ptr(dev)), "radiance_loss_backward_sg")
+        lobes_shape, alb_shape, rough_shape, ratio_shape = ctx.shapes
+        return (None if d_lobes is None else d_lobes.reshape(lobes_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape),
+                None if d_ratio is None else d_ratio.reshape(ratio_shape)) + (None,) * 10
+
+
 def _rows(what, t, shape, name):
     n = 1
     for d in shape:
@@ -248,4 +315,14 @@ class Renderer:
         out = _RadianceConsistency.apply(env, albedos, roughnesses, radiance_ratio, (env_softplus, env_scale, env_transform), xyz,
                                          camera_center, geo_normal, incident_dirs, incident_areas, visibility, normals, radiances,
                                          self.hemi_index_buffers, self.uv_buffers)
+        return out if with_sum else out[:3]
+
+    def radiance_consistency_sg(self, xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, lgtSGs, normals, albedos,
+                                roughnesses, radiances, radiance_ratio, with_sum=False):
+        """radiance_consistency under the reference's DirectLightSG (svgir_radiance_loss_forward_sg / _backward_sg): the light of a
+        sample is the unclamped mixture of the raw lobes `lgtSGs` [M,7] along its incident direction times its area; everything else --
+        the selection, the hit rules, the target, the non-finite rule, the returned tuple -- is radiance_consistency's.  Gradients reach
+        lgtSGs (when it requires grad), albedos, roughnesses and radiance_ratio."""
+        out = _RadianceConsistencySG.apply(lgtSGs, albedos, roughnesses, radiance_ratio, xyz, camera_center, geo_normal, incident_dirs,
+                                           incident_areas, visibility, normals, radiances, self.hemi_index_buffers, self.uv_buffers)
         return out if with_sum else out[:3]

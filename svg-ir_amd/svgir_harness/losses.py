@@ -164,10 +164,26 @@ def fused_radiance_loss(renderer, xyz, camera_center, geo_normal, incident_dirs,
     A row whose radiance or target is not finite makes the loss NaN, as in torch, but contributes to no gradient
     (include/svgir_raster.h)."""
     from gaussian_renderer import shading
-    shading._no_sg(light, "fused_radiance_loss")   # (radiance_loss with envmap = sg_direct_light(lgtSGs, dirs) * areas serves an SG light)
+    # (an SG light: fused_radiance_loss_sg -- or radiance_loss with envmap = sg_direct_light(lgtSGs, dirs) * areas, which carries the
+    # light's gradient through svgir_sg_eval_backward)
+    shading._no_sg(light, "fused_radiance_loss")
     env, softplus, scale, transform = shading._env_of(light)
     out = renderer.radiance_consistency(xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, env, softplus, scale,
                                         transform, normals12, albedos, roughnesses, radiances, radiance_ratio)
+    return out if with_rows else out[0]
+
+
+def fused_radiance_loss_sg(renderer, xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, light, normals12, albedos,
+                           roughnesses, radiances, radiance_ratio, with_rows=False):
+    """fused_radiance_loss for the reference's DirectLightSG (`light.lgtSGs` [M,7]; `Renderer.radiance_consistency_sg`): what
+    `radiance_loss` computes when it is fed envmap = sg_direct_light(light.lgtSGs, incident_dirs) * incident_areas, without that [N,S,3]
+    tensor or its gradient.  Gradients reach light.lgtSGs (when it requires grad), albedos, roughnesses and radiance_ratio; the return
+    value and the non-finite rule are fused_radiance_loss's."""
+    from gaussian_renderer import shading
+    if not shading._is_sg(light):
+        raise TypeError("fused_radiance_loss_sg: the light must expose .lgtSGs (DirectLightSG); a texture light goes through fused_radiance_loss")
+    out = renderer.radiance_consistency_sg(xyz, camera_center, geo_normal, incident_dirs, incident_areas, visibility, light.lgtSGs, normals12,
+                                           albedos, roughnesses, radiances, radiance_ratio)
     return out if with_rows else out[0]
 
 

@@ -188,14 +188,34 @@ def unpack(rendered, bg_color, is_training):
     return res
 
 
-def _host_f32(x, shape, what):
+def _host_f32(x, shape, what, who="environment_backdrop"):
     """A small camera / transform matrix as a contiguous fp32 numpy array (tensors on the GPU are copied to the host)."""
     if torch.is_tensor(x):
         x = x.detach().cpu().numpy()
     a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
     if a.shape not in shape:
-        raise RuntimeError(f"environment_backdrop: {what} must have shape {' or '.join(str(s) for s in shape)}, got {a.shape}")
+        raise RuntimeError(f"{who}: {what} must have shape {' or '.join(str(s) for s in shape)}, got {a.shape}")
     return a
+
+
+def _backdrop_camera(who, intrinsics, c2w, image, opacity, vfeature):
+    """The checks both backdrops share: (device, {fx, fy, cx, cy}, c2w[:3,:3]) as the C arrays of the call."""
+    dev = image.device
+    if dev.type != "cuda" or opacity.device.type != "cuda" or vfeature.device.type != "cuda":
+        raise RuntimeError(f"{who}: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
+    K = _host_f32(intrinsics, ((3, 3),), "intrinsics", who)
+    R = _host_f32(c2w, ((4, 4), (3, 3)), "c2w", who)[:3, :3]
+    return dev, (C.c_float * 4)(K[0, 0], K[1, 1], K[0, 2], K[1, 2]), (C.c_float * 9)(*R.reshape(-1))
+
+
+def _backdrop_planes(who, dev, image, opacity, vfeature):
+    """(image, opacity, vfeature as contiguous fp32, H, W, the poisoned [9,H,W] result) -- the planes' shape check of both backdrops."""
+    im, op, vf = (N.f32c(t.detach(), dev) for t in (image, opacity, vfeature))
+    H, W = im.shape[-2], im.shape[-1]
+    if im.numel() != 3 * H * W or op.numel() != H * W or vf.dim() != 3 or vf.shape[0] < 3 or tuple(vf.shape[1:]) != (H, W):
+        raise RuntimeError(f"{who}: expected image [3,H,W], opacity [1,H,W], vfeature [>=3,H,W], got "
+                           f"{tuple(image.shape)}, {tuple(opacity.shape)}, {tuple(vfeature.shape)}")
+    return im, op, vf, H, W, N.out_tensor((9, H, W), torch.float32, dev)
 
 
 def environment_backdrop(light, intrinsics, c2w, image, opacity, vfeature):
@@ -206,14 +226,8 @@ def environment_backdrop(light, intrinsics, c2w, image, opacity, vfeature):
     the host; image [3,H,W], opacity [1,H,W], vfeature [>= 3,H,W]: the rasterizer's raw outputs (its first three vfeature planes are
     the pbr).  Returns {env_only, render_env, pbr_env}: [3,H,W] views of one buffer; they never require grad (the reference runs
     this tail under no_grad)."""
-    shading._no_sg(light, "environment_backdrop")   # (the backdrop kernel samples the lat-long texture; an SG light has none)
-    dev = image.device
-    if dev.type != "cuda" or opacity.device.type != "cuda" or vfeature.device.type != "cuda":
-        raise RuntimeError("environment_backdrop: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
-    K = _host_f32(intrinsics, ((3, 3),), "intrinsics")
-    R = _host_f32(c2w, ((4, 4), (3, 3)), "c2w")[:3, :3]
-    intr = (C.c_float * 4)(K[0, 0], K[1, 1], K[0, 2], K[1, 2])
-    rot = (C.c_float * 9)(*R.reshape(-1))
+    shading._no_sg(light, "environment_backdrop")   # (this kernel samples the lat-long texture; an SG light: sg_environment_backdrop)
+    dev, intr, rot = _backdrop_camera("environment_backdrop", intrinsics, c2w, image, opacity, vfeature)
     src = getattr(light, "env", getattr(light, "envmap", None))
     if torch.is_tensor(src) and src.device.type != "cuda":
         raise RuntimeError("environment_backdrop: the light must live on the GPU (libsvgir_raster.so has no CPU path)")
@@ -224,16 +238,29 @@ def environment_backdrop(light, intrinsics, c2w, image, opacity, vfeature):
         env = env.reshape((-1,) + tuple(env.shape[-3:]))[0]
         if env.shape[-1] != 3:
             raise RuntimeError(f"environment_backdrop: the environment map must have 3 channels, got {tuple(env.shape)}")
-        im, op, vf = (N.f32c(t.detach(), dev) for t in (image, opacity, vfeature))
-        H, W = im.shape[-2], im.shape[-1]
-        if im.numel() != 3 * H * W or op.numel() != H * W or vf.dim() != 3 or vf.shape[0] < 3 or tuple(vf.shape[1:]) != (H, W):
-            raise RuntimeError(f"environment_backdrop: expected image [3,H,W], opacity [1,H,W], vfeature [>=3,H,W], got "
-                               f"{tuple(image.shape)}, {tuple(opacity.shape)}, {tuple(vfeature.shape)}")
+        im, op, vf, H, W, out = _backdrop_planes("environment_backdrop", dev, image, opacity, vfeature)
         work = torch.empty((env.shape[0] * env.shape[1], 4), dtype=torch.float32, device=dev)
-        out = N.out_tensor((9, H, W), torch.float32, dev)
         N.check(N.lib.svgir_env_backdrop(W, H, intr, rot, tr, env.data_ptr(), env.shape[0], env.shape[1], int(softplus), float(scale),
                                          work.data_ptr(), im.data_ptr(), op.data_ptr(), vf.data_ptr(), out.data_ptr(),
                                          N.stream_ptr(dev)), "env_backdrop")
+    return dict(env_only=out[0:3], render_env=out[3:6], pbr_env=out[6:9])
+
+
+def sg_environment_backdrop(light, intrinsics, c2w, image, opacity, vfeature):
+    """environment_backdrop under a DirectLightSG-like light (`.lgtSGs` [M,7]; svgir_env_backdrop_sg): the unclamped mixture of lobes
+    evaluated along the same pixel directions (no lookup transform: DirectLightSG.direct_light ignores it), the same three images, the
+    same argument checks and return dict."""
+    who = "sg_environment_backdrop"
+    if not shading._is_sg(light):
+        raise TypeError(f"{who}: the light must expose .lgtSGs (DirectLightSG); a texture light goes through environment_backdrop")
+    dev, intr, rot = _backdrop_camera(who, intrinsics, c2w, image, opacity, vfeature)
+    if light.lgtSGs.device.type != "cuda":
+        raise RuntimeError(f"{who}: the light must live on the GPU (libsvgir_raster.so has no CPU path)")
+    with torch.no_grad(), torch.cuda.device(dev):
+        lt, keep = shading._sg_light(shading.SGLobes(light.lgtSGs).lobes, dev)
+        im, op, vf, H, W, out = _backdrop_planes(who, dev, image, opacity, vfeature)
+        N.check(N.lib.svgir_env_backdrop_sg(W, H, intr, rot, lt, im.data_ptr(), op.data_ptr(), vf.data_ptr(), out.data_ptr(),
+                                            N.stream_ptr(dev)), "env_backdrop_sg")
     return dict(env_only=out[0:3], render_env=out[3:6], pbr_env=out[6:9])
 
 
@@ -251,7 +278,8 @@ def camera_of(sc):
 
 def _with_backdrop(res, rendered, light, is_training, camera):
     if camera is not None and not is_training:
-        res.update(environment_backdrop(light, camera["intrinsics"], camera["c2w"], rendered[1], rendered[3], rendered[6]))
+        backdrop = sg_environment_backdrop if shading._is_sg(light) else environment_backdrop
+        res.update(backdrop(light, camera["intrinsics"], camera["c2w"], rendered[1], rendered[3], rendered[6]))
     return res
 
 
