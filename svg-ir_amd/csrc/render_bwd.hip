@@ -342,7 +342,8 @@ render_bwd_kernel(const RenderBwdArgs a) {
                 const float Gs = exp_nonpos(pw);
                 const float al = fminf(0.99f, B.y * Gs);
                 const bool pre = slot < last_contributor && pw <= 0.0f && al >= (1.0f / 255.0f);
-                const float ioma = __builtin_amdgcn_rcpf(1.f - al);
+                const float oma = 1.f - al;
+                const float ioma = __builtin_amdgcn_rcpf(oma);
                 float cw0 = 0.f, cw1 = 0.f, cw2 = 0.f, cw3 = 0.f;
                 if (SVGSS && sp) {
                     const float4 Jv = q[2];  // J0..J3
@@ -371,7 +372,11 @@ render_bwd_kernel(const RenderBwdArgs a) {
                 }
                 // (2) the sequential part: T <- T / (1 - alpha) and the scalar replay recurrence (backward.cu:700-850)
                 const float inv_Told = __builtin_amdgcn_rcpf(T);
-                const float Tn = T * ioma;
+                // T / (1 - alpha) to half an ulp: the product with the rounded reciprocal plus one residual step.  The bare product carries the
+                // reciprocal's rounding into every step of the segment -- the same error each time where a stack repeats one alpha (64 / 63 rounds
+                // up by 0.49 ulp: 68 eps32 over 64 candidates, tests/composite_cases.py deep700); the reference divides
+                const float Tq = T * ioma;
+                const float Tn = __builtin_fmaf(__builtin_fmaf(-oma, Tq, T), ioma, Tq);
                 const float An = last_alpha * s_last + (1.f - last_alpha) * A_acc;
                 float dL_dalpha = kdn * inv_Told + (sd - An);
                 dL_dalpha *= Tn;

@@ -316,7 +316,8 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
             const float Gs = exp_nonpos(pw);
             const float al = fminf(0.99f, cur.op * Gs);
             const bool pre = cur.slot < last_contributor && pw <= 0.0f && al >= (1.0f / 255.0f);
-            const float ioma = __builtin_amdgcn_rcpf(1.f - al);
+            const float oma = 1.f - al;
+            const float ioma = __builtin_amdgcn_rcpf(oma);
             // (a b + c d has two fused forms; which one is written out, so that the sums do not depend on where the compiler finds the
             // operands -- the forms are those of the scalar-operand build this path was measured against, profiles/bwd_lds_records_ab.txt)
             float sd = __builtin_fmaf(cur.cb, gC[2], __builtin_fmaf(cur.cr, gC[0], cur.cg * gC[1]));
@@ -327,7 +328,9 @@ render_bwd_plain_kernel(const RenderBwdArgs a) {
             for (int ch = 0; ch < S; ch++) sd += cur.f[ch] * gFe[ch];
             // the sequential part: T <- T / (1 - alpha) and the scalar replay recurrence (backward.cu:700-850)
             const float inv_Told = __builtin_amdgcn_rcpf(T);
-            const float Tn = T * ioma;
+            // T / (1 - alpha) to half an ulp: product with the rounded reciprocal plus one residual step (render_bwd.hip)
+            const float Tq = T * ioma;
+            const float Tn = __builtin_fmaf(__builtin_fmaf(-oma, Tq, T), ioma, Tq);
             const float An = last_alpha * s_last + (1.f - last_alpha) * A_acc;
             float dL_dalpha = kdn * inv_Told + (sd - An);
             dL_dalpha *= Tn;

@@ -183,11 +183,15 @@ __global__ void __launch_bounds__(64) render_bwd_generic_kernel(const RenderBwdA
                 const float4 c4 = reinterpret_cast<const float4*>(a.vfeatures)[(size_t)e.x * VC + ch];
                 sdot += (c4.x * g.cw[0] + c4.y * g.cw[1] + c4.z * g.cw[2] + c4.w * g.cw[3]) * gbuf[(S + ch) * 64 + lane];
             }
-            const float ioma = __builtin_amdgcn_rcpf(1.f - g.alpha);
+            // T <- T / (1 - alpha) is a DIVISION here, as in the reference: this wave replays the whole list from final_T, and a product with
+            // the rounded reciprocal carries that reciprocal's rounding error into every step -- the same one each time where a stack repeats
+            // one alpha, so that T_k is off by (list length) x eps instead of its square root (tests/composite_cases.py `deep`: 91 eps32
+            // over 183 candidates of alpha 2^-5).  The segmented kernels restart from a stored T every 64 candidates.
+            const float oma = 1.f - g.alpha;
             const float inv_Told = __builtin_amdgcn_rcpf(T);
-            const float Tn = T * ioma;
+            const float Tn = T / oma;
             const float An = last_alpha * s_last + (1.f - last_alpha) * A_acc;
-            float dL_dalpha = (kdn * inv_Told + (sdot - An)) * Tn + gO_kbg * (T_final * ioma);
+            float dL_dalpha = (kdn * inv_Told + (sdot - An)) * Tn + gO_kbg * (T_final / oma);
             T = pass ? Tn : T; A_acc = pass ? An : A_acc; s_last = pass ? sdot : s_last; last_alpha = pass ? g.alpha : last_alpha;
             dL_dalpha = pass ? dL_dalpha : 0.f;
             const float vw = pass ? g.alpha * Tn : 0.f;
