@@ -493,6 +493,14 @@ int svgir_last_timings(const char** names, float* avg_ms, int* counts, int cap) 
     return n;
 }
 
+// DepthRows (depth_sort_plan.hpp) inside the geometry blob: no array of their own.  Under the bucket plan nothing ping-pongs: slot 0 of
+// the keys and of the ids, and shade_list -- dead until the sort is done -- hold the grouped rows; the row tables take the place of the
+// LSD passes' histograms (one row per sort block there too) and group totals.
+static_assert(DEPTH_ROW == 1024, "a row of the bucket plan = a sort block: sort_blocks() sizes the row tables");
+inline DepthRows geom_depth_rows(const GeomLayout& g, int P) {
+    return DepthRows{g.key[0], g.idx[0], g.shade_list, g.radix_tbl, g.radix_wtbl, radix_gtot(g.radix_tbl, P)};
+}
+
 // One svgir_forward, in two halves: begin() validates, allocates and launches EVERYTHING -- the count-dependent stages speculatively, for
 // capacities guessed from the workload's recent views -- without waiting for the GPU; finish() waits for the instance count (it only
 // confirms the guess, or re-runs the dependent stages) and returns it.  svgir_forward is begin() + finish(); svgir_forward_batch begins all
@@ -655,17 +663,24 @@ struct ForwardCall {
         pa.needed = prepass ? G.needed : nullptr;
         pa.span = G.counters + 3;
         if (p->shade) pa.tabs = shade_tables(&p->shade->sp, nullptr, 0);   // (the preprocess launch carries the shading kernels' tables)
-        pa.zero_words = radix_gtot(G.radix_tbl, P); pa.n_zero_words = (int)radix_gtot_words(P);
         ckey = workload_key(p);
         static const bool key_spec_env = getenv("SVGIR_NO_KEY_SPEC") == nullptr;
         spec_top = (key_spec && key_spec_env) ? g_history.guess_top(ckey) : -1;
         pa.spec_top = spec_top; pa.key_top = G.key_top;
+        // which plan sorts the depth keys (depth_sort_plan.hpp): under the bucket plan the preprocess leaves its rows grouped for the one
+        // kernel of that plan, and there are no group totals to clear
+        static const bool forced_lsd = depth_sort_forced_lsd(getenv("SVGIR_DEPTH_SORT"));
+        static const int bucket_cap = depth_bucket_cap(getenv("SVGIR_DEPTH_BUCKET_CAP"));
+        const bool buckets = depth_sort_plan(P, spec_top, forced_lsd) == DepthSortPlan::kBuckets;
+        const DepthRows rows = geom_depth_rows(G, P);
+        pa.zero_words = radix_gtot(G.radix_tbl, P); pa.n_zero_words = (int)radix_gtot_words(P);
         pa.prefilter_violation = nullptr;
         if (p->prefiltered) {   // the violation flag sits next to the instance counter and is read back with it
             HIP_OK(hipMemsetAsync(G.counters, 0, 16, s));
             pa.prefilter_violation = G.counters + 1;
         }
-        launch_preprocess(pa, svgss, s);
+        if (buckets) launch_preprocess_rows(pa, rows, svgss, s);
+        else launch_preprocess(pa, svgss, s);
         if (int rc = check("preprocess")) return rc;
         stage_mark(tm, "preprocess");
 
@@ -674,11 +689,9 @@ struct ForwardCall {
         depth_order = G.idx[(depth_bits / 8) & 1];
         // (its last pass sums the tile counts next to the keys: G.offsets, the instance count R and what the host reads with it -- no scan stage)
         const RadixWeights rw{G.tiles, G.radix_wtbl, G.offsets, G.counters, G.key_top, (P + 63) / 64, pa.prefilter_violation, R_pin.at, R_pin.tag};
-        // (under a speculated byte and up to DEPTH_BUCKET_MAX_P keys: one global pass over the visible keys + in-LDS bucket sorts, which
-        // end in the same slot with the same visible order and offsets -- depth_sort_plan.hpp)
-        static const bool forced_lsd = depth_sort_forced_lsd(getenv("SVGIR_DEPTH_SORT"));
-        static const int bucket_cap = depth_bucket_cap(getenv("SVGIR_DEPTH_BUCKET_CAP"));
-        if (depth_sort_plan(P, spec_top, forced_lsd) == DepthSortPlan::kBuckets) launch_depth_bucket_sort(G.key, G.idx, P, G.radix_tbl, bucket_cap, s, rw);
+        // (under a speculated byte and up to DEPTH_BUCKET_MAX_P keys: in-LDS bucket sorts over the rows the preprocess grouped, which end
+        // in the same slot with the same visible order and offsets -- depth_sort_plan.hpp)
+        if (buckets) launch_depth_bucket_sort(rows, G.key[1], G.idx[1], P, bucket_cap, s, rw);
         else launch_radix_sort(G.key, G.idx, P, nullptr, depth_bits, 8, G.radix_tbl, s, &rw);
         if (int rc = check("depth sort")) return rc;
         stage_mark(tm, "sort_depth");

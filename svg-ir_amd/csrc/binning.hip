@@ -41,9 +41,7 @@ struct WeightArgs {
     RadixWeights w;
 };
 
-// F (with W; the bucket plan's one global pass, launch_depth_bucket_sort): a key that weighs nothing is not counted, and the per-block
-// weight rows are not written (the pass's scatter needs the weights' group totals only).
-template <int ITEMS, bool W = false, bool F = false>
+template <int ITEMS, bool W = false>
 __global__ void __launch_bounds__(BLOCK) radix_hist_kernel(const uint32_t* __restrict__ keys, int n_cap,
                                                            const uint32_t* __restrict__ n_dev, int bit_lo,
                                                            uint32_t mask, uint32_t* __restrict__ table,
@@ -71,8 +69,7 @@ __global__ void __launch_bounds__(BLOCK) radix_hist_kernel(const uint32_t* __res
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const int e = base + i * BLOCK + threadIdx.x;
-        if constexpr (F) { if (e < n && w[i] != 0u) atomicAdd(&hist[(k[i] >> bit_lo) & mask], 1u); }
-        else if (e < n) atomicAdd(&hist[(k[i] >> bit_lo) & mask], 1u);
+        if (e < n) atomicAdd(&hist[(k[i] >> bit_lo) & mask], 1u);
         if constexpr (W) if (e < n && w[i] != 0u) atomicAdd(&whist[(k[i] >> bit_lo) & mask], w[i]);
     }
     __syncthreads();
@@ -81,7 +78,7 @@ __global__ void __launch_bounds__(BLOCK) radix_hist_kernel(const uint32_t* __res
     if (c) atomicAdd(&gtot[(size_t)(blockIdx.x / GS) * 256 + threadIdx.x], c);
     if constexpr (W) {   // the same row and the same group slot once more, for the weights
         const uint32_t wc = whist[threadIdx.x];
-        if constexpr (!F) wa.w.wtable[(size_t)blockIdx.x * 256 + threadIdx.x] = wc;
+        wa.w.wtable[(size_t)blockIdx.x * 256 + threadIdx.x] = wc;
         if (wc) atomicAdd(&wa.wgtot[(size_t)(blockIdx.x / GS) * 256 + threadIdx.x], wc);
     }
 }
@@ -294,113 +291,10 @@ __global__ void __launch_bounds__(BLOCK) radix_scatter_kernel(const uint32_t* __
 
 // ---- bucket plan of the geometry depth sort (depth_sort_plan.hpp) -------------------------------------------------
 // Under a speculated common top byte 24 key bits are left, and the culled Gaussians -- more than half of a closed surface's surfels -- emit
-// nothing.  ONE global pass (filtered weighted histogram above + the scatter below) puts the visible keys, stably, into the 256 buckets of
-// bits 16..23; each bucket is a contiguous range that one workgroup finishes on bits 0..15 inside LDS, and the same workgroup scans the
-// weights in final order: the instance offsets.  Three launches instead of three passes of two.
-
-// The scatter of that pass: radix_scatter_kernel's cursors and ranking over the keys that weigh something; a key's weight travels with it
-// (wout: the offsets array, which the bucket kernel reads and then overwrites).  Block 0 publishes what the weighted LSD pass publishes --
-// it needs the weights' group totals only -- and counters[3] = the number of visible keys.
-template <int ITEMS>
-__global__ void __launch_bounds__(BLOCK) depth_bucket_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
-                                                                     uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
-                                                                     uint32_t* __restrict__ wout, int n, int bit_lo,
-                                                                     const uint32_t* __restrict__ table, const uint32_t* __restrict__ gtot,
-                                                                     const uint32_t* __restrict__ wgtot, int ngroups, RadixWeights w) {
-    __shared__ uint32_t wcnt[4][256];   // per-wave digit counters, later the waves' output cursors
-    __shared__ uint32_t wtot[4], wtot2[4], wtot3[4], ksum[4], wcul[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int base = blockIdx.x * (BLOCK * ITEMS) + wave * (64 * ITEMS);
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t ks[ITEMS], vs[ITEMS], ws[ITEMS], rk[ITEMS];
-#pragma unroll
-    for (int c = 0; c < ITEMS; c++) {
-        const int e = base + c * 64 + lane;
-        ks[c] = e < n ? kin[e] : 0u;
-        vs[c] = e < n ? vin[e] : 0u;
-    }
-#pragma unroll
-    for (int c = 0; c < ITEMS; c++) ws[c] = base + c * 64 + lane < n ? w.tiles[2 * (size_t)vs[c]] : 0u;
-    if (blockIdx.x == 0) {   // the publishing block folds the preprocess waves' depth-key summaries {AND << 8 | OR}
-        uint32_t kv = 0xff00u;
-#pragma unroll 8
-        for (int j = t; j < w.n_key_top; j += BLOCK) kv = key_top_fold(kv, w.key_top[j]);
-        kv = wave_reduce(kv, key_top_fold);
-        if (lane == 0) ksum[wave] = kv;   // (read behind the barrier of the cursor scan)
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) wcnt[q][t] = 0;
-    uint32_t cursor, nvis, cull_base;   // cull_base: where this block's first key without weight goes
-    {
-        const int g = blockIdx.x / GS;
-        uint32_t tot = 0, pre = 0, wsum = 0;
-#pragma unroll 8
-        for (int gg = 0; gg < ngroups; gg++) {
-            const uint32_t v = gtot[(size_t)gg * 256 + t];
-            tot += v;
-            pre += gg < g ? v : 0u;
-            if (blockIdx.x == 0) wsum += wgtot[(size_t)gg * 256 + t];
-        }
-#pragma unroll 8
-        for (int b = g * GS; b < (int)blockIdx.x; b++) pre += table[(size_t)b * 256 + t];
-        cursor = block_excl_scan<4>(tot, wtot, &nvis) + pre;   // (its barrier also: the wave counters are zero)
-        cull_base = nvis + blockIdx.x * (BLOCK * ITEMS) - block_sum<4>(pre, wtot3);   // (every block in front of this one is full)
-        if (blockIdx.x == 0) {
-            uint32_t R;
-            (void)block_excl_scan<4>(wsum, wtot2, &R);
-            if (t == 0) {
-                const uint32_t summary = key_top_fold(key_top_fold(ksum[0], ksum[1]), key_top_fold(ksum[2], ksum[3]));
-                w.counters[0] = R;
-                w.counters[2] = summary;
-                w.counters[3] = nvis;
-                if (w.host_out) {   // (tag format: radix_scatter_kernel)
-                    const uint32_t viol = w.violation ? (w.violation[0] != 0u ? 1u : 0u) : 0u;
-                    __hip_atomic_store(w.host_out, ((unsigned long long)w.host_tag << 32) | R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store(w.host_out + 1, ((unsigned long long)w.host_tag << 32) | (viol << 16) | summary, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-        }
-    }
-    uint32_t ncul = 0;
-#pragma unroll
-    for (int c = 0; c < ITEMS; c++) {
-        const bool valid = base + c * 64 + lane < n && ws[c] != 0u;
-        const uint32_t d = (ks[c] >> bit_lo) & 255u;
-        const unsigned long long same = wave_match(d, 8, valid);
-        const uint32_t in_round = (uint32_t)__popcll(same & lt_mask);
-        const uint32_t prior = wcnt[wave][d];   // (the DS operations of a wave execute in order: every lane reads before the leader writes)
-        rk[c] = prior + in_round;
-        if (valid && in_round == 0) wcnt[wave][d] = prior + (uint32_t)__popcll(same);
-        // a key without weight: its rank among those of its wave, in key order
-        const unsigned long long culled = __ballot(base + c * 64 + lane < n && ws[c] == 0u);
-        if (!valid) rk[c] = ncul + (uint32_t)__popcll(culled & lt_mask);
-        ncul += (uint32_t)__popcll(culled);
-    }
-    if (lane == 0) wcul[wave] = ncul;
-    __syncthreads();
-    {   // digit t: the waves' cursors = block cursor + counts of the waves in front
-        const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t];
-        __syncthreads();
-        wcnt[0][t] = cursor; wcnt[1][t] = cursor + c0; wcnt[2][t] = cursor + c0 + c1; wcnt[3][t] = cursor + c0 + c1 + c2;
-    }
-    __syncthreads();
-    for (int q = 0; q < wave; q++) cull_base += wcul[q];
-#pragma unroll
-    for (int c = 0; c < ITEMS; c++) {
-        if (base + c * 64 + lane >= n) continue;
-        if (ws[c] != 0u) {
-            const uint32_t pos = wcnt[wave][(ks[c] >> bit_lo) & 255u] + rk[c];
-            kout[pos] = ks[c];
-            vout[pos] = vs[c];
-            wout[pos] = ws[c];
-        } else {
-            // (the values without weight follow the visible ones, in their input order: val[1] stays a permutation of the input values, and
-            // the fused shading walks its back to clear the rows of the surfels this view does not shade -- shade.hip zero_rest_rows)
-            vout[cull_base + rk[c]] = vs[c];
-        }
-    }
-}
+// nothing.  preprocess_kernel leaves every row of DEPTH_ROW consecutive Gaussians stably grouped by bits 16..23 of the visible keys
+// (DepthRows).  Rows taken in index order are a stable pass on that digit: bucket d is, row by row, the rows' groups d.  One workgroup per
+// bucket gathers it, finishes it on bits 0..15 inside LDS and scans the weights in final order: the instance offsets.  One launch instead
+// of three passes of two.
 
 constexpr int DB_THREADS = 1024, DB_WAVES = DB_THREADS / 64, DB_ROUNDS = DEPTH_BUCKET_CAP / DB_THREADS;
 
@@ -457,36 +351,98 @@ __device__ __forceinline__ void bucket_pass(int m, int shift, Get get, Put put, 
     __syncthreads();
 }
 
-// Workgroup d finishes bucket d: the keys whose bits 16..23 are d, n of them from position `start` of slot 1 (key1 / val1 / their weights in
-// `offsets`); start, n and the weight base are exclusive sums over the digits of the pass's group totals.
-//   n <= cap: keys {low 16 bits | local index}, ids and weights into LDS, two in-LDS passes, the weights scanned in final order, out.
-//   n > cap, low 16 bits all equal: the order is already there; the weights (gathered through the ids) are scanned chunk by chunk.
-//   n > cap otherwise: the two passes run chunk by chunk through global memory -- the bucket's own range of slot 0 and back -- then that scan.
-// Nothing outside [start, start + n) is touched: the buckets are disjoint.
-__global__ void __launch_bounds__(DB_THREADS) depth_bucket_sort_kernel(uint32_t* key0, uint32_t* val0, uint32_t* key1, uint32_t* val1, uint32_t* offsets,
-                                                                       const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ gtot,
-                                                                       const uint32_t* __restrict__ wgtot, int ngroups, int cap) {
+// Workgroup d finishes bucket d: the visible keys whose bits 16..23 are d.  Column d of the row tables -- one row per thread -- gives, summed
+// over the rows, the bucket's position `start` in the order, its size n and its weight base, and scanned over the rows where item j of the
+// bucket lies: in the last row b with prefix[b] <= j, at the row's base + the row's scan[d] + (j - prefix[b]).
+//   n <= cap: keys {low 16 bits | local index}, ids and weights gathered into LDS, two in-LDS passes, the weights scanned in final order, out.
+//   n > cap, low 16 bits all equal: the gathered order is the order; the weights (gathered through the ids) are scanned chunk by chunk.
+//   n > cap otherwise: the two passes run chunk by chunk through global memory -- out of the rows into the bucket's own range of two scratch
+//     arrays, and from there into the order -- then that scan.
+// Of the order, nothing outside [start, start + n) is touched: the buckets are disjoint.  Behind the V visible ids follow the rows' other
+// ids, row b's run by workgroup b mod 256; workgroup 0 publishes R, V, the key summary and the host words (RadixWeights).
+__device__ __forceinline__ int bucket_row_of(const uint32_t* prefix, int nrows, uint32_t j) {   // the last row b with prefix[b] <= j
+    int lo = 0, hi = nrows;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (prefix[mid] <= j) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(DB_THREADS) depth_bucket_sort_kernel(const DepthRows rows, int nrows, int P, uint32_t* key1, uint32_t* val1,
+                                                                       uint32_t* offsets, int cap, const RadixWeights w) {
     __shared__ uint32_t sA[DEPTH_BUCKET_CAP], sB[DEPTH_BUCKET_CAP], sI[DEPTH_BUCKET_CAP], sW[DEPTH_BUCKET_CAP];
     __shared__ uint32_t wcnt[DB_WAVES][256];
-    __shared__ uint32_t cur[256], wsum[DB_WAVES], wsum2[DB_WAVES], hdr[3], red[2][DB_WAVES];
+    __shared__ uint32_t cur[256], wsum[DB_WAVES], wsum2[DB_WAVES], tot3[3][DB_WAVES], ksum[DB_WAVES], red[2][DB_WAVES];
+    // the rows' prefixes live in sB, which is free until the first pass stores into it
+    static_assert(3 * (DEPTH_ROWS_MAX + 1) <= DEPTH_BUCKET_CAP && DEPTH_ROWS_MAX <= DB_THREADS, "row prefixes: one row per thread, inside sB");
+    static_assert(sizeof(uint32_t) * (4 * DEPTH_BUCKET_CAP + DB_WAVES * 256 + 256 + 8 * DB_WAVES) <= 160 * 1024, "LDS of one CU");
+    uint32_t* const prefix = sB;                              // [nrows + 1] items of this bucket in the rows in front
+    uint32_t* const rowsrc = sB + (DEPTH_ROWS_MAX + 1);       // [nrows] where item j of the row's share lies, minus j
+    uint32_t* const vprefix = sB + 2 * (DEPTH_ROWS_MAX + 1);  // [nrows + 1] visible Gaussians in the rows in front
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t cnt = 0, wt = 0;
-    if (t < 256)
-        for (int g = 0; g < ngroups; g++) { cnt += gtot[(size_t)g * 256 + t]; wt += wgtot[(size_t)g * 256 + t]; }
-    const uint32_t cpre = block_excl_scan<DB_WAVES>(cnt, wsum);
-    const uint32_t wpre = block_excl_scan<DB_WAVES>(wt, wsum2);
-    if (t == (int)blockIdx.x) { hdr[0] = cpre; hdr[1] = cnt; hdr[2] = wpre; }
+    const uint32_t d = blockIdx.x;
+    uint32_t c0 = 0, c1 = 0, w0 = 0;
+    uint2 rt = make_uint2(0u, 0u);
+    if (t < nrows) {
+        rt = reinterpret_cast<const uint2*>(rows.tot)[t];
+        c0 = rows.cscan[(size_t)t * 256 + d];
+        c1 = d < 255u ? rows.cscan[(size_t)t * 256 + d + 1] : rt.x;
+        w0 = rows.wscan[(size_t)t * 256 + d];
+    }
+    uint32_t kv = 0xff00u;
+    if (d == 0u) {   // the publishing workgroup folds the preprocess waves' depth-key summaries {AND << 8 | OR}
+#pragma unroll 4
+        for (int j = t; j < w.n_key_top; j += DB_THREADS) kv = key_top_fold(kv, w.key_top[j]);
+    }
+    uint32_t n_u, V;
+    const uint32_t pre = block_excl_scan<DB_WAVES>(c1 - c0, wsum, &n_u);
+    const uint32_t vpre = block_excl_scan<DB_WAVES>(rt.x, wsum2, &V);
+    {
+        const uint32_t s0 = wave_reduce_add(c0), s1 = wave_reduce_add(w0), s2 = wave_reduce_add(rt.y);
+        kv = wave_reduce(kv, key_top_fold);
+        if (lane == 0) { tot3[0][wave] = s0; tot3[1][wave] = s1; tot3[2][wave] = s2; ksum[wave] = kv; }
+    }
+    if (t < nrows) { prefix[t] = pre; rowsrc[t] = (uint32_t)t * DEPTH_ROW + c0 - pre; vprefix[t] = vpre; }
+    if (t == nrows) { prefix[t] = n_u; vprefix[t] = V; }
+    if (t == 0 && nrows == DB_THREADS) { prefix[nrows] = n_u; vprefix[nrows] = V; }
     __syncthreads();
-    const uint32_t start = hdr[0], wbase = hdr[2];
-    const int n = (int)hdr[1];
+    uint32_t start = 0, wbase = 0, R = 0;
+#pragma unroll
+    for (int q = 0; q < DB_WAVES; q++) { start += tot3[0][q]; wbase += tot3[1][q]; R += tot3[2][q]; }
+    const int n = (int)n_u;
+    if (d == 0u && t == 0) {
+        uint32_t summary = 0xff00u;
+#pragma unroll
+        for (int q = 0; q < DB_WAVES; q++) summary = key_top_fold(summary, ksum[q]);
+        w.counters[0] = R;
+        w.counters[2] = summary;
+        w.counters[3] = V;
+        if (w.host_out) {   // (tag format: radix_scatter_kernel)
+            const uint32_t viol = w.violation ? (w.violation[0] != 0u ? 1u : 0u) : 0u;
+            __hip_atomic_store(w.host_out, ((unsigned long long)w.host_tag << 32) | R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(w.host_out + 1, ((unsigned long long)w.host_tag << 32) | (viol << 16) | summary, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    // (the ids without weight follow the visible ones, by index: val[1] stays a permutation of the ids, and the fused shading walks its
+    // back to clear the rows of the surfels this view does not shade -- shade.hip zero_rest_rows)
+    for (int b = (int)d; b < nrows; b += 256) {
+        const uint32_t vb = vprefix[b], nv = vprefix[b + 1] - vb;
+        const int len = min(DEPTH_ROW, P - b * DEPTH_ROW) - (int)nv;
+        const uint32_t* src = rows.id + (size_t)b * DEPTH_ROW + nv;
+        uint32_t* dst = val1 + V + ((uint32_t)b * DEPTH_ROW - vb);   // (every row in front of b is full)
+        for (int i = t; i < len; i += DB_THREADS) dst[i] = src[i];
+    }
     if (n == 0) return;
     if (n <= cap) {
         for (int i = t; i < n; i += DB_THREADS) {
-            sA[i] = (key1[start + i] << 16) | (uint32_t)i;
-            sI[i] = val1[start + i];
-            sW[i] = offsets[start + i];
+            const uint32_t src = rowsrc[bucket_row_of(prefix, nrows, (uint32_t)i)] + (uint32_t)i;
+            sA[i] = (rows.key[src] << 16) | (uint32_t)i;
+            sI[i] = rows.id[src];
+            sW[i] = rows.w[src];
         }
-        // (the barrier behind the passes' clearing of the counters also orders these stores)
+        // (the barrier behind the passes' clearing of the counters also orders these stores, and the reads of the prefixes in sB)
         bucket_pass<false>(n, 16, [&](int i) { return make_uint2(sA[i], 0u); }, [&](uint32_t pos, uint2 it) { sB[pos] = it.x; }, wcnt, cur, wsum);
         bucket_pass<false>(n, 24, [&](int i) { return make_uint2(sB[i], 0u); }, [&](uint32_t pos, uint2 it) { sA[pos] = it.x; }, wcnt, cur, wsum);
         // the weights in final order, DB_ROUNDS consecutive ones per thread, and their exclusive scan (into sB)
@@ -511,9 +467,15 @@ __global__ void __launch_bounds__(DB_THREADS) depth_bucket_sort_kernel(uint32_t*
         }
         return;
     }
+    // oversize.  (The rows' arrays are read-only here -- other workgroups gather from them -- so the passes' intermediate lives in the
+    // bucket's own range of two arrays that hold nothing before this workgroup's last stores: the offsets and the keys of slot 1.)
+    const auto item = [&](int i) {
+        const uint32_t src = rowsrc[bucket_row_of(prefix, nrows, (uint32_t)i)] + (uint32_t)i;
+        return make_uint2(rows.key[src], rows.id[src]);
+    };
     {   // do the low 16 bits differ at all?
         uint32_t a = 0xffffu, o = 0u;
-        for (int i = t; i < n; i += DB_THREADS) { const uint32_t k = key1[start + i] & 0xffffu; a &= k; o |= k; }
+        for (int i = t; i < n; i += DB_THREADS) { const uint32_t k = item(i).x & 0xffffu; a &= k; o |= k; }
         a = wave_reduce(a, [](uint32_t x, uint32_t y) { return x & y; });
         o = wave_reduce(o, [](uint32_t x, uint32_t y) { return x | y; });
         if (lane == 0) { red[0][wave] = a; red[1][wave] = o; }
@@ -521,24 +483,33 @@ __global__ void __launch_bounds__(DB_THREADS) depth_bucket_sort_kernel(uint32_t*
         a = 0xffffu; o = 0u;
 #pragma unroll
         for (int q = 0; q < DB_WAVES; q++) { a &= red[0][q]; o |= red[1][q]; }
-        if (a != o) {
-            for (int pass = 0; pass < 2; pass++) {
-                const uint32_t* sk = (pass ? key0 : key1) + start; const uint32_t* sv = (pass ? val0 : val1) + start;
-                uint32_t* dk = (pass ? key1 : key0) + start; uint32_t* dv = (pass ? val1 : val0) + start;
+        if (a == o) {   // the gathered order is the order
+            for (int i = t; i < n; i += DB_THREADS) val1[start + i] = item(i).y;
+        } else {
+            uint32_t* const tk = offsets + start;
+            uint32_t* const tv = key1 + start;
+            for (int pass = 0; pass < 2; pass++) {   // rows -> {tk, tv} on bits 0..7, {tk, tv} -> the ids of slot 1 on bits 8..15
                 const int shift = 8 * pass;
                 if (t < 256) cur[t] = 0u;
                 __syncthreads();
-                for (int i = t; i < n; i += DB_THREADS) atomicAdd(&cur[(sk[i] >> shift) & 255u], 1u);
+                for (int i = t; i < n; i += DB_THREADS) atomicAdd(&cur[((pass ? tk[i] : item(i).x) >> shift) & 255u], 1u);
                 __syncthreads();
                 const uint32_t ex = block_excl_scan<DB_WAVES>(t < 256 ? cur[t] : 0u, wsum);
                 if (t < 256) cur[t] = ex;   // (read behind the first barrier of the pass below)
-                for (int c0 = 0; c0 < n; c0 += cap)
-                    bucket_pass<true>(min(cap, n - c0), shift, [&](int i) { return make_uint2(sk[c0 + i], sv[c0 + i]); },
-                                      [&](uint32_t pos, uint2 it) { dk[pos] = it.x; dv[pos] = it.y; }, wcnt, cur, wsum);
+                for (int c0 = 0; c0 < n; c0 += cap) {
+                    if (pass == 0)
+                        bucket_pass<true>(min(cap, n - c0), shift, [&](int i) { return item(c0 + i); },
+                                          [&](uint32_t pos, uint2 it) { tk[pos] = it.x; tv[pos] = it.y; }, wcnt, cur, wsum);
+                    else
+                        bucket_pass<true>(min(cap, n - c0), shift, [&](int i) { return make_uint2(tk[c0 + i], tv[c0 + i]); },
+                                          [&](uint32_t pos, uint2 it) { val1[start + pos] = it.y; }, wcnt, cur, wsum);
+                }
                 __threadfence_block();   // (the next pass, and the scan below, read what other waves of this workgroup stored)
                 __syncthreads();
             }
         }
+        __threadfence_block();
+        __syncthreads();
     }
     uint32_t carry = wbase;
     for (int c0 = 0; c0 < n; c0 += DB_THREADS * DB_ROUNDS) {
@@ -546,7 +517,7 @@ __global__ void __launch_bounds__(DB_THREADS) depth_bucket_sort_kernel(uint32_t*
 #pragma unroll
         for (int j = 0; j < DB_ROUNDS; j++) {
             const int i = c0 + t * DB_ROUNDS + j;
-            wv[j] = i < n ? tiles[2 * (size_t)val1[start + i]] : 0u;
+            wv[j] = i < n ? w.tiles[2 * (size_t)val1[start + i]] : 0u;
             sum += wv[j];
         }
         uint32_t all;
@@ -932,19 +903,11 @@ void launch_radix_sort(uint32_t* const key[2], uint32_t* const val[2], int n, co
     else radix_sort_impl<16>(key, val, n, n_dev, total_bits, bits_per_pass, table, gtot, s, weights);
 }
 
-// depth_sort_plan.hpp.  Group totals: the counts in slot 0, the weights in the weighted pass's slot.
-void launch_depth_bucket_sort(uint32_t* const key[2], uint32_t* const val[2], int n, uint32_t* table, int cap, hipStream_t s, const RadixWeights& w) {
+// depth_sort_plan.hpp
+void launch_depth_bucket_sort(const DepthRows& rows, uint32_t* key1, uint32_t* val1, int n, int cap, hipStream_t s, const RadixWeights& w) {
     if (n <= 0) return;
-    constexpr int ITEMS = 4;
     assert(n <= DEPTH_BUCKET_MAX_P && cap >= DEPTH_BUCKET_CAP_MIN && cap <= DEPTH_BUCKET_CAP);
-    const int nb = (n + BLOCK * ITEMS - 1) / (BLOCK * ITEMS), ng = (nb + GS - 1) / GS;
-    uint32_t* gtot = radix_gtot(table, n);
-    uint32_t* wgtot = gtot + (size_t)RADIX_WGTOT_SLOT * ng * 256;
-    const WeightArgs wa{val[0], wgtot, w};
-    hipLaunchKernelGGL((radix_hist_kernel<ITEMS, true, true>), dim3(nb), dim3(BLOCK), 0, s, key[0], n, (const uint32_t*)nullptr, 16, 255u, table, gtot, wa);
-    hipLaunchKernelGGL((depth_bucket_scatter_kernel<ITEMS>), dim3(nb), dim3(BLOCK), 0, s, key[0], val[0], key[1], val[1], w.offsets, n, 16, table, gtot,
-                       wgtot, ng, w);
-    hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(256), dim3(DB_THREADS), 0, s, key[0], val[0], key[1], val[1], w.offsets, w.tiles, gtot, wgtot, ng, cap);
+    hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(256), dim3(DB_THREADS), 0, s, rows, depth_rows(n), n, key1, val1, w.offsets, cap, w);
 }
 
 void launch_emit(int P, const uint32_t* order, const uint32_t* tiles, const uint32_t* offsets, float* rec,

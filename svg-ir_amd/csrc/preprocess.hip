@@ -8,11 +8,13 @@
 // One lane per Gaussian.  Everything the composite kernels gather later is packed into ONE 96-byte record per
 // Gaussian (six aligned float4 stores) instead of the reference's eleven separate arrays, so a (tile, splat)
 // instance costs one contiguous gather.  The depth-sort key and the identity permutation for the depth sort
-// are written here too.  Bandwidth-trivial (<= 236 B in, ~140 B out per Gaussian).
+// are written here too -- or, under the depth sort's bucket plan, the workgroup's Gaussians grouped by a key digit, which is that
+// plan's one global pass (depth_sort_plan.hpp DepthRows).  Bandwidth-trivial (<= 236 B in, ~140 B out per Gaussian).
 //
 // Floating-point contraction is OFF in this file: culling decisions, radii and tile rectangles are integer
 // outputs (num_rendered, radii, point_list) and are kept bit-identical to the un-fused arithmetic of the oracle.
 #include "common.hpp"
+#include "depth_sort_plan.hpp"
 #include "shade_tables.hpp"
 
 #pragma clang fp contract(off)
@@ -120,8 +122,11 @@ __device__ __forceinline__ uint32_t sh_to_rgb(const PreArgs& a, const float* sh,
     return mask;
 }
 
-template <bool SVGSS>
-__global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
+// BK: the depth sort runs the bucket plan (depth_sort_plan.hpp).  A workgroup is then a ROW of DEPTH_ROW Gaussians: no thread leaves before
+// the epilogue, which groups the row's visible keys by bits 16..23 -- DepthRows -- instead of the stores of key[] and idx[].
+template <bool SVGSS, bool BK>
+__global__ void __launch_bounds__(BK ? DEPTH_ROW : BLOCK) preprocess_kernel(const PreArgs a, const DepthRows rows) {
+    constexpr int BLOCK = BK ? DEPTH_ROW : svgir::BLOCK;   // threads of a workgroup
     const int idx = blockIdx.x * BLOCK + threadIdx.x;
     // Memory order (one round of waves: the kernel costs its chain of dependent memory latencies): the uniform inputs are read
     // before the first store (behind one, the compiler can no longer prove them unclobbered and they stop being scalar loads); a
@@ -136,7 +141,9 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
         shade_table_entry(a.tabs, ((int)blockIdx.x - a.pblocks) * BLOCK + (int)threadIdx.x);
         return;
     }
-    if (idx >= a.P) return;
+    uint32_t vis_key = 0u, vis_w = 0u;   // BK: what a visible Gaussian takes into the epilogue
+    const bool visible = [&]() -> bool {   // (false: culled, or no Gaussian)
+    if (idx >= a.P) return false;
     const bool surface = cfg_flag(a.cfg, 0), pix_depth = cfg_flag(a.cfg, 2);
     if (a.out_weights) a.out_weights[idx] = 0.f;
     if (a.needed) a.needed[idx] = 0;
@@ -146,8 +153,10 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
     a.tiles[2 * idx] = 0;
     // (behind every visible key; under a speculated common top byte the depth sort skips that byte, so the culled keys carry it too.
     // Where a culled Gaussian lands in the depth order is immaterial: it emits nothing)
-    a.key[idx] = a.spec_top >= 0 ? (((uint32_t)a.spec_top << 24) | 0x00FFFFFFu) : 0xFFFFFFFFu;
-    a.idx[idx] = (uint32_t)idx;
+    if constexpr (!BK) {
+        a.key[idx] = a.spec_top >= 0 ? (((uint32_t)a.spec_top << 24) | 0x00FFFFFFu) : 0xFFFFFFFFu;
+        a.idx[idx] = (uint32_t)idx;
+    }
     if ((threadIdx.x & 63) == 0) a.key_top[idx >> 6] = 0xff00u;   // this wave's summary: none visible so far
 
     const float po[3] = {a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]};
@@ -170,12 +179,12 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
         const float w = x1 - x0, h = y1 - y0, e = (float)0.2;
         if (pv[2] < 0 || pix[0] < x0 - w * e || pix[0] >= x1 + w * e || pix[1] < y0 - h * e || pix[1] >= y1 + h * e) {
             if (a.prefilter_violation) *a.prefilter_violation = 1u;   // the reference traps here (auxiliary.h:163-167)
-            return;
+            return false;
         }
     } else {
         if (pv[2] <= 0.2f) {
             if (a.prefilter_violation) *a.prefilter_violation = 1u;
-            return;
+            return false;
         }
     }
 
@@ -202,7 +211,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
         const float dot = pv[0] * nv[0] + pv[1] * nv[1] + pv[2] * nv[2];
         if ((double)dot > -0.01) {  // back-facing
             if (a.prefilter_violation) *a.prefilter_violation = 1u;   // auxiliary.h:195-199
-            return;
+            return false;
         }
         if (pix_depth) {
             // local homography between the screen and the tangent plane (auxiliary.h:291-388)
@@ -214,7 +223,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
             const float m1 = normalize3(d1);
             const float c0 = d0[0] * nv[0] + d0[1] * nv[1] + d0[2] * nv[2];
             const float c1 = d1[0] * nv[0] + d1[1] * nv[1] + d1[2] * nv[2];
-            if (fabsf(c0 / m0) < 0.01f || fabsf(c1 / m1) < 0.01f) return;  // grazing
+            if (fabsf(c0 / m0) < 0.01f || fabsf(c1 / m1) < 0.01f) return false;  // grazing
             const float t = pv[0] * nv[0] + pv[1] * nv[1] + pv[2] * nv[2];
             const float t0 = t / c0, t1 = t / c1;
             float xu0[3], xu1[3];
@@ -282,7 +291,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
     const Mat3 cov = mmul(mmul(mtr(Tm), mtr(Vk)), Tm);
     const float ca = cov.m[0][0] + 0.3f, cb = cov.m[0][1], cc = cov.m[1][1] + 0.3f;
     const float det = ca * cc - cb * cb;
-    if (det == 0.0f) return;
+    if (det == 0.0f) return false;
     const float det_inv = 1.f / det;
     const float conic[3] = {cc * det_inv, -cb * det_inv, ca * det_inv};
     const float mid = 0.5f * (ca + cc);
@@ -292,7 +301,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
     int rmin[2], rmax[2];
     tile_rect(pix[0], pix[1], (int)my_radius, a.gx, a.gy, rmin, rmax);
     const int area = (rmax[0] - rmin[0]) * (rmax[1] - rmin[1]);
-    if (area == 0) return;
+    if (area == 0) return false;
 
     float emb[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // no vfeatures: the feature row travels in the record (common.hpp rec_embeds_features)
     if (a.embed_S > 0) {
@@ -305,7 +314,8 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
     a.radii[idx] = (int)my_radius;
     reinterpret_cast<uint2*>(a.tiles)[idx] = make_uint2((uint32_t)area, (uint32_t)rmin[0] | ((uint32_t)rmin[1] << 10) | ((uint32_t)(rmax[0] - rmin[0]) << 20));
     const uint32_t depth_key = __float_as_uint(pv[2]);
-    a.key[idx] = depth_key;
+    if constexpr (BK) { vis_key = depth_key; vis_w = (uint32_t)area; }
+    else a.key[idx] = depth_key;
     {   // AND / OR of the top bytes of this wave's visible keys (the lanes still here), for the host's guess of the next view's common byte
         const unsigned long long act = __ballot(true);
         uint32_t av = 0, ov = 0;
@@ -334,6 +344,58 @@ __global__ void __launch_bounds__(BLOCK) preprocess_kernel(const PreArgs a) {
     rec[3] = make_float4(db, rgb[0], rgb[1], rgb[2]);
     rec[4] = make_float4(nv[0], nv[1], nv[2], embed ? emb[4] : iu);
     rec[5] = make_float4(iv, 0.f, 0.f, 0.f);
+    return true;
+    }();
+    if constexpr (BK) {
+        // ---- the row, grouped (DepthRows): the ranking of a stable counting pass -- wave_match against wave-private counters, the waves'
+        // counts combined in order -- over the digit d of the visible keys; the other ids follow by index ----
+        constexpr int WAVES = BLOCK / 64;
+        __shared__ uint32_t wcnt[WAVES][256];   // per-wave digit counts, later the waves' cursors inside the row
+        __shared__ uint32_t whist[256], wsum[WAVES], wsum2[WAVES], wcul[WAVES];
+        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+        for (int i = t; i < WAVES * 256; i += BLOCK) (&wcnt[0][0])[i] = 0u;
+        if (t < 256) whist[t] = 0u;
+        __syncthreads();
+        const uint32_t d = (vis_key >> 16) & 255u;
+        const unsigned long long same = wave_match(d, 8, visible);
+        uint32_t rk = (uint32_t)__popcll(same & lt_mask);
+        if (visible) {
+            if (rk == 0) wcnt[wave][d] = (uint32_t)__popcll(same);
+            atomicAdd(&whist[d], vis_w);
+        }
+        const bool other = !visible && idx < a.P;
+        const unsigned long long others = __ballot(other);
+        if (other) rk = (uint32_t)__popcll(others & lt_mask);
+        if (lane == 0) wcul[wave] = (uint32_t)__popcll(others);
+        __syncthreads();
+        uint32_t c[WAVES], total = 0, wt = 0;
+#pragma unroll
+        for (int q = 0; q < WAVES; q++) { c[q] = t < 256 ? wcnt[q][t] : 0u; total += c[q]; }
+        if (t < 256) wt = whist[t];
+        uint32_t nvis, wall;
+        uint32_t run = block_excl_scan<WAVES>(total, wsum, &nvis);
+        const uint32_t wrun = block_excl_scan<WAVES>(wt, wsum2, &wall);
+        const size_t row = blockIdx.x;
+        if (t < 256) {   // (column t of the counters is this thread's alone until the barrier)
+            rows.cscan[row * 256 + t] = run;
+            rows.wscan[row * 256 + t] = wrun;
+#pragma unroll
+            for (int q = 0; q < WAVES; q++) { wcnt[q][t] = run; run += c[q]; }
+        }
+        if (t == 0) reinterpret_cast<uint2*>(rows.tot)[row] = make_uint2(nvis, wall);
+        __syncthreads();
+        if (visible) {
+            const size_t pos = row * BLOCK + wcnt[wave][d] + rk;
+            rows.key[pos] = vis_key;
+            rows.id[pos] = (uint32_t)idx;
+            rows.w[pos] = vis_w;
+        } else if (other) {
+            uint32_t before = nvis;
+            for (int q = 0; q < wave; q++) before += wcul[q];
+            rows.id[row * BLOCK + before + rk] = (uint32_t)idx;
+        }
+    }
 }
 
 __global__ void __launch_bounds__(BLOCK) mark_visible_kernel(int P, const float* means3D, const float* V,
@@ -346,13 +408,21 @@ __global__ void __launch_bounds__(BLOCK) mark_visible_kernel(int P, const float*
 
 }  // namespace
 
-void launch_preprocess(const PreArgs& a_, bool svgss, hipStream_t s) {
+static void launch_pre(const PreArgs& a_, const DepthRows* rows, bool svgss, hipStream_t s) {
     PreArgs a = a_;
-    a.pblocks = (a.P + BLOCK - 1) / BLOCK;
-    const int grid = a.pblocks + (a.tabs.entries() + BLOCK - 1) / BLOCK;   // (+ the shading tables of the fused path)
-    if (svgss) hipLaunchKernelGGL(preprocess_kernel<true>, dim3(grid), dim3(BLOCK), 0, s, a);
-    else hipLaunchKernelGGL(preprocess_kernel<false>, dim3(grid), dim3(BLOCK), 0, s, a);
+    const int block = rows ? DEPTH_ROW : BLOCK;
+    a.pblocks = (a.P + block - 1) / block;
+    const int grid = a.pblocks + (a.tabs.entries() + block - 1) / block;   // (+ the shading tables of the fused path)
+    if (rows) {
+        a.n_zero_words = 0;
+        if (svgss) hipLaunchKernelGGL((preprocess_kernel<true, true>), dim3(grid), dim3(block), 0, s, a, *rows);
+        else hipLaunchKernelGGL((preprocess_kernel<false, true>), dim3(grid), dim3(block), 0, s, a, *rows);
+    } else if (svgss) hipLaunchKernelGGL((preprocess_kernel<true, false>), dim3(grid), dim3(block), 0, s, a, DepthRows{});
+    else hipLaunchKernelGGL((preprocess_kernel<false, false>), dim3(grid), dim3(block), 0, s, a, DepthRows{});
 }
+
+void launch_preprocess(const PreArgs& a, bool svgss, hipStream_t s) { launch_pre(a, nullptr, svgss, s); }
+void launch_preprocess_rows(const PreArgs& a, const DepthRows& rows, bool svgss, hipStream_t s) { launch_pre(a, &rows, svgss, s); }
 
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s) {
     hipLaunchKernelGGL(mark_visible_kernel, dim3((P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, P, means3D, view, present);
