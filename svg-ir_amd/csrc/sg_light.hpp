@@ -1,7 +1,8 @@
 // svg-ir_amd/csrc/sg_light.hpp -- the lobe arithmetic of the spherical-Gaussian direct light (scene/direct_light_sg.py:
 // render_envmap_sg / DirectLightSG.direct_light), shared by the prepared-table prologue, svgir_sg_eval and the SG instantiations of the
-// shading kernels (csrc/shade.hip), and -- the second half of the file -- by the light's other consumers: the eval backward
-// (csrc/sg_light.hip), the eval view's backdrop (csrc/backdrop.hip) and the fused radiance-consistency loss (csrc/irradiance.hip).
+// shading kernels (csrc/shade.hip), and -- the second half of the file: the gradient's building blocks -- also by the light's other
+// consumers: the eval backward (csrc/sg_light.hip), the eval view's backdrop (csrc/backdrop.hip) and the fused radiance-consistency loss
+// (csrc/irradiance.hip).
 //
 // Raw parameters: lobes [M,7] = (xi.xyz, lambda, mu.rgb).  Light of a direction d (used as given):
 //   a = xi / |xi|,  e = exp(|lambda| (d.a - 1)),  L_c = sum_m |mu_mc| e_m      (fp32, m ascending, the accurate expf: |lambda| is in the
@@ -62,9 +63,8 @@ __device__ __forceinline__ void sg_eval(const float4* __restrict__ tab, int M, c
 // torch.clamp(L, 0, 64): NaN stays NaN (fminf / fmaxf would return the bound)
 __device__ __forceinline__ float sg_clamp(float L) { return L != L ? L : fminf(64.f, fmaxf(0.f, L)); }
 
-// ---- what the units outside shade.hip share (sg_light.hip, backdrop.hip, irradiance.hip).  A kernel cannot be launched across translation
-// units, so each unit wraps these in small __global__ kernels of its own.  (shade.hip keeps its own copies -- sg_prologue_kernel,
-// sg_chunk_adjoint, sg_grad_kernel -- until a change may touch that file: its hash is pinned to the committed counter profiles.)
+// ---- the building blocks of the light's kernels (shade.hip, sg_light.hip, backdrop.hip, irradiance.hip).  A kernel cannot be launched
+// across translation units, so each unit wraps these in small __global__ kernels of its own.
 
 // the prepared table of the whole light and the clear of `zero` [nzero], by every thread of a 1-D grid of at least M threads
 __device__ __forceinline__ void sg_table_build(const float* __restrict__ lobes, int M, float4* __restrict__ tab, float* __restrict__ zero, int nzero) {
@@ -79,7 +79,8 @@ __device__ __forceinline__ void sg_table_build(const float* __restrict__ lobes, 
 // samples j, j + ngroups, ...: records are LDS broadcasts, e is recomputed, and the seven table-space sums of a lobe
 //     d|mu|_c = sum e g_c,   d|lambda| = sum (d.a - 1) s,   G = sum s d      with s = sum_c |mu_c| e g_c   (dL/da = |lambda| G)
 // stay private to the thread for the call; they then go to the fp64 accumulator acc[8 M] = {G.xyz, d|lambda|, d|mu|.rgb, -} in LDS with
-// seven ds_add_f64 (the layout and the scheme of shade.hip's sg_chunk_adjoint).  A sample whose adjoint is all zero is skipped.
+// seven ds_add_f64 (the layout and the scheme of shade.hip's sg_chunk_adjoint, which stays a copy of this loop over the shading backward's
+// own records: routed through here that kernel measured 1.4 % slower).  A sample whose adjoint is all zero is skipped.
 // The caller orders the records' writes before the call and their reuse after it (a barrier, or wave_lds_sync for wave-private records).
 __device__ __forceinline__ void sg_adjoint_accumulate(const float4* __restrict__ sD, const float4* __restrict__ sG, int cnt,
                                                       const float4* __restrict__ tab, double* __restrict__ acc, int M, int tid, int nthr) {
@@ -138,7 +139,7 @@ __device__ __forceinline__ void sg_pullback(const float* __restrict__ lobes, con
 
 int report_error(int code, const char* fmt, ...);   // api.hip: records the per-thread message behind svgir_last_error, returns `code`
 
-// what every entry point outside shade.hip asks of a svgir_sg_light, before any HIP call
+// what every entry point asks of a svgir_sg_light, before any HIP call
 inline int sg_light_valid(const svgir_sg_light* l, const char* who) {
     if (!l) return report_error(SVGIR_ERR_INVALID, "%s: light is NULL", who);
     if (l->count < 1 || l->count > SVGIR_SG_MAX_LOBES)

@@ -37,6 +37,7 @@ namespace svgir {
 namespace {
 
 constexpr int SREC = 17;   // floats per staged sample: d(3) L(3) H(3) frac0 Lg(3) Ll(3) area
+constexpr int FW_WAVE_LDS = 64 * SREC + 80 + 32;   // LDS floats per wave of shade_fwd_kernel: 64 sample records | the output strip | the packing inputs
 constexpr int NRED = SVGIR_SHADE_REDUCED;
 constexpr float kPi = 3.14159265358979323846f;
 constexpr float kInvPi = 0.31830988618379067154f;
@@ -259,6 +260,56 @@ __device__ __forceinline__ float incident_of(float raw, const RadRatio& rr) {
     return v != v ? 0.f : c;
 }
 
+// The corner-independent prefix of a sample: il = 1 / |d|, L = d il, the UNNORMALISED half vector h = (L + V) / 2 and ih = 1 / |h|.
+// stage_samples and stage_raw_bwd normalise h and take V.H; the quad kernel never forms H and takes (V.h) ih -- another rounding.
+struct HalfVec { float il, L[3], h[3], ih; };
+__device__ __forceinline__ HalfVec half_vector(const float* d, const float* V) {
+    HalfVec hv;
+    hv.il = inv_norm(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // = 1 / max(|.|, 1e-12)
+#pragma unroll
+    for (int j = 0; j < 3; j++) { hv.L[j] = d[j] * hv.il; hv.h[j] = (hv.L[j] + V[j]) * 0.5f; }
+    hv.ih = inv_norm(hv.h[0] * hv.h[0] + hv.h[1] * hv.h[1] + hv.h[2] * hv.h[2]);   // = 1 / max(|.|, 1e-12)
+    return hv;
+}
+// the Schlick term of the raw V.H: 0.04 + 0.96 * 2^((-5.55473 x - 6.98316) x), x = clamp(V.H, 1e-6, 1)
+__device__ __forceinline__ float schlick(float voh) {
+    const float VoH = fminf(1.f, fmaxf(1e-6f, voh));
+    return 0.04f + (1.f - 0.04f) * __builtin_amdgcn_exp2f((-5.55473f * VoH - 6.98316f) * VoH);
+}
+
+// The texture light of direction d, before scale and clamp: the optional env_transform, the four bilinear taps, 12 unconditional gathers
+// (out-of-range taps: texel 0 with weight 0 -- one memory latency for all of them) and the weighted sum.
+__device__ __forceinline__ void tex_light(const svgir_shade_params& p, const float* d, float* E) {
+    EnvTap t;
+    float dl[3] = {d[0], d[1], d[2]};
+    if (p.env_transform) {
+        const float* m = p.env_transform;
+#pragma unroll
+        for (int j = 0; j < 3; j++) dl[j] = m[3 * j] * d[0] + m[3 * j + 1] * d[1] + m[3 * j + 2] * d[2];
+    }
+    env_taps(dl, p.env_h, p.env_w, t);
+    float tex[4][3];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float4 tq = reinterpret_cast<const float4*>(p.env_work)[t.idx[j] >= 0 ? t.idx[j] : 0];
+        tex[j][0] = tq.x; tex[j][1] = tq.y; tex[j][2] = tq.z;
+    }
+    E[0] = E[1] = E[2] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float w = t.idx[j] >= 0 ? t.w[j] : 0.f;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) E[ch] += w * tex[j][ch];
+    }
+}
+// E[3] = the unclamped global light of direction d: the lat-long texture, or the spherical-Gaussian mixture whose prepared table `sgt`
+// sits in LDS (p.env_w: the lobe count, see svgir_shade_forward_sg)
+template <int LIGHT>
+__device__ __forceinline__ void light_of(const svgir_shade_params& p, const float4* __restrict__ sgt, const float* d, float* E) {
+    if constexpr (LIGHT == LIGHT_SG) sg_eval(sgt, p.env_w, d, E);
+    else tex_light(p, d, E);
+}
+
 // the raw inputs of one incident sample (lane = sample), loadable a chunk / a Gaussian ahead of their use
 struct RawSample { float d[3], rad[3], vis, area; };
 
@@ -297,42 +348,16 @@ __device__ __forceinline__ void stage_samples(const svgir_shade_params& p, size_
         const float raw3[3] = {p.radiance[o * 3], p.radiance[o * 3 + 1], p.radiance[o * 3 + 2]};   // (one 96-bit load)
         const float rad[3] = {incident_of(raw3[0], rr), incident_of(raw3[1], rr), incident_of(raw3[2], rr)};
         const float vis = p.visibility[o], area = p.incident_areas ? p.incident_areas[o] : kTwoPi;
-        const float il = inv_norm(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // = 1 / max(|.|, 1e-12)
-        const float L[3] = {d[0] * il, d[1] * il, d[2] * il};
-        float H[3] = {(L[0] + V[0]) * 0.5f, (L[1] + V[1]) * 0.5f, (L[2] + V[2]) * 0.5f};
-        const float ih = inv_norm(H[0] * H[0] + H[1] * H[1] + H[2] * H[2]);   // = 1 / max(|.|, 1e-12)
-        H[0] *= ih; H[1] *= ih; H[2] *= ih;
-        const float VoH = fminf(1.f, fmaxf(1e-6f, V[0] * H[0] + V[1] * H[1] + V[2] * H[2]));
-        const float frac0 = 0.04f + (1.f - 0.04f) * __builtin_amdgcn_exp2f((-5.55473f * VoH - 6.98316f) * VoH);
-        float E[3] = {0.f, 0.f, 0.f};
-        if constexpr (LIGHT == LIGHT_SG) sg_eval(sgt, p.env_w, d, E);   // (env_w: the lobe count, see svgir_shade_forward_sg)
-        else {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
-        EnvTap t;
-        float dl[3] = {d[0], d[1], d[2]};
-        if (p.env_transform) {
-            const float* m = p.env_transform;
-#pragma unroll
-            for (int j = 0; j < 3; j++) dl[j] = m[3 * j] * d[0] + m[3 * j + 1] * d[1] + m[3 * j + 2] * d[2];
-        }
-        env_taps(dl, p.env_h, p.env_w, t);
-            float tex[4][3];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float4 tq = reinterpret_cast<const float4*>(p.env_work)[t.idx[j] >= 0 ? t.idx[j] : 0];
-                tex[j][0] = tq.x; tex[j][1] = tq.y; tex[j][2] = tq.z;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float w = t.idx[j] >= 0 ? t.w[j] : 0.f;
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) E[ch] += w * tex[j][ch];
-            }
-        }
+        const HalfVec hv = half_vector(d, V);
+        const float H[3] = {hv.h[0] * hv.ih, hv.h[1] * hv.ih, hv.h[2] * hv.ih};
+        const float frac0 = schlick(V[0] * H[0] + V[1] * H[1] + V[2] * H[2]);
+        float E[3];
+        light_of<LIGHT>(p, sgt, d, E);
         float* r = sS + lane * SREC;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
             const float Lg = (LIGHT == LIGHT_SG ? sg_clamp(E[ch]) : fminf(64.f, fmaxf(0.f, E[ch] * p.env_scale))) * vis;
-            r[ch] = d[ch]; r[3 + ch] = L[ch]; r[6 + ch] = H[ch];
+            r[ch] = d[ch]; r[3 + ch] = hv.L[ch]; r[6 + ch] = H[ch];
             r[10 + ch] = Lg; r[13 + ch] = rad[ch];
             m[3 + ch] += rad[ch]; m[6 + ch] += Lg;
         }
@@ -355,6 +380,23 @@ __device__ __forceinline__ void zero_rest_rows(const ShadeArgs& a, size_t wave_i
     }
 }
 
+// Element e of a surfel's `vfeatures` row [52 in training, else 64] (svgss.py:143-166), from so = its NRED reduced outputs and si = its
+// 28 packing inputs (base_color[12] | normals[12] | roughness[4]), both in LDS; vm = the view matrix of the normals @ view term.
+// (The 4/7-float `features` row is a pick of one slot of `so`, written where it is stored: the wave kernel selects between two loaded
+// values and the quad kernel between two slot indices, and either form in the other kernel changes that kernel's vector code.)
+__device__ __forceinline__ float pack_vfeature(const float* so, const float* si, int e, bool training, const float* __restrict__ vm) {
+    if (e < 12) return so[e];
+    if (e < 24) return si[e - 12];
+    if (e < 36) {
+        const int ee = e - 24, ch = ee >> 2, kc = ee & 3;  // channel*4 + corner
+        const float* n = si + 12 + kc * 3;
+        return n[0] * vm[0 * 4 + ch] + n[1] * vm[1 * 4 + ch] + n[2] * vm[2 * 4 + ch];
+    }
+    if (e < 40) return si[24 + (e - 36)];
+    if (e < 52) return training ? so[12 + (e - 40)] : so[36 + (e - 40)];
+    return so[48 + (e - 52)];
+}
+
 #ifndef SHADE_FWPE
 #define SHADE_FWPE 5   // 96 VGPRs without spills; the default heuristic settles on 107 (4 waves per SIMD): 285 -> 252 us at P = 200k, Ns = 64
 #endif
@@ -367,7 +409,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
     const svgir_shade_params& p = a.p;
     const float4* sgt = nullptr;   // LIGHT_SG: the prepared lobe table, staged behind the waves' strips (2 float4 per lobe, 4 KB at 128)
     if constexpr (LIGHT == LIGHT_SG) {
-        float4* st = reinterpret_cast<float4*>(smem + (size_t)4 * (64 * SREC + 80 + 32));
+        float4* st = reinterpret_cast<float4*>(smem + (size_t)4 * FW_WAVE_LDS);
         for (int i = threadIdx.x; i < 2 * p.env_w; i += BLOCK) st[i] = reinterpret_cast<const float4*>(p.env_work)[i];
         __syncthreads();
         sgt = st;
@@ -375,7 +417,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int Ns = p.Ns;
     const RadRatio rr = RATIO ? rad_ratio(p) : RadRatio{1.f, false};
-    float* sS = smem + (size_t)wave * (64 * SREC + 80 + 32);
+    float* sS = smem + (size_t)wave * FW_WAVE_LDS;
     float* sOut = sS + 64 * SREC;
     float* sIn = sOut + 80;   // base_color[12] | normals[12] | roughness[4] of this Gaussian, for the packing in the epilogue
     // work item -> surfel: all P of them, or the front of the caller's partition (svgir_shade_params.subset)
@@ -467,19 +509,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
     }
     if (a.vfeatures) {
         const int VS = p.training ? 52 : 64;
-        if (lane < VS) {
-            float v;
-            if (lane < 12) v = sOut[lane];
-            else if (lane < 24) v = sIn[lane - 12];
-            else if (lane < 36) {
-                const int e = lane - 24, ch = e >> 2, kc = e & 3;  // channel*4 + corner
-                const float* n = sIn + 12 + kc * 3;
-                v = n[0] * p.viewmatrix[0 * 4 + ch] + n[1] * p.viewmatrix[1 * 4 + ch] + n[2] * p.viewmatrix[2 * 4 + ch];
-            } else if (lane < 40) v = sIn[24 + (lane - 36)];
-            else if (lane < 52) v = p.training ? sOut[12 + (lane - 40)] : sOut[36 + (lane - 40)];
-            else v = sOut[48 + (lane - 52)];
-            a.vfeatures[g * VS + lane] = v;
-        }
+        if (lane < VS) a.vfeatures[g * VS + lane] = pack_vfeature(sOut, sIn, lane, p.training, p.viewmatrix);
     }
     DEV_TRACE_MARK(3);
     DEV_TRACE_END(1, 1u, (unsigned)Ns, 0u);
@@ -512,6 +542,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
 constexpr int FQ_SURF = 16;                      // surfels per wave
 constexpr int FQ_ROW = NRED + 2;                 // LDS floats per surfel: the 70 reduced outputs (+ pad: rows of a quad group on distinct banks)
 constexpr int FQ_IN = 28;                        // base_color[12] | normals[12] | roughness[4] of a surfel (for the packing)
+constexpr int FQ_WAVE_LDS = FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF;   // LDS floats per wave of shade_fwd_quad_kernel: output rows | packing inputs | surfel ids
 template <int J>
 __device__ __forceinline__ float quad_bcast(float v) {   // value of lane (quad base + J) in all four lanes of the quad
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), J | (J << 2) | (J << 4) | (J << 6), 0xf, 0xf, false));
@@ -525,14 +556,14 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
     const svgir_shade_params& p = a.p;
     const float4* sgt = nullptr;   // LIGHT_SG: the prepared lobe table, staged behind the waves' strips (see shade_fwd_kernel)
     if constexpr (LIGHT == LIGHT_SG) {
-        float4* st = reinterpret_cast<float4*>(smem + (size_t)4 * (FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF));
+        float4* st = reinterpret_cast<float4*>(smem + (size_t)4 * FQ_WAVE_LDS);
         for (int i = threadIdx.x; i < 2 * p.env_w; i += BLOCK) st[i] = reinterpret_cast<const float4*>(p.env_work)[i];
         __syncthreads();
         sgt = st;
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int Ns = p.Ns;
-    float* sOut = smem + (size_t)wave * (FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF);
+    float* sOut = smem + (size_t)wave * FQ_WAVE_LDS;
     float* sIn = sOut + FQ_SURF * FQ_ROW;
     uint32_t* sId = reinterpret_cast<uint32_t*>(sIn + FQ_SURF * FQ_IN);   // surfel of each of the wave's work items (subset launches)
     const int q = lane >> 2, k = lane & 3;
@@ -574,10 +605,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
     const float omk = 1.f - c.kk, a2m1 = c.a2 - 1.f;
 
     // raw inputs of the lane's sample of a step, fetched one step ahead
-    struct Raw { float d[3], rad[3], vis, area; };
     const RadRatio rrq = RATIO ? rad_ratio(p) : RadRatio{1.f, false};
-    auto load_raw_q = [&](int s) -> Raw {
-        Raw r;
+    auto load_raw_q = [&](int s) -> RawSample {   // (its own loader: through load_raw the compiler pairs the products of |d|^2 differently -- other bits)
+        RawSample r;
         const int sc = min(s, Ns - 1);
         const size_t o = gg * (size_t)Ns + (size_t)sc;
         if (!lattice) { r.d[0] = p.incident_dirs[o * 3]; r.d[1] = p.incident_dirs[o * 3 + 1]; r.d[2] = p.incident_dirs[o * 3 + 2]; }
@@ -587,11 +617,11 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
         r.area = p.incident_areas ? p.incident_areas[o] : kTwoPi;
         return r;
     };
-    Raw raw = load_raw_q(k);
+    RawSample raw = load_raw_q(k);
     for (int s0 = 0; s0 < Ns; s0 += 4) {
         const int s = s0 + k;
         const bool act = s < Ns;
-        Raw x = raw;
+        RawSample x = raw;
         raw = load_raw_q(s + 4);
         if (RATIO) {   // (at the values' USE, not at their load: the loads above are a step ahead)
 #pragma unroll
@@ -602,15 +632,11 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
         {
             float d[3] = {x.d[0], x.d[1], x.d[2]};
             if (lattice) lattice_dir(lf, ltab[min(s, Ns - 1)], min(s, Ns - 1), has_off, d);
-            const float il = inv_norm(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // = 1 / max(|.|, 1e-12)
-            const float L[3] = {d[0] * il, d[1] * il, d[2] * il};
-            float H[3] = {(L[0] + V[0]) * 0.5f, (L[1] + V[1]) * 0.5f, (L[2] + V[2]) * 0.5f};
-            const float ih = inv_norm(H[0] * H[0] + H[1] * H[1] + H[2] * H[2]);   // = 1 / max(|.|, 1e-12)
-            const float VoH = fminf(1.f, fmaxf(1e-6f, (V[0] * H[0] + V[1] * H[1] + V[2] * H[2]) * ih));
-            f.frac0 = 0.04f + (1.f - 0.04f) * __builtin_amdgcn_exp2f((-5.55473f * VoH - 6.98316f) * VoH);
+            const HalfVec hv = half_vector(d, V);
+            f.frac0 = schlick((V[0] * hv.h[0] + V[1] * hv.h[1] + V[2] * hv.h[2]) * hv.ih);   // (H is never formed: another rounding than V.H)
             float E[3] = {0.f, 0.f, 0.f};
             if constexpr (LIGHT == LIGHT_SG) sg_eval(sgt, p.env_w, d, E);   // the M lobes in place of the texture's taps
-            else {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
+            else {   // tex_light's lines, kept here: through the helper the compiler pairs the products of |d|^2 above differently (other bits)
             EnvTap t;
             float dl[3] = {d[0], d[1], d[2]};
             if (p.env_transform) {
@@ -641,7 +667,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
                 if (act) { m[ch] += x.rad[ch]; m[3 + ch] += Lg; }
             }
             if (act) m[6] += x.vis;
-            f.il = il; f.ih = ih;
+            f.il = hv.il; f.ih = hv.ih;
         }
         // ---- the quad's four samples against this lane's corner ----
         auto corner = [&](const FqSample& r) {
@@ -722,20 +748,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SHAD
         }
     }
     if (a.vfeatures) {
-        auto pack = [&](int qq, int e, bool training) -> float {
-            const float* so = sOut + qq * FQ_ROW;
-            const float* si = sIn + qq * FQ_IN;
-            if (e < 12) return so[e];
-            if (e < 24) return si[e - 12];
-            if (e < 36) {
-                const int ee = e - 24, ch = ee >> 2, kc = ee & 3;  // channel*4 + corner
-                const float* n = si + 12 + kc * 3;
-                return n[0] * p.viewmatrix[0 * 4 + ch] + n[1] * p.viewmatrix[1 * 4 + ch] + n[2] * p.viewmatrix[2 * 4 + ch];
-            }
-            if (e < 40) return si[24 + (e - 36)];
-            if (e < 52) return training ? so[12 + (e - 40)] : so[36 + (e - 40)];
-            return so[48 + (e - 52)];
-        };
+        auto pack = [&](int qq, int e, bool training) -> float { return pack_vfeature(sOut + qq * FQ_ROW, sIn + qq * FQ_IN, e, training, p.viewmatrix); };
         if (p.training) {
             for (int i = lane; i < nsurf * 52; i += 64) { const int qq = i / 52, e = i - qq * 52; a.vfeatures[row_of(qq) * 52 + e] = pack(qq, e, true); }
         } else {
@@ -776,6 +789,9 @@ constexpr int BREC = 20;
 #endif
 constexpr int BWAVES = SHADE_BWAVES;   // waves per backward workgroup
 constexpr int KB_G = SHADE_KB_G, KREC = 52;   // Gaussians prepared per batch; floats per (Gaussian, corner) record (13 float4)
+constexpr int BW_WAVE_LDS = 64 * BREC + 4 * KB_G * KREC;   // LDS floats per backward wave: 64 sample records + its batch of surfel records
+constexpr int BW_GROUP_LDS = BWAVES * BW_WAVE_LDS;         // ... per workgroup: all waves' sample records, then all waves' batches; the fp64 image follows
+static_assert(BW_GROUP_LDS % 2 == 0, "the fp64 image behind the sample records is 8-byte aligned");
 
 // LIGHT_SG: the record's footprint slots are free -- [16] carries the clamp flags alone, and [16..18] later receive the adjoint of the
 // sample's unclamped light (shade_bwd_kernel); ve = visibility.
@@ -783,86 +799,75 @@ template <int LIGHT>
 __device__ __forceinline__ void stage_raw_bwd(const svgir_shade_params& p, const RawSample& x, int lane, const float* V,
                                               float* __restrict__ sS, const RadRatio& rr, const float4* __restrict__ sgt) {
     const float* d = x.d;
-    const float il = inv_norm(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // = 1 / max(|.|, 1e-12)
-    const float L[3] = {d[0] * il, d[1] * il, d[2] * il};
-    float H[3] = {(L[0] + V[0]) * 0.5f, (L[1] + V[1]) * 0.5f, (L[2] + V[2]) * 0.5f};
-    const float ih = inv_norm(H[0] * H[0] + H[1] * H[1] + H[2] * H[2]);   // = 1 / max(|.|, 1e-12)
-    H[0] *= ih; H[1] *= ih; H[2] *= ih;
-    const float VoH = fminf(1.f, fmaxf(1e-6f, V[0] * H[0] + V[1] * H[1] + V[2] * H[2]));
-    const float frac0 = 0.04f + (1.f - 0.04f) * __builtin_amdgcn_exp2f((-5.55473f * VoH - 6.98316f) * VoH);
+    const HalfVec hv = half_vector(d, V);
+    const float il = hv.il;
+    const float H[3] = {hv.h[0] * hv.ih, hv.h[1] * hv.ih, hv.h[2] * hv.ih};
+    const float frac0 = schlick(V[0] * H[0] + V[1] * H[1] + V[2] * H[2]);
+    float Lg[3], ve, fx = 0.f, fy = 0.f;   // the clamped global light x visibility; slots 15, 17, 18 of the record
+    uint32_t word = 0;                      // slot 16: the clamp flags in bits 28..30 (+ the texture's footprint origin)
     if constexpr (LIGHT == LIGHT_SG) {
         float E[3];
         sg_eval(sgt, p.env_w, d, E);
-        float r[BREC];
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            Lg[ch] = sg_clamp(E[ch]) * x.vis;
+            word |= (E[ch] >= 0.f && E[ch] <= 64.f) ? (1u << ch) : 0u;   // (torch.clamp passes its gradient at the bounds; NaN: none)
+        }
+        ve = x.vis;
+        word <<= 28;
+    } else {
+        // bilinear footprint (same arithmetic as env_taps)
+        const int He = p.env_h, We = p.env_w;
+        float dl[3] = {d[0], d[1], d[2]};
+        if (p.env_transform) {
+            const float* m = p.env_transform;
+#pragma unroll
+            for (int j = 0; j < 3; j++) dl[j] = m[3 * j] * d[0] + m[3 * j + 1] * d[1] + m[3 * j + 2] * d[2];
+        }
+        const float phi = acosf(dl[2]) - 1e-6f;
+        const float theta = atan2f(dl[1], dl[0]);
+        const float gy = phi * (2.f * kInvPi) - 1.f;
+        const float gx = -theta * kInvPi;
+        const float xx = (gx + 1.f) * 0.5f * (float)(We - 1);
+        const float yy = (gy + 1.f) * 0.5f * (float)(He - 1);
+        const float x0f = floorf(xx), y0f = floorf(yy);
+        fx = xx - x0f; fy = yy - y0f;
+        const int x0 = (int)x0f, y0 = (int)y0f;
+        float E[3] = {0.f, 0.f, 0.f};
+        {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
+            float tex[4][3], tw[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int xi = x0 + (j & 1), yi = y0 + (j >> 1);
+                const bool ok = xi >= 0 && xi < We && yi >= 0 && yi < He;
+                tw[j] = ok ? ((j & 1) ? fx : 1.f - fx) * ((j >> 1) ? fy : 1.f - fy) : 0.f;
+                const float4 tq = reinterpret_cast<const float4*>(p.env_work)[ok ? yi * We + xi : 0];
+                tex[j][0] = tq.x; tex[j][1] = tq.y; tex[j][2] = tq.z;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) E[ch] += tw[j] * tex[j][ch];
+            }
+        }
         uint32_t flags = 0;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            r[ch] = d[ch]; r[4 + ch] = H[ch];
-            r[8 + ch] = sg_clamp(E[ch]) * x.vis; r[12 + ch] = incident_of(x.rad[ch], rr);
-            flags |= (E[ch] >= 0.f && E[ch] <= 64.f) ? (1u << ch) : 0u;   // (torch.clamp passes its gradient at the bounds; NaN: none)
+            const float Es = E[ch] * p.env_scale;
+            Lg[ch] = fminf(64.f, fmaxf(0.f, Es)) * x.vis;
+            flags |= (Es >= 0.f && Es <= 64.f) ? (1u << ch) : 0u;
         }
-        r[3] = il; r[7] = frac0; r[11] = x.area; r[15] = x.vis;
-        r[16] = __builtin_bit_cast(float, flags << 28);
-        r[17] = 0.f; r[18] = 0.f;
-        uint32_t nf = 0;
-        if (rr.on) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) nf |= ratio_finite(x.rad[ch], rr) ? 0u : (1u << ch);
-        }
-        r[19] = __builtin_bit_cast(float, nf);
-        float4* o = reinterpret_cast<float4*>(sS + lane * BREC);
-#pragma unroll
-        for (int i = 0; i < BREC / 4; i++) o[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
-        return;
+        ve = x.vis * p.env_scale;
+        // footprint origin, biased by +1 (x0, y0 >= -1 by construction), 14 bits each (the launcher checks the map's size)
+        const int xb = min(max(x0 + 1, 0), 16383), yb = min(max(y0 + 1, 0), 16383);
+        word = (uint32_t)xb | ((uint32_t)yb << 14) | (flags << 28);
     }
-    // bilinear footprint (same arithmetic as env_taps)
-    const int He = p.env_h, We = p.env_w;
-    float dl[3] = {d[0], d[1], d[2]};
-    if (p.env_transform) {
-        const float* m = p.env_transform;
-#pragma unroll
-        for (int j = 0; j < 3; j++) dl[j] = m[3 * j] * d[0] + m[3 * j + 1] * d[1] + m[3 * j + 2] * d[2];
-    }
-    const float phi = acosf(dl[2]) - 1e-6f;
-    const float theta = atan2f(dl[1], dl[0]);
-    const float gy = phi * (2.f * kInvPi) - 1.f;
-    const float gx = -theta * kInvPi;
-    const float xx = (gx + 1.f) * 0.5f * (float)(We - 1);
-    const float yy = (gy + 1.f) * 0.5f * (float)(He - 1);
-    const float x0f = floorf(xx), y0f = floorf(yy);
-    const float fx = xx - x0f, fy = yy - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    float E[3] = {0.f, 0.f, 0.f};
-    {   // 12 unconditional gathers (out-of-range taps: texel 0 with weight 0), one memory latency for all of them
-        float tex[4][3], tw[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int xi = x0 + (j & 1), yi = y0 + (j >> 1);
-            const bool ok = xi >= 0 && xi < We && yi >= 0 && yi < He;
-            tw[j] = ok ? ((j & 1) ? fx : 1.f - fx) * ((j >> 1) ? fy : 1.f - fy) : 0.f;
-            const float4 tq = reinterpret_cast<const float4*>(p.env_work)[ok ? yi * We + xi : 0];
-            tex[j][0] = tq.x; tex[j][1] = tq.y; tex[j][2] = tq.z;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) E[ch] += tw[j] * tex[j][ch];
-        }
-    }
+    // ---- the record (both light kinds) ----
     float r[BREC];
-    uint32_t flags = 0;
 #pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const float Es = E[ch] * p.env_scale;
-        r[ch] = d[ch]; r[4 + ch] = H[ch];
-        r[8 + ch] = fminf(64.f, fmaxf(0.f, Es)) * x.vis; r[12 + ch] = incident_of(x.rad[ch], rr);
-        flags |= (Es >= 0.f && Es <= 64.f) ? (1u << ch) : 0u;
-    }
-    r[3] = il; r[7] = frac0; r[11] = x.area; r[15] = x.vis * p.env_scale;
-    // footprint origin, biased by +1 (x0, y0 >= -1 by construction), 14 bits each (the launcher checks the map's size)
-    const int xb = min(max(x0 + 1, 0), 16383), yb = min(max(y0 + 1, 0), 16383);
-    r[16] = __builtin_bit_cast(float, (uint32_t)xb | ((uint32_t)yb << 14) | (flags << 28));
-    r[17] = fx; r[18] = fy;
+    for (int ch = 0; ch < 3; ch++) { r[ch] = d[ch]; r[4 + ch] = H[ch]; r[8 + ch] = Lg[ch]; r[12 + ch] = incident_of(x.rad[ch], rr); }
+    r[3] = il; r[7] = frac0; r[11] = x.area; r[15] = ve;
+    r[16] = __builtin_bit_cast(float, word); r[17] = fx; r[18] = fy;
     {   // radiance_ratio: which channels' products were not finite (nan_to_num passes no gradient there), bits 0..2
         uint32_t nf = 0;
         if (rr.on) {
@@ -893,6 +898,9 @@ __device__ __forceinline__ float stride4_sum(float v) {
 //     d|mu|_c = sum e g_c,   d|lambda| = sum (d.a - 1) s,   G = sum s d      with s = sum_c |mu_c| e g_c   (dL/da = |lambda| G)
 // are private to the lane for the chunk: no cross-lane reduction.  They then go to the workgroup's fp64 accumulator with seven ds_add_f64
 // per lobe and chunk (against 12 per 16 samples for the texture's taps).  Samples without an adjoint (occluded, clamped) are skipped.
+// (sg_light.hpp's sg_adjoint_accumulate is this loop for any thread count and the other units' record layout.  Through it the kernel's
+// vector code is the same and its set-up four bytes shorter -- one scalar min for a compare and a select --, and the SG backward measured
+// 1.4 % slower in alternated runs: the copy stays.)
 __device__ __forceinline__ void sg_chunk_adjoint(const float* __restrict__ sS, int cnt, const float4* __restrict__ sgt, double* __restrict__ acc,
                                                  int M, int lane) {
     const int lpg_shift = M > 32 ? 6 : 32 - __builtin_clz((unsigned)max(M, 2) - 1u);   // lanes per sample group: the power of two >= min(M, 64)
@@ -953,14 +961,14 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
     const int ntex = LIGHT == LIGHT_SG ? 8 * We : He * We * 3;   // (LIGHT_SG: env_w = the lobe count, env_in_lds = 1)
     float* sS = smem + (size_t)wave * (64 * BREC);
     float* sK = smem + (size_t)BWAVES * (64 * BREC) + (size_t)wave * (4 * KB_G * KREC);   // this wave's batch of per-(Gaussian, corner) records
-    double* sEnv = reinterpret_cast<double*>(smem + (size_t)BWAVES * (64 * BREC + 4 * KB_G * KREC));   // [ntex] (only when env_in_lds)
+    double* sEnv = reinterpret_cast<double*>(smem + (size_t)BW_GROUP_LDS);   // [ntex] (only when env_in_lds)
     if (!VIEW && env_in_lds) {
         for (int i = threadIdx.x; i < ntex; i += BWAVES * 64) sEnv[i] = 0.0;
     }
     // LIGHT_SG: the lobe count and the table's place are derived where they are used instead of being named across the kernel
     auto sg_count = [&]() -> int { return p.env_w; };
     auto sg_tab = [&]() -> const float4* {
-        return LIGHT == LIGHT_SG ? reinterpret_cast<const float4*>(smem + (size_t)BWAVES * (64 * BREC + 4 * KB_G * KREC)) + 4 * sg_count() : nullptr;
+        return LIGHT == LIGHT_SG ? reinterpret_cast<const float4*>(smem + (size_t)BW_GROUP_LDS) + 4 * sg_count() : nullptr;
     };
     if constexpr (LIGHT == LIGHT_SG) {
         float4* st = reinterpret_cast<float4*>(sEnv + 8 * We);
@@ -1373,20 +1381,24 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
 
 #undef SHADE_LOAD_REC
 
+// dL/d(radiance_ratio): the backward workgroups' partial sums (<= BLOCK of them) added by the BLOCK threads of one workgroup in a fixed
+// tree -- reproducible, whatever order the workgroups finished in
+__device__ __forceinline__ void ratio_tree(const float* __restrict__ ratio_part, int nparts, float* __restrict__ d_ratio) {
+    __shared__ float part[BLOCK];
+    part[threadIdx.x] = (int)threadIdx.x < nparts ? ratio_part[threadIdx.x] : 0.f;
+    __syncthreads();
+    for (int h = BLOCK / 2; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *d_ratio = part[0];
+}
+
 // dL/d env_raw = dL/d f(env) * f'(env);  softplus' = sigmoid
 __global__ void __launch_bounds__(BLOCK) env_grad_kernel(const float* __restrict__ env, const float* __restrict__ dtab,
                                                          float* __restrict__ denv, int n, int softplus,
                                                          const float* __restrict__ ratio_part, int nparts, float* __restrict__ d_ratio) {
-    if (d_ratio && blockIdx.x == 0) {   // dL/d(radiance_ratio): the workgroups' partial sums (<= 256), a fixed tree
-        __shared__ float part[BLOCK];
-        part[threadIdx.x] = (int)threadIdx.x < nparts ? ratio_part[threadIdx.x] : 0.f;
-        __syncthreads();
-        for (int h = BLOCK / 2; h >= 1; h >>= 1) {
-            if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) *d_ratio = part[0];
-    }
+    if (d_ratio && blockIdx.x == 0) ratio_tree(ratio_part, nparts, d_ratio);
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const float x = env[i];
@@ -1399,7 +1411,7 @@ __global__ void __launch_bounds__(BLOCK) env_grad_kernel(const float* __restrict
 // table-space gradient accumulator
 __global__ void __launch_bounds__(BLOCK) sg_prologue_kernel(const float* __restrict__ lobes, int M, float4* __restrict__ tab, const ShadeTables t) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < M) sg_table_entry(lobes, i, tab);
+    if (i < M) sg_table_entry(lobes, i, tab);   // (sg_table_build reads blockDim: two more registers than the constant BLOCK)
     shade_table_entry(t, i);
     for (int j = i; j < t.nzero; j += gridDim.x * BLOCK) t.zero[j] = 0.f;
 }
@@ -1423,28 +1435,10 @@ __global__ void __launch_bounds__(BLOCK) sg_eval_kernel(const float4* __restrict
 __global__ void __launch_bounds__(BLOCK) sg_grad_kernel(const float* __restrict__ lobes, const float4* __restrict__ tab, const float* __restrict__ dtab,
                                                         float* __restrict__ dlobes, int M, const float* __restrict__ ratio_part, int nparts,
                                                         float* __restrict__ d_ratio) {
-    if (d_ratio) {   // dL/d(radiance_ratio): the workgroups' partial sums (<= 256), a fixed tree (as env_grad_kernel; one block)
-        __shared__ float part[BLOCK];
-        part[threadIdx.x] = (int)threadIdx.x < nparts ? ratio_part[threadIdx.x] : 0.f;
-        __syncthreads();
-        for (int h = BLOCK / 2; h >= 1; h >>= 1) {
-            if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) *d_ratio = part[0];
-    }
+    if (d_ratio) ratio_tree(ratio_part, nparts, d_ratio);   // (one block)
     const int m = threadIdx.x;
     if (m >= M) return;
-    auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); };
-    const float4 al = tab[2 * m], mu = tab[2 * m + 1];
-    const float* g = dtab + 8 * m;
-    const float* l = lobes + 7 * m;
-    const float ag = al.x * g[0] + al.y * g[1] + al.z * g[2];
-    const float sc = al.w * mu.w;   // |lambda| / |xi|
-    float* o = dlobes + 7 * m;
-    o[0] = sc * (g[0] - al.x * ag); o[1] = sc * (g[1] - al.y * ag); o[2] = sc * (g[2] - al.z * ag);
-    o[3] = sgn(l[3]) * g[3];
-    o[4] = sgn(l[4]) * g[4]; o[5] = sgn(l[5]) * g[5]; o[6] = sgn(l[6]) * g[6];
+    sg_pullback(lobes, tab, dtab, m, dlobes);
 }
 
 static_assert(SVGIR_SG_MAX_LOBES <= BLOCK, "sg_grad_kernel: one thread per lobe, one block");
@@ -1462,11 +1456,11 @@ void launch_shade_fwd(const ShadeArgs& a, size_t light_lds, hipStream_t s) {
     // those are amortised anyway and the one-wave-per-surfel kernel streams the samples better (lane = sample: 768 contiguous bytes
     // per load; 771 us against 1 001 us at Ns = 384)
     if (SHADE_FWD_QUAD && p->Ns <= SHADE_FWD_QUAD_MAX_NS) {
-        const size_t lds = (size_t)4 * (FQ_SURF * (FQ_ROW + FQ_IN) + FQ_SURF) * 4 + light_lds;
+        const size_t lds = (size_t)4 * FQ_WAVE_LDS * 4 + light_lds;
         if (p->radiance_ratio) hipLaunchKernelGGL((shade_fwd_quad_kernel<true, LIGHT>), dim3((p->P + 4 * FQ_SURF - 1) / (4 * FQ_SURF)), dim3(BLOCK), lds, s, a);
         else hipLaunchKernelGGL((shade_fwd_quad_kernel<false, LIGHT>), dim3((p->P + 4 * FQ_SURF - 1) / (4 * FQ_SURF)), dim3(BLOCK), lds, s, a);
     } else {
-        const size_t lds = (size_t)4 * (64 * SREC + 80 + 32) * 4 + light_lds;
+        const size_t lds = (size_t)4 * FW_WAVE_LDS * 4 + light_lds;
         if (p->radiance_ratio) hipLaunchKernelGGL((shade_fwd_kernel<true, LIGHT>), dim3((p->P + 3) / 4), dim3(BLOCK), lds, s, a);
         else hipLaunchKernelGGL((shade_fwd_kernel<false, LIGHT>), dim3((p->P + 3) / 4), dim3(BLOCK), lds, s, a);
     }
@@ -1485,6 +1479,48 @@ int shade_bwd_lds_opt_in() {
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     return 0;
+}
+
+// the backward twin of launch_shade_fwd: the RATIO x VIEW instantiation of one light kind (VIEW: the view-direction pass)
+template <int LIGHT>
+void launch_shade_bwd(const ShadeBwdArgs& a, int blocks, size_t lds, bool view, int env_in_lds, hipStream_t s) {
+    const bool ratio = a.p.radiance_ratio != nullptr;
+    if (view) {
+        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, true, LIGHT>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, env_in_lds);
+        else hipLaunchKernelGGL((shade_bwd_kernel<false, true, LIGHT>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, env_in_lds);
+    } else {
+        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, false, LIGHT>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, env_in_lds);
+        else hipLaunchKernelGGL((shade_bwd_kernel<false, false, LIGHT>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, env_in_lds);
+    }
+}
+
+// the backward's grid: persistent workgroups, as many as fit the device at SHADE_BWPE waves per SIMD (256 CUs) and no more than there is work
+int shade_bwd_blocks(int P) {
+    static_assert(256 * (SHADE_BWPE * 4 / BWAVES > 1 ? SHADE_BWPE * 4 / BWAVES : 1) <= SVGIR_SHADE_RATIO_WORK, "one partial sum per workgroup");
+    return std::max(1, std::min((P + BWAVES - 1) / BWAVES, 256 * std::max(1, SHADE_BWPE * 4 / BWAVES)));
+}
+
+// the backward kernels' arguments.  `work`: the gradient accumulator of the light's table (ntab floats: the f(env) table, or the lobes'
+// table-space sums) with the SVGIR_SHADE_RATIO_WORK per-workgroup partial sums of dL/d(radiance_ratio) behind it
+ShadeBwdArgs shade_bwd_args(const svgir_shade_params& p, const float* g_red, const float* g_feat, const float* g_vfeat, float* d_base, float* d_rough,
+                            float* d_normals, float* d_radiance, float* work, int ntab, const float* d_ratio, float* d_viewdirs, int zero_rest) {
+    ShadeBwdArgs a;
+    a.p = p; a.g_red = g_red; a.g_feat = g_feat; a.g_vfeat = g_vfeat; a.d_base = d_base; a.d_rough = d_rough; a.d_normals = d_normals;
+    a.d_radiance = d_radiance; a.d_envtab = work; a.d_viewdirs = d_viewdirs;
+    a.ratio_part = d_ratio ? work + ntab : nullptr;
+    a.zero_rest = zero_rest;
+    return a;
+}
+
+// What every shading entry point, of either light kind, asks of the incident inputs of a call with P > 0 (and of lattice_work's alignment
+// whatever P is); `materials`: also of the material / incident tensors.  nullptr, or what is wrong -- the SG entry points report it, the
+// texture's return a bare SVGIR_ERR_INVALID.
+const char* shade_inputs_check(const svgir_shade_params* p, bool materials) {
+    if (materials && p->P > 0 && (!p->base_color || !p->roughness || !p->normals || !p->viewdirs || !p->radiance || !p->visibility))
+        return "a material / incident input is NULL";
+    if (p->P > 0 && !p->incident_dirs && !(p->lattice_normals && p->lattice_work)) return "neither incident_dirs nor the lattice inputs are given";
+    if (p->lattice_work && ((uintptr_t)p->lattice_work & 15)) return "lattice_work must be 16-byte aligned";   // read as float4
+    return nullptr;
 }
 
 }  // namespace
@@ -1521,14 +1557,10 @@ svgir::ShadeTables svgir::shade_tables(const svgir_shade_params* p, float* zero,
 int svgir::shade_forward_impl(const svgir_shade_params* p, float* reduced, float* features, float* vfeatures, bool tables_ready, void* stream) {
     if (!p || p->P < 0 || p->Ns <= 0 || p->env_h <= 0 || p->env_w <= 0) return SVGIR_ERR_INVALID;
     if (p->P == 0) return 0;
-    if (!p->base_color || !p->roughness || !p->normals || !p->viewdirs || !p->radiance || !p->visibility ||
-        !p->env || !p->env_work || (vfeatures && !p->viewmatrix))
-        return SVGIR_ERR_INVALID;
-    if (!p->incident_dirs && !(p->lattice_normals && p->lattice_work)) return SVGIR_ERR_INVALID;
-    if (((uintptr_t)p->env_work & 15) || (p->lattice_work && ((uintptr_t)p->lattice_work & 15))) return SVGIR_ERR_INVALID;   // read as float4
+    if (shade_inputs_check(p, true) || !p->env || !p->env_work || (vfeatures && !p->viewmatrix)) return SVGIR_ERR_INVALID;
+    if ((uintptr_t)p->env_work & 15) return SVGIR_ERR_INVALID;   // read as float4
     if ((p->subset != nullptr) != (p->subset_count != nullptr)) return SVGIR_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const int ntex = p->env_h * p->env_w * 3;
     StageMarks tm = stage_begin(s);
     if (!tables_ready) launch_shade_prologue(p, nullptr, 0, s);
     stage_mark(tm, "shade_env_table");
@@ -1543,25 +1575,12 @@ int svgir::shade_forward_impl(const svgir_shade_params* p, float* reduced, float
 // ---- spherical-Gaussian light (include/svgir_raster.h "Spherical-Gaussian direct light") --------------------------------------------
 namespace {
 
-int sg_light_check(const svgir_sg_light* l, const char* who) {
-    if (!l) return report_error(SVGIR_ERR_INVALID, "%s: light is NULL", who);
-    if (l->count < 1 || l->count > SVGIR_SG_MAX_LOBES)
-        return report_error(SVGIR_ERR_INVALID, "%s: light.count = %d, 1 ... %d lobes", who, l->count, SVGIR_SG_MAX_LOBES);
-    if (!l->lobes || !l->work) return report_error(SVGIR_ERR_INVALID, "%s: light.lobes / light.work is NULL", who);
-    if ((uintptr_t)l->work & 15) return report_error(SVGIR_ERR_INVALID, "%s: light.work must be 16-byte aligned (read as float4)", who);
-    return 0;
-}
-
 // what the two shading entry points ask of svgir_shade_params (the env* fields are not read)
 int sg_params_check(const svgir_shade_params* p, const char* who) {
     if (!p || p->P < 0 || p->Ns <= 0) return report_error(SVGIR_ERR_INVALID, "%s: bad P / Ns", who);
     if (p->subset || p->subset_count)
         return report_error(SVGIR_ERR_INVALID, "%s: subset shading belongs to the rasterizer-fused path, which has no SG light", who);
-    if (p->P > 0 && (!p->base_color || !p->roughness || !p->normals || !p->viewdirs || !p->radiance || !p->visibility))
-        return report_error(SVGIR_ERR_INVALID, "%s: a material / incident input is NULL", who);
-    if (p->P > 0 && !p->incident_dirs && !(p->lattice_normals && p->lattice_work))
-        return report_error(SVGIR_ERR_INVALID, "%s: neither incident_dirs nor the lattice inputs are given", who);
-    if (p->lattice_work && ((uintptr_t)p->lattice_work & 15)) return report_error(SVGIR_ERR_INVALID, "%s: lattice_work must be 16-byte aligned", who);
+    if (const char* why = shade_inputs_check(p, true)) return report_error(SVGIR_ERR_INVALID, "%s: %s", who, why);
     return 0;
 }
 
@@ -1589,7 +1608,7 @@ size_t svgir_sg_grad_work_bytes(int32_t count) {
 }
 
 int svgir_sg_eval(const svgir_sg_light* light, int64_t n, const float* dirs, float* out, void* stream) {
-    if (int rc = sg_light_check(light, "sg_eval")) return rc;
+    if (int rc = sg_light_valid(light, "sg_eval")) return rc;
     if (n < 0 || (n > 0 && (!dirs || !out))) return report_error(SVGIR_ERR_INVALID, "sg_eval: bad n / NULL dirs or out");
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1602,7 +1621,7 @@ int svgir_sg_eval(const svgir_sg_light* light, int64_t n, const float* dirs, flo
 int svgir_shade_forward_sg(const svgir_shade_params* p, const svgir_sg_light* light, float* reduced, float* features, float* vfeatures,
                            void* stream) {
     if (int rc = sg_params_check(p, "shade_forward_sg")) return rc;
-    if (int rc = sg_light_check(light, "shade_forward_sg")) return rc;
+    if (int rc = sg_light_valid(light, "shade_forward_sg")) return rc;
     if (vfeatures && !p->viewmatrix) return report_error(SVGIR_ERR_INVALID, "shade_forward_sg: vfeatures needs viewmatrix");
     if (p->P == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1620,7 +1639,7 @@ int svgir_shade_backward_sg(const svgir_shade_params* p, const svgir_sg_light* l
                             const float* dL_dvfeatures, float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance,
                             float* dL_dlobes, float* grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream) {
     if (int rc = sg_params_check(p, "shade_backward_sg")) return rc;
-    if (int rc = sg_light_check(light, "shade_backward_sg")) return rc;
+    if (int rc = sg_light_valid(light, "shade_backward_sg")) return rc;
     if ((!dL_dreduced && !dL_dfeatures && !dL_dvfeatures) || (dL_dvfeatures && !p->viewmatrix) || !dL_dbase_color || !dL_droughness || !dL_dnormals ||
         !dL_dlobes || !grad_work)
         return report_error(SVGIR_ERR_INVALID, "shade_backward_sg: an upstream gradient, an output or grad_work is missing");
@@ -1630,28 +1649,20 @@ int svgir_shade_backward_sg(const svgir_shade_params* p, const svgir_sg_light* l
     const int M = light->count, ntab = 8 * M;
     StageMarks tm = stage_begin(s);
     launch_sg_prologue(light, p, grad_work, ntab, s);   // (also when P == 0: dL_dlobes is then all zeros)
-    ShadeBwdArgs a;
-    a.p = sg_kernel_params(p, light); a.g_red = dL_dreduced; a.g_feat = dL_dfeatures; a.g_vfeat = dL_dvfeatures; a.d_base = dL_dbase_color;
-    a.d_rough = dL_droughness; a.d_normals = dL_dnormals; a.d_radiance = dL_dradiance; a.d_envtab = grad_work; a.d_viewdirs = dL_dviewdirs;
-    a.ratio_part = dL_dradiance_ratio ? grad_work + ntab : nullptr;   // (SVGIR_SHADE_RATIO_WORK floats behind the table-space sums)
-    a.zero_rest = 0;
-    const bool ratio = p->radiance_ratio != nullptr;
+    const ShadeBwdArgs a = shade_bwd_args(sg_kernel_params(p, light), dL_dreduced, dL_dfeatures, dL_dvfeatures, dL_dbase_color, dL_droughness, dL_dnormals,
+                                          dL_dradiance, grad_work, ntab, dL_dradiance_ratio, dL_dviewdirs, 0);
     // the waves' records, the fp64 sums (8 M doubles) and the prepared table (8 M floats): 110 KB at M = 128, one workgroup per CU
-    const size_t lds = BWAVES * (size_t)(64 * BREC + 4 * KB_G * KREC) * 4 + (size_t)ntab * 8 + (size_t)ntab * 4;
+    const size_t lds = (size_t)BW_GROUP_LDS * 4 + (size_t)ntab * 8 + (size_t)ntab * 4;
     if (int rc = shade_bwd_lds_opt_in<LIGHT_SG>()) return rc;
-    const int blocks = std::max(1, std::min((p->P + BWAVES - 1) / BWAVES, 256 * std::max(1, SHADE_BWPE * 4 / BWAVES)));
+    const int blocks = shade_bwd_blocks(p->P);
     stage_mark(tm, "shade_bwd_sg_prologue");
-    if (p->P > 0) {
-        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, false, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 1);
-        else hipLaunchKernelGGL((shade_bwd_kernel<false, false, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 1);
-    }
+    if (p->P > 0) launch_shade_bwd<LIGHT_SG>(a, blocks, lds, false, 1, s);
     stage_mark(tm, "shade_bwd_sg");
     hipLaunchKernelGGL(sg_grad_kernel, dim3(1), dim3(BLOCK), 0, s, light->lobes, (const float4*)light->work, grad_work, dL_dlobes, M,
                        a.ratio_part, p->P > 0 ? blocks : 0, dL_dradiance_ratio);   // (P == 0: the scalar's gradient is 0 too)
     stage_mark(tm, "shade_sg_grad");
     if (dL_dviewdirs && p->P > 0) {   // the view-direction pass: the same grid and LDS layout (the sums' slots stay unused)
-        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, true, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 0);
-        else hipLaunchKernelGGL((shade_bwd_kernel<false, true, LIGHT_SG>), dim3(blocks), dim3(BWAVES * 64), lds, s, a, 0);
+        launch_shade_bwd<LIGHT_SG>(a, blocks, lds, true, 0, s);
         stage_mark(tm, "shade_bwd_view_sg");
     }
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
@@ -1692,49 +1703,31 @@ int svgir::shade_backward_impl(const svgir_shade_params* p, const float* dL_dred
         return SVGIR_ERR_INVALID;
     // (with radiance_ratio the cache itself is detached in the reference: its gradient is optional; the scalar's gradient needs the scalar)
     if ((!dL_dradiance && !p->radiance_ratio) || (dL_dradiance_ratio && !p->radiance_ratio)) return SVGIR_ERR_INVALID;
-    if (!p->incident_dirs && !(p->lattice_normals && p->lattice_work)) return SVGIR_ERR_INVALID;
-    if (((uintptr_t)p->env_work & 15) || (p->lattice_work && ((uintptr_t)p->lattice_work & 15))) return SVGIR_ERR_INVALID;   // read as float4
+    if (shade_inputs_check(p, false) || ((uintptr_t)p->env_work & 15)) return SVGIR_ERR_INVALID;   // (env_work: read as float4)
     if ((p->subset != nullptr) != (p->subset_count != nullptr)) return SVGIR_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int ntex = p->env_h * p->env_w * 3;
     StageMarks tm = stage_begin(s);
     if (!tables_ready) launch_shade_prologue(p, env_grad_work, ntex, s);
 
-    ShadeBwdArgs a;
-    a.p = *p; a.g_red = dL_dreduced; a.g_feat = dL_dfeatures; a.g_vfeat = dL_dvfeatures; a.d_base = dL_dbase_color; a.d_rough = dL_droughness; a.d_normals = dL_dnormals;
-    a.d_radiance = dL_dradiance; a.d_envtab = env_grad_work; a.d_viewdirs = dL_dviewdirs;
-    a.ratio_part = dL_dradiance_ratio ? env_grad_work + ntex : nullptr;   // (SVGIR_SHADE_RATIO_WORK floats behind the env-gradient table)
-    const bool ratio = p->radiance_ratio != nullptr;
-    a.zero_rest = (p->subset && !rows_precleared) ? 1 : 0;   // (every output is written completely: rows outside the subset are zero)
-    const size_t per_wave = (size_t)(64 * BREC + 4 * KB_G * KREC) * 4;
-    size_t lds = BWAVES * per_wave;
+    // (zero_rest: every output is written completely -- rows outside the subset are zero)
+    const ShadeBwdArgs a = shade_bwd_args(*p, dL_dreduced, dL_dfeatures, dL_dvfeatures, dL_dbase_color, dL_droughness, dL_dnormals, dL_dradiance,
+                                          env_grad_work, ntex, dL_dradiance_ratio, dL_dviewdirs, (p->subset && !rows_precleared) ? 1 : 0);
+    const size_t rec_lds = (size_t)BW_GROUP_LDS * 4;
+    size_t lds = rec_lds;
     int env_in_lds = 0;
     if (p->env_w > 16000 || p->env_h > 16000) return SVGIR_ERR_INVALID;   // (14-bit footprint origins in the sample records)
-    static_assert((BWAVES * (64 * BREC + 4 * KB_G * KREC)) % 2 == 0, "the fp64 image behind the sample records is 8-byte aligned");
     if (lds + (size_t)ntex * 8 <= 160 * 1024) { env_in_lds = 1; lds += (size_t)ntex * 8; }   // one workgroup per CU
-    {
-        static bool attr_set[64] = {};   // per device (> 64 KB of dynamic LDS needs the opt-in; idempotent, so races are harmless)
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return SVGIR_ERR_HIP;
-        if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-            for (const void* f : {reinterpret_cast<const void*>(shade_bwd_kernel<false>), reinterpret_cast<const void*>(shade_bwd_kernel<true>),
-                                  reinterpret_cast<const void*>(shade_bwd_kernel<false, true>), reinterpret_cast<const void*>(shade_bwd_kernel<true, true>)})
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SVGIR_ERR_HIP;
-            if (dev >= 0 && dev < 64) attr_set[dev] = true;
-        }
-    }
-    const int blocks = std::min((p->P + BWAVES - 1) / BWAVES, 256 * std::max(1, SHADE_BWPE * 4 / BWAVES));
-    static_assert(256 * (SHADE_BWPE * 4 / BWAVES > 1 ? SHADE_BWPE * 4 / BWAVES : 1) <= SVGIR_SHADE_RATIO_WORK, "one partial sum per workgroup");
+    if (int rc = shade_bwd_lds_opt_in<LIGHT_TEX>()) return rc;
+    const int blocks = shade_bwd_blocks(p->P);
     stage_mark(tm, "shade_bwd_prologue");
-    if (ratio) hipLaunchKernelGGL(shade_bwd_kernel<true>, dim3(blocks), dim3(BWAVES * 64), lds, s, a, env_in_lds);
-    else hipLaunchKernelGGL(shade_bwd_kernel<false>, dim3(blocks), dim3(BWAVES * 64), lds, s, a, env_in_lds);
+    launch_shade_bwd<LIGHT_TEX>(a, blocks, lds, false, env_in_lds, s);
     stage_mark(tm, "shade_bwd");
     hipLaunchKernelGGL(env_grad_kernel, dim3((ntex + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, p->env, env_grad_work,
                        dL_denv, ntex, p->env_softplus, a.ratio_part, blocks, dL_dradiance_ratio);
     stage_mark(tm, "shade_env_grad");
     if (dL_dviewdirs) {   // the view-direction pass: the same grid; the sample and surfel records only (no env image)
-        if (ratio) hipLaunchKernelGGL((shade_bwd_kernel<true, true>), dim3(blocks), dim3(BWAVES * 64), BWAVES * per_wave, s, a, 0);
-        else hipLaunchKernelGGL((shade_bwd_kernel<false, true>), dim3(blocks), dim3(BWAVES * 64), BWAVES * per_wave, s, a, 0);
+        launch_shade_bwd<LIGHT_TEX>(a, blocks, rec_lds, true, 0, s);
         stage_mark(tm, "shade_bwd_view");
     }
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;

@@ -82,6 +82,8 @@ CASES = [
     _case("P17-Ns384-M128-eval", 17, 384, 128, mode=False),
     _case("P65-Ns64-M128-train-lattice-ratio", 65, 64, 128, mode=True, lattice=True, ratio=1.21),
     _case("P33-Ns24-M32-view-train", 33, 24, 32, mode=True, view=True),
+    # the two instantiations no row above reaches: the wide forward with a ratio, the view pass with a ratio (P: no multiple of 4, 12, 16, 64)
+    _case("P67-Ns129-M5-ratio-view", 67, 129, 5, ratio=0.83, view=True),
     _case("signs-and-zeros", 33, 24, 8, special="signs"),
     _case("sharp-on-axis", 17, 16, 4, special="sharp"),
     _case("clamp64", 33, 24, 5, special="clamp"),
