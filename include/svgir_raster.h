@@ -683,6 +683,50 @@ size_t svgir_albedo_scale_partials(int32_t W, int32_t H);
 int svgir_albedo_scale(int32_t W, int32_t H, const float* render_albedo, const float* gt_albedo, int32_t gt_srgb, double* partial,
                        float* scale3, int32_t* count, void* stream);
 
+/* LPIPS with the VGG16 backbone (lpipsPyTorch/modules/{lpips,networks,utils}.py as called with net_type='vgg' at train.py:398,
+ * eval_nvs.py:81, eval_relighting_tensoIR.py:370/375), forward only, fp32 throughout, fused in csrc/lpips.hip: a stem (operands composed
+ * on load, z-score, conv1_1), twelve 3 x 3 convolutions as implicit GEMM on the fp32-input MFMA, four 2 x 2 max pools, five tap kernels
+ * and one reduction -- 23 launches per call, whatever n_pairs is.  No entry point waits for the device, allocates or uses atomics; two
+ * runs give the same bits, and the result does not depend on what the workspace held before.
+ *
+ * THE NETWORK.  svgir_lpips_pack turns torch's tensors (device fp32, contiguous) into the kernels' layout, once: conv_w[l] [Cout,Cin,3,3]
+ * and conv_b[l] [Cout] of the thirteen convolutions of torchvision's vgg16().features in order (features.0, 2, 5, 7, 10, 12, 14, 17, 19, 21,
+ * 24, 26, 28), lin_w[k] [C_k] of the five 1 x 1 layers (C_k = 64, 128, 256, 512, 512).  conv_w / conv_b / lin_w are HOST arrays of device
+ * pointers read during the call.  packed: svgir_lpips_packed_floats floats of device memory, 16-byte aligned.
+ *
+ * THE ARITHMETIC, per image (image 2 p is operand a of pair p, image 2 p + 1 operand b; an image's bits depend on its own pixels only, not
+ * on its position in the call nor on the other images, so a pair of equal images scores exactly 0 and a pair scores the same alone or
+ * among four):
+ *   x    = the plane operand (above), used as given: no rescale to [-1, 1]
+ *   z    = (x - mean_c) / std_c            mean = -0.030, -0.088, -0.188; std = 0.458, 0.448, 0.450; the correctly rounded fp32 division
+ *   conv = 3 x 3, zero padding 1 applied to z (not to x); per output one fmaf chain over (input channel, ky, kx) for every 64 input channels,
+ *          the chains added in channel order, the bias last, then ReLU -- an order that depends on the layer's shape only
+ *   pool = 2 x 2 / stride 2 maximum, floor sizes, after relu1_2, relu2_2, relu3_3, relu4_3 (never after relu5_3)
+ * NaN propagates as in torch: relu(NaN) = NaN, a pooled NaN stays NaN; a non-finite input pixel gives a NaN score.
+ *   tap_k, k = 0 ... 4, from f = relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 BEFORE the pool, per pixel, all fp32, no contraction:
+ *          n   = sqrt(sum_c f_c^2)                      for a and for b
+ *          u_c = f_c / (n + 1e-10)                      (an all-zero vector gives zeros, not NaN)
+ *          s   = sum_c w_kc * ((ua_c - ub_c) * (ua_c - ub_c))
+ *          tap_k = (float)(the mean of s over the H_k W_k pixels, summed in double in a fixed order)
+ *   score = (float)((((tap_0 + tap_1) + tap_2) + tap_3) + tap_4), the taps as doubles
+ *   work      svgir_lpips_work_bytes bytes of device scratch, 16-byte aligned: two activation buffers of [2 n_pairs][H][W][64] floats
+ *             (channels-contiguous) and the workgroup records
+ *   taps      [n_pairs][5] device floats; score [n_pairs] device floats; every element is written
+ *   tap_maps  NULL, or a HOST array of five device pointers: tap k's feature maps f as [2 n_pairs, C_k, H_k, W_k] floats (NCHW, H_k =
+ *             H >> k, W_k = W >> k), written completely; for tests (five more launches)
+ * `pairs` is a HOST array read during the call.  n_pairs outside 1 ... SVGIR_METRIC_MAX_TERMS, W or H below 16 (relu5_3 would be empty;
+ * torch raises there too), a NULL src, fill without mask, a NULL or misaligned packed / work, a NULL taps / score / tap_maps entry: -1 and a
+ * message before any HIP call.  svgir_lpips_work_bytes returns 0 for arguments the call would refuse.
+ * Unpinned by the published weights: the arithmetic is tested against torch with seeded weights of the same shapes. */
+typedef struct svgir_lpips_pair {
+    svgir_plane_op a, b;
+} svgir_lpips_pair;
+size_t svgir_lpips_packed_floats(void);
+int svgir_lpips_pack(const float* const conv_w[13], const float* const conv_b[13], const float* const lin_w[5], float* packed, void* stream);
+size_t svgir_lpips_work_bytes(int32_t W, int32_t H, int32_t n_pairs);
+int svgir_lpips(int32_t W, int32_t H, int32_t n_pairs, const svgir_lpips_pair* pairs, const float* packed, void* work, float* taps,
+                float* score, float* const* tap_maps, void* stream);
+
 /* The model's activation getters, fused (scene/gaussian_model.py:104-125, 270-355: get_scaling, get_rotation, get_opacity, get_geo_normal,
  * get_shading_normal, get_base_color / get_albedo, get_roughness; gaussian_renderer/svgss.py:109: viewdirs; svgss.py:316: the regulariser
  * mse_loss(_normal, 0)): the step from the optimizer's raw parameters to what the shading and the rasterizer consume, one forward launch

@@ -21,6 +21,7 @@
 //                        one workgroup; the result stays on the device.
 // No atomics, no host wait.
 #include "common.hpp"
+#include "plane_op.hpp"
 #include "srgb.hpp"
 #include "ssim_tile.hpp"
 
@@ -31,23 +32,6 @@ int report_error(int code, const char* fmt, ...);   // api.hip
 namespace {
 
 constexpr int VM_REC = 3;                             // doubles per workgroup record: sum d^2, sum |d|, sum of the SSIM map
-
-// element i of channel c of a plane operand; N = H W.  No contraction: plain operators under the pragma (__fmul_rn / __fadd_rn are
-// operators in a header to the compiler and are fused like any other, csrc/knn.hip); srgb() keeps the arithmetic it has everywhere else.  SRGB = false: for callers
-// that have refused sRGB operands on the host (no powf in their code)
-template <bool SRGB = true>
-__device__ __forceinline__ float compose(const svgir_plane_op& p, int c, size_t N, size_t i) {
-#pragma clang fp contract(off)
-    float x = p.src[(size_t)c * N + i];
-    if (p.scale != 1.f || p.offset != 0.f) x = (x * p.scale) + p.offset;
-    if (p.mask) {
-        const float m = p.mask[i];
-        const float f = p.fill ? p.fill[(size_t)c * N + i] : p.bg[c];
-        x = (x * m) + ((1.f - m) * f);
-    }
-    if (SRGB && p.srgb) x = srgb(x);
-    return x;
-}
 
 struct MetricArgs {
     int W, H;
@@ -208,12 +192,6 @@ __global__ void __launch_bounds__(256) albedo_scale_reduce_kernel(const double* 
         for (int c = 0; c < 3; c++) scale3[c] = (float)(v[c] / v[3]);   // empty selection: 0 / 0 = NaN, torch's mean of nothing
         count[0] = (int32_t)v[3];
     }
-}
-
-const char* check_op(const svgir_plane_op& p) {
-    if (!p.src) return "an operand has no src";
-    if (p.fill && !p.mask) return "an operand has a fill plane but no mask";
-    return nullptr;
 }
 
 }  // namespace

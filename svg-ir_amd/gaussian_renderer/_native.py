@@ -128,6 +128,11 @@ class MetricTerm(C.Structure):
     _fields_ = [("a", PlaneOp), ("b", PlaneOp), ("want_ssim", C.c_int32)]
 
 
+class LpipsPair(C.Structure):
+    """svgir_lpips_pair: the two operands of one pair of svgir_lpips."""
+    _fields_ = [("a", PlaneOp), ("b", PlaneOp)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -211,6 +216,15 @@ def _load():
     lib.svgir_albedo_scale_partials.argtypes = [C.c_int32] * 2
     lib.svgir_albedo_scale.restype = C.c_int
     lib.svgir_albedo_scale.argtypes = [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 4
+    # LPIPS (svgir_harness/metrics.py): host arrays of device pointers, device pointers, stream
+    lib.svgir_lpips_packed_floats.restype = C.c_size_t
+    lib.svgir_lpips_packed_floats.argtypes = []
+    lib.svgir_lpips_pack.restype = C.c_int
+    lib.svgir_lpips_pack.argtypes = [C.POINTER(C.c_void_p)] * 3 + [C.c_void_p] * 2
+    lib.svgir_lpips_work_bytes.restype = C.c_size_t
+    lib.svgir_lpips_work_bytes.argtypes = [C.c_int32] * 3
+    lib.svgir_lpips.restype = C.c_int
+    lib.svgir_lpips.argtypes = [C.c_int32] * 3 + [C.POINTER(LpipsPair)] + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p), C.c_void_p]
     # the spherical-Gaussian direct light (gaussian_renderer/shading.py): the light block, device pointers, stream
     lib.svgir_sg_grad_work_bytes.restype = C.c_size_t
     lib.svgir_sg_grad_work_bytes.argtypes = [C.c_int32]
@@ -255,7 +269,7 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_view_metrics_partials", "svgir_view_metrics", "svgir_capture_u8", "svgir_albedo_scale_partials", "svgir_albedo_scale",
            "svgir_sg_grad_work_bytes", "svgir_sg_eval", "svgir_shade_forward_sg", "svgir_shade_backward_sg",
            "svgir_sg_eval_backward", "svgir_env_backdrop_sg", "svgir_radiance_loss_sg_work_bytes", "svgir_radiance_loss_forward_sg",
-           "svgir_radiance_loss_backward_sg")
+           "svgir_radiance_loss_backward_sg", "svgir_lpips_packed_floats", "svgir_lpips_pack", "svgir_lpips_work_bytes", "svgir_lpips")
 
 
 _scope = threading.local()

@@ -214,3 +214,126 @@ def relighting_frame(render_pkg, gt_image, gt_albedo, gt_normal, mask, bg, captu
                          (plane(render_pkg["base_color"]), plane(gt_albedo, mask=mask, bg=bg, srgb=True), True),
                          (seen("normal"), plane(gt_normal, mask=mask, bg=bg), False)])
     return images, rows
+
+
+# ---- LPIPS (csrc/lpips.hip) ------------------------------------------------------------------------------------------------------------
+VGG_CONV_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)   # the convolutions of torchvision's vgg16().features up to relu5_3
+VGG_CONV_SHAPE = ((64, 3), (64, 64), (128, 64), (128, 128), (256, 128), (256, 256), (256, 256), (512, 256), (512, 512), (512, 512),
+                  (512, 512), (512, 512), (512, 512))               # (Cout, Cin)
+LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)                       # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+LPIPS_MIN_SIZE = 16
+
+
+def _state(s, what):
+    if isinstance(s, (str, bytes)) or hasattr(s, "__fspath__"):
+        s = torch.load(s, map_location="cpu", weights_only=True)
+    if not hasattr(s, "keys"):
+        raise TypeError(f"LPIPS: {what} must be a state dict or a path to one, got {type(s).__name__}")
+    return s
+
+
+def _pick(state, names, shape, what, squeeze=False):
+    """state[first of `names` present], which must have exactly `shape` (squeeze: after dropping dimensions of size 1)."""
+    for k in names:
+        if k in state:
+            t = state[k].detach()
+            got = tuple(d for d in t.shape if d != 1) if squeeze else tuple(t.shape)
+            if got != tuple(shape):
+                raise ValueError(f"LPIPS: {what} '{k}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
+            return t.reshape(shape)
+    raise KeyError(f"LPIPS: {what} has none of the keys {names}")
+
+
+class LPIPS:
+    """lpipsPyTorch's `LPIPS('vgg')` on the HIP kernels.  vgg_state: the state dict of torchvision's vgg16 (keys `features.N.weight` /
+    `.bias`) or of its `.features` (`N.weight`), or a path to one; lin_state: the LPIPS linear layers as published (`linK.model.1.weight`)
+    or as lpipsPyTorch renames them (`K.1.weight`), or a path.  Nothing is downloaded.  The weights are packed once per device, on first
+    use there.  `net(x, y)`: x, y [3,H,W] or [1,3,H,W] device tensors in [0, 1] -> the reference's [1,1,1,1] fp32 device tensor."""
+
+    def __init__(self, vgg_state, lin_state):
+        vgg, lin = _state(vgg_state, "vgg_state"), _state(lin_state, "lin_state")
+        self._w, self._b, self._lin = [], [], []
+        for i, (co, ci) in zip(VGG_CONV_INDEX, VGG_CONV_SHAPE):
+            self._w.append(_pick(vgg, (f"features.{i}.weight", f"{i}.weight"), (co, ci, 3, 3), "vgg_state").to("cpu", torch.float32))
+            self._b.append(_pick(vgg, (f"features.{i}.bias", f"{i}.bias"), (co,), "vgg_state").to("cpu", torch.float32))
+        for k, c in enumerate(LPIPS_TAP_CHANNELS):
+            self._lin.append(_pick(lin, (f"lin{k}.model.1.weight", f"{k}.1.weight"), (c,), "lin_state", squeeze=True).to("cpu", torch.float32))
+        self._packed = {}
+
+    def packed(self, dev):
+        """The kernels' weight block on `dev` (packed on first use)."""
+        dev = torch.device(dev)
+        if dev.type != "cuda":
+            raise RuntimeError("LPIPS: the kernels run on the GPU only (libsvgir_raster.so has no CPU path)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if dev not in self._packed:
+            with torch.cuda.device(dev):
+                src = [t.to(dev).contiguous() for t in self._w + self._b + self._lin]
+                arrs = []
+                for part in (src[:13], src[13:26], src[26:]):
+                    arrs.append((C.c_void_p * len(part))(*[t.data_ptr() for t in part]))
+                out = N.out_tensor((N.lib.svgir_lpips_packed_floats(),), torch.float32, dev)
+                N.check(N.lib.svgir_lpips_pack(arrs[0], arrs[1], arrs[2], out.data_ptr(), N.stream_ptr(dev)), "lpips_pack")
+                for t in src:   # the pack kernels read them on this stream after we return
+                    t.record_stream(torch.cuda.current_stream(dev))
+            self._packed[dev] = out
+        return self._packed[dev]
+
+    def __call__(self, x, y):
+        return lpips_terms(self, [(_image3(x, "x"), _image3(y, "y"))]).reshape(1, 1, 1, 1)
+
+
+def _image3(t, what):
+    """[3,H,W] from a [3,H,W] or [1,3,H,W] device tensor."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"lpips: {what} must be a tensor, got {type(t).__name__}")
+    if t.dim() == 4:
+        if t.shape[0] != 1:
+            raise ValueError(f"lpips: {what} has a batch of {t.shape[0]}; one image per call (the reference sums a batch into one number, "
+                             f"which is not reproduced) -- use metrics.lpips_terms for several pairs")
+        t = t[0]
+    if t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError(f"lpips: {what} must be [3,H,W] or [1,3,H,W], got {tuple(t.shape)}")
+    _gpu(t, what)
+    return t
+
+
+def lpips_terms(net, pairs, out=None, with_taps=False, tap_maps=False):
+    """LPIPS scores of up to 4 pairs of one image size from one batched pass (23 launches whatever the count).  pairs: [(a, b)], a / b a
+    `plane(...)` operand or a plain [3,H,W] device tensor, values as the reference passes them (in [0, 1]).  Returns float32 [n] on the
+    device (`out`: a contiguous float32 [n] device view to write instead); with_taps=True: (scores, taps [n,5]), the per-layer terms whose
+    sum the score is; tap_maps=True (tests): additionally the five tapped feature maps, [2 n, C_k, H_k, W_k] each, image 2 p = a of pair p.
+    A pair's bits do not depend on the other pairs of the call."""
+    pairs = list(pairs)
+    n = len(pairs)
+    if not 1 <= n <= MAX_TERMS:
+        raise ValueError(f"lpips_terms: {n} pairs given, 1 ... {MAX_TERMS} per call")
+    ops = [(_as_plane(a), _as_plane(b)) for a, b in pairs]
+    H, W, dev = _same_size([p for pair in ops for p in pair], "lpips_terms")
+    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+        raise ValueError(f"lpips_terms: image {H} x {W} is smaller than {LPIPS_MIN_SIZE} x {LPIPS_MIN_SIZE}: relu5_3 would be empty")
+    arr = (N.LpipsPair * n)()
+    for k, (a, b) in enumerate(ops):
+        _fill_op(arr[k].a, a)
+        _fill_op(arr[k].b, b)
+    packed = net.packed(dev)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = N.out_tensor((n,), torch.float32, dev)
+        elif out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (n,) or not out.is_contiguous():
+            raise ValueError(f"lpips_terms: out must be a contiguous float32 [{n}] tensor on {dev}")
+        taps = N.out_tensor((n, 5), torch.float32, dev)
+        work = N.out_tensor((N.lib.svgir_lpips_work_bytes(W, H, n) // 4,), torch.float32, dev)
+        maps, mp = None, None
+        if tap_maps:
+            maps = [N.out_tensor((2 * n, c, H >> k, W >> k), torch.float32, dev) for k, c in enumerate(LPIPS_TAP_CHANNELS)]
+            mp = (C.c_void_p * 5)(*[m.data_ptr() for m in maps])
+        N.check(N.lib.svgir_lpips(W, H, n, arr, packed.data_ptr(), work.data_ptr(), taps.data_ptr(), out.data_ptr(), mp,
+                                  N.stream_ptr(dev)), "lpips")
+    res = (out,)
+    if with_taps:
+        res += (taps,)
+    if tap_maps:
+        res += (maps,)
+    return res[0] if len(res) == 1 else res
