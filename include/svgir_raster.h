@@ -683,6 +683,59 @@ size_t svgir_albedo_scale_partials(int32_t W, int32_t H);
 int svgir_albedo_scale(int32_t W, int32_t H, const float* render_albedo, const float* gt_albedo, int32_t gt_srgb, double* partial,
                        float* scale3, int32_t* count, void* stream);
 
+/* The exact per-column LOWER MEDIAN of an fp32 view x [n, C], C = 1 ... 4, x[i, c] = base[i * row_stride + c * col_stride] (strides in
+ * elements: row_stride = C, col_stride = 1 is a row-major [n, C]; row_stride = 1, col_stride = n a planar [C, n]): the contract of
+ * torch.median(x, dim=0), by radix select in csrc/select.hip -- four 8-bit digit passes over order-preserving uint32 keys, a pass over the
+ * rows for the index and one single-workgroup finish: one memset and 6 launches whatever n is.  No host wait, no allocation, integer
+ * atomics only: two runs give the same bits, and nothing depends on what `scratch` held before.
+ *   values    [C] device floats: the element of rank (n - 1) / 2 (0-based, integer division) of each column, bit for bit an element of
+ *             the column.  DECISIONS (torch leaves them open or differs): -0 and +0 are one value and come out as +0; a column with at
+ *             least one NaN gives NaN (as torch); +-inf are ordinary values; n == 0 gives NaN, index -1 and counts 0 (torch raises).
+ *   indices   [C] device int32: the SMALLEST row whose value equals the median (torch leaves the choice among ties unspecified); in a
+ *             NaN column the smallest row that holds a NaN.
+ *   n_less, n_greater   [C] device int32 each, or NULL: the rows strictly below / strictly above the median value, exact.  They are counted
+ *             on the keys, where NaN stands above +inf: in a NaN column n_less is the number of rows that are not NaN, n_greater 0.
+ *   scratch   svgir_column_median_scratch_bytes(n, C) bytes of device memory, 4-byte aligned (0 for arguments the call refuses).
+ * C outside 1 ... 4, n < 0 or n >= 2^31, a NULL values / indices, a NULL base / scratch with n > 0: -1 and a message before any HIP call. */
+size_t svgir_column_median_scratch_bytes(int64_t n, int32_t C);
+int svgir_column_median(const float* base, int64_t n, int32_t C, int64_t row_stride, int64_t col_stride, void* scratch, float* values,
+                        int32_t* indices, int32_t* n_less, int32_t* n_greater, void* stream);
+
+/* The albedo scale the relighting eval APPLIES (eval_relighting_tensoIR.py:227-237; svgir_albedo_scale above is the variant of :285-294,
+ * which the reference computes and never uses): per pixel, fp32 in torch's operation order, every operation rounded on its own,
+ *   r_c = srgb_to_rgb(render_albedo[c]) when render_srgb != 0, else render_albedo[c]
+ *         srgb_to_rgb (utils/graphics_utils.py:218-229): x <= 0.04045 ? x / 12.92 : powf((x + 0.055) / 1.055, 2.4); NaN stays NaN
+ *   the pixel is selected iff ((r_0 + r_1) + r_2) / 3 > 0
+ *   key_c = clamp(gt_albedo[c] / r_c, lo, hi), the clamp passing NaN: x / 0 = inf becomes hi, 0 / 0 makes that channel's scale NaN and no other
+ * and scale3[c] = the lower median of key_c over the selected pixels by the selection of svgir_column_median (same rules for zeros and
+ * NaN), the keys recomputed in each of its four passes: one memset and 5 launches.  render_albedo, gt_albedo: [3,H,W] contiguous device
+ * floats.  The eval uses lo = 1e-6, hi = 10.
+ *   scale3    3 device floats; count: 1 device int32, the number of selected pixels.  An empty selection gives NaN and 0.  scale3 can be
+ *             handed on as svgir_activation.base_color_scale without visiting the host.
+ *   scratch   svgir_albedo_scale_median_scratch_bytes(W, H) bytes of device memory, 4-byte aligned
+ * A NULL pointer, W or H <= 0, W * H >= 2^31, lo > hi (or a NaN bound): -1 and a message before any HIP call. */
+size_t svgir_albedo_scale_median_scratch_bytes(int32_t W, int32_t H);
+int svgir_albedo_scale_median(int32_t W, int32_t H, const float* render_albedo, const float* gt_albedo, int32_t render_srgb, float lo, float hi,
+                              void* scratch, float* scale3, int32_t* count, void* stream);
+
+/* Stage 1's lambda_surface term (gaussian_renderer/render.py:217-222): loss = exp(-mean |xyz - median(xyz, dim=0)|), xyz [P,3] contiguous
+ * device floats.  (svgir_geometry_loss_* holds the cos term the harness calls surface_loss; this is the other one.)
+ *   partials: the number of DOUBLES `partial` must hold: the selection's scratch, then one record per 2048 rows.
+ *   forward : the median c of svgir_column_median (its rules: a NaN coordinate makes c_c NaN), then the fp32 values |x_ic - c_c| summed in
+ *             double in a fixed order (wave butterfly, the four waves in order, the workgroup records in order): one memset and 6 launches.
+ *             `stats` [11] device doubles = {sum, 3 P, then per column c: index_c, n_less_c, n_greater_c}; `loss` 1 device float =
+ *             float32(exp(-sum / (3 P))), the exp in double.  No float atomics: two runs give the same bits.
+ *   backward: `stats` as the forward wrote it; `g` 1 device float the host never reads.  dL_dxyz [P,3] is written completely by one
+ *             elementwise launch without atomics: -g L sign(x_ic - c_c) / (3 P) with sign(0) = 0, and in row index_c of column c
+ *             additionally +g L (n_greater_c - n_less_c) / (3 P): torch's subgradient of median, which hands the gradient of `center`
+ *             to the row it returned (here: the smallest such row).  Evaluated in double from L = the fp32 loss, rounded once.
+ *             A NaN anywhere in xyz makes the loss and every element of dL_dxyz NaN, as in torch.
+ * P == 0: the loss is NaN and nothing else is written (torch raises).  P < 0 or P >= 2^31, a NULL stats / loss, any other NULL pointer with
+ * P > 0: -1 and a message before any HIP call. */
+size_t svgir_surface_center_loss_partials(int64_t P);
+int svgir_surface_center_loss_forward(int64_t P, const float* xyz, double* partial, double* stats, float* loss, void* stream);
+int svgir_surface_center_loss_backward(int64_t P, const float* xyz, const double* stats, const float* g, float* dL_dxyz, void* stream);
+
 /* LPIPS with the VGG16 backbone (lpipsPyTorch/modules/{lpips,networks,utils}.py as called with net_type='vgg' at train.py:398,
  * eval_nvs.py:81, eval_relighting_tensoIR.py:370/375), forward only, fp32 throughout, fused in csrc/lpips.hip: a stem (operands composed
  * on load, z-score, conv1_1), twelve 3 x 3 convolutions as implicit GEMM on the fp32-input MFMA, four 2 x 2 max pools, five tap kernels

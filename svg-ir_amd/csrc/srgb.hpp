@@ -22,6 +22,15 @@ __device__ __forceinline__ float dsrgb(float x) {
     if (!(y >= 0.f && y <= 1.f)) return 0.f;
     return x > 0.0031308f ? (1.055f / 2.4f) * powf(x, 1.0f / 2.4f - 1.0f) : 12.92f;
 }
+
+// `srgb_to_rgb` (utils/graphics_utils.py:218-229): x <= 0.04045 ? x / 12.92 : pow((max(x, 0.04045) + 0.055) / 1.055, 2.4), every
+// operation rounded on its own in fp32.  On the pow side of the compare max(x, 0.04045) is x itself.  NaN: `<=` is false, torch.where
+// takes the pow branch, whose max and pow propagate it: NaN.  No clip: the reference has none here.
+__device__ __forceinline__ float srgb_to_rgb(float x) {
+#pragma clang fp contract(off)
+    if (x <= 0.04045f) return __fdiv_rn(x, 12.92f);
+    return powf(__fdiv_rn(x + 0.055f, 1.055f), 2.4f);
+}
 #endif
 
 }  // namespace svgir

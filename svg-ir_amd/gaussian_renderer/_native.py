@@ -216,6 +216,21 @@ def _load():
     lib.svgir_albedo_scale_partials.argtypes = [C.c_int32] * 2
     lib.svgir_albedo_scale.restype = C.c_int
     lib.svgir_albedo_scale.argtypes = [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 4
+    # the exact column median and its consumers (svgir_harness/metrics.py, losses.py): sizes / strides, device pointers, stream
+    lib.svgir_column_median_scratch_bytes.restype = C.c_size_t
+    lib.svgir_column_median_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.svgir_column_median.restype = C.c_int
+    lib.svgir_column_median.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64] + [C.c_void_p] * 6
+    lib.svgir_albedo_scale_median_scratch_bytes.restype = C.c_size_t
+    lib.svgir_albedo_scale_median_scratch_bytes.argtypes = [C.c_int32] * 2
+    lib.svgir_albedo_scale_median.restype = C.c_int
+    lib.svgir_albedo_scale_median.argtypes = [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] + [C.c_float] * 2 + [C.c_void_p] * 4
+    lib.svgir_surface_center_loss_partials.restype = C.c_size_t
+    lib.svgir_surface_center_loss_partials.argtypes = [C.c_int64]
+    lib.svgir_surface_center_loss_forward.restype = C.c_int
+    lib.svgir_surface_center_loss_forward.argtypes = [C.c_int64] + [C.c_void_p] * 5
+    lib.svgir_surface_center_loss_backward.restype = C.c_int
+    lib.svgir_surface_center_loss_backward.argtypes = [C.c_int64] + [C.c_void_p] * 5
     # LPIPS (svgir_harness/metrics.py): host arrays of device pointers, device pointers, stream
     lib.svgir_lpips_packed_floats.restype = C.c_size_t
     lib.svgir_lpips_packed_floats.argtypes = []
@@ -269,7 +284,9 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_view_metrics_partials", "svgir_view_metrics", "svgir_capture_u8", "svgir_albedo_scale_partials", "svgir_albedo_scale",
            "svgir_sg_grad_work_bytes", "svgir_sg_eval", "svgir_shade_forward_sg", "svgir_shade_backward_sg",
            "svgir_sg_eval_backward", "svgir_env_backdrop_sg", "svgir_radiance_loss_sg_work_bytes", "svgir_radiance_loss_forward_sg",
-           "svgir_radiance_loss_backward_sg", "svgir_lpips_packed_floats", "svgir_lpips_pack", "svgir_lpips_work_bytes", "svgir_lpips")
+           "svgir_radiance_loss_backward_sg", "svgir_lpips_packed_floats", "svgir_lpips_pack", "svgir_lpips_work_bytes", "svgir_lpips",
+           "svgir_column_median_scratch_bytes", "svgir_column_median", "svgir_albedo_scale_median_scratch_bytes", "svgir_albedo_scale_median",
+           "svgir_surface_center_loss_partials", "svgir_surface_center_loss_forward", "svgir_surface_center_loss_backward")
 
 
 _scope = threading.local()

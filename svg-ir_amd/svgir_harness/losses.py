@@ -4,7 +4,8 @@ utils/loss_utils.py:21-64), one kernel forward, one backward; and the radiance-c
 around the irradiance kernel of csrc/irradiance.hip, and the same loss fused end to end (`fused_radiance_loss`); and the geometry terms of both stages (`cos_loss`, `surface_loss`, `mask_loss`,
 `mask_entropy_loss`, `geometry_losses`: gaussian_renderer/render.py:157-188, svgss.py:297-313, 333-338), fused in csrc/geom_loss.hip; and the
 edge-aware smoothness and TV terms (`first_order_edge_aware_loss`, `second_order_edge_aware_loss`, `tv_loss`, `smoothness_losses`:
-utils/loss_utils.py:101-117; svgss.py:366-399, render.py:192-196), fused in csrc/smooth_loss.hip."""
+utils/loss_utils.py:101-117; svgss.py:366-399, render.py:192-196), fused in csrc/smooth_loss.hip; and stage 1's lambda_surface term
+(`surface_center_loss`: render.py:217-222) on the exact median of csrc/select.hip."""
 import ctypes as C
 
 import torch
@@ -317,6 +318,59 @@ def mask_entropy_loss(opacity, mask):
     """-(mask * log(o) + (1 - mask) * log(1 - o)).mean() with o = opacity.clamp(1e-6, 1 - 1e-6) (render.py:184-186, svgss.py:333-336).
     Differentiable in `opacity`."""
     return geometry_losses(opacity=opacity, mask=mask, terms=("entropy",))["entropy"]
+
+
+# ---- lambda_surface (csrc/select.hip) -----------------------------------------------------------------------------------------------
+SURFACE_CENTER_STATS = 11   # sum, 3 P, then {index, n_less, n_greater} per column
+
+
+class _SurfaceCenterLoss(torch.autograd.Function):
+    """exp(-mean |xyz - median(xyz, dim=0)|) as ONE node: the selection and one fixed-order reduction forward, one elementwise launch
+    backward.  Returns the loss (a 0-d fp32 device tensor) and the kernels' stats [11] (doubles)."""
+
+    @staticmethod
+    def forward(ctx, xyz):
+        dev = xyz.device
+        if dev.type != "cuda":
+            raise RuntimeError("surface_center_loss: tensors must live on the GPU (libsvgir_raster.so has no CPU path)")
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"surface_center_loss: xyz must be [P,3], got {tuple(xyz.shape)}")
+        x = N.f32c(xyz.detach(), dev)
+        P = int(x.shape[0])
+        with torch.cuda.device(dev):
+            partial = N.out_tensor((max(N.lib.svgir_surface_center_loss_partials(P), 1),), torch.float64, dev)
+            stats = N.out_tensor((SURFACE_CENTER_STATS,), torch.float64, dev)
+            loss = N.out_tensor((1,), torch.float32, dev)
+            N.check(N.lib.svgir_surface_center_loss_forward(P, N.ptr(x), partial.data_ptr(), stats.data_ptr(), loss.data_ptr(),
+                                                            N.stream_ptr(dev)), "surface_center_loss forward")
+        ctx.save_for_backward(x, stats)
+        ctx.shape = tuple(xyz.shape)
+        ctx.mark_non_differentiable(stats)
+        return loss[0], stats
+
+    @staticmethod
+    def backward(ctx, g, _g_stats):
+        x, stats = ctx.saved_tensors
+        dev = x.device
+        P = int(x.shape[0])
+        out = N.out_tensor((P, 3), torch.float32, dev)
+        if P:
+            gdev = g.to(torch.float32).reshape(1).contiguous()   # the upstream scalar stays on the device
+            with torch.cuda.device(dev):
+                N.check(N.lib.svgir_surface_center_loss_backward(P, x.data_ptr(), stats.data_ptr(), gdev.data_ptr(), out.data_ptr(),
+                                                                 N.stream_ptr(dev)), "surface_center_loss backward")
+        return out.reshape(ctx.shape)
+
+
+def surface_center_loss(xyz, with_stats=False):
+    """Stage 1's lambda_surface term (gaussian_renderer/render.py:217-222): torch.exp(-(xyz - torch.median(xyz, dim=0)[0][None]).abs().mean())
+    for xyz [P,3], on the exact median of csrc/select.hip (`metrics.column_median`: its rules for ties, zeros and NaN).  Differentiable in
+    xyz: every element gets -L sign(x - c) / (3 P), and the median's own row of each column the gradient of `center` on top, as torch's
+    median hands it to the row it returned.  A NaN coordinate makes the loss and every gradient NaN, as in torch; P == 0 gives NaN.
+    with_stats=True returns (loss, stats), stats the device tensor [11] (float64) {sum, 3 P, then index, n_less, n_greater per column}.
+    (`surface_loss` above is the cos term of render.py:158-160; the two share only the reference's word "surface".)"""
+    loss, stats = _SurfaceCenterLoss.apply(xyz)
+    return (loss, stats) if with_stats else loss
 
 
 # ---- edge-aware smoothness and TV terms (csrc/smooth_loss.hip) ------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """The tail of an eval view, fused (csrc/view_metrics.hip): MSE / PSNR / SSIM / L1 rows of composed image pairs (`view_metrics`, the
 drop-ins `mse` and `psnr` for utils/image_utils.py:32-37), the 8-bit arrays that get written as images (`captures_u8`: what torchvision's
-save_image hands to PIL), the albedo scale of the relighting eval (`albedo_scale`: eval_relighting_tensoIR.py:285-294) and the whole tail
-of one relighting frame (`relighting_frame`: :333-378).  Nothing here waits for the device: every result is a device tensor, a metrics row
+save_image hands to PIL), the albedo scale of the relighting eval (`albedo_scale`: eval_relighting_tensoIR.py:285-294, the variant the
+reference never uses; `albedo_scale_median`: :227-237, the one it applies, on the exact median of csrc/select.hip, which `column_median`
+exposes as a drop-in for torch.median(x, dim=0)) and the whole tail of one relighting frame (`relighting_frame`: :333-378).  Nothing here waits for the device: every result is a device tensor, a metrics row
 can be written straight into row v of the [views, terms, 10] table that `view_parallel.run_views` gathers at the end."""
 import ctypes as C
 
@@ -181,6 +182,54 @@ def albedo_scale(render_albedo, gt_albedo, gt_srgb=False):
         count = N.out_tensor((1,), torch.int32, dev)
         N.check(N.lib.svgir_albedo_scale(W, H, r.data_ptr(), g.data_ptr(), int(bool(gt_srgb)), partial.data_ptr(), scale.data_ptr(),
                                          count.data_ptr(), N.stream_ptr(dev)), "albedo_scale")
+    return scale, count
+
+
+SELECT_ROWS = 2048    # rows per workgroup of csrc/select.hip (SEL_ROWS = BLOCK * SEL_PER_THREAD): the tests put their sizes around it
+MEDIAN_MAX_COLUMNS = 4
+
+
+def column_median(x, with_counts=False):
+    """Drop-in for `torch.median(x, dim=0)` on a 2-D fp32 device tensor [n, C] of ANY strides, C = 1 ... 4 (a planar [C, n] goes in as
+    `planes.t()`): (values [C] fp32, indices [C] int64), both on the device, from csrc/select.hip's radix select -- no sort, no host wait.
+    The value is the lower median, bit for bit an element of the column; -0 and +0 are one value and come out as +0; a NaN in a column
+    gives NaN; the index is the SMALLEST row holding the value (torch leaves ties open), in a NaN column the first NaN row; n == 0 gives
+    NaN and -1 (torch raises).  with_counts=True adds (n_less [C], n_greater [C]) int32: the rows strictly below / above the value."""
+    x = _gpu(x, "x")
+    if x.dim() != 2 or x.dtype != torch.float32 or not 1 <= x.shape[1] <= MEDIAN_MAX_COLUMNS:
+        raise ValueError(f"column_median: x must be a 2-D float32 tensor [n, 1 ... {MEDIAN_MAX_COLUMNS}], got "
+                         f"{x.dtype} {tuple(x.shape)}")
+    dev = x.device
+    x = x.detach()
+    n, Cn = int(x.shape[0]), int(x.shape[1])
+    with torch.cuda.device(dev):
+        scratch = N.out_tensor((max(N.lib.svgir_column_median_scratch_bytes(n, Cn) // 4, 1),), torch.int32, dev)
+        values = N.out_tensor((Cn,), torch.float32, dev)
+        idx, less, greater = (N.out_tensor((Cn,), torch.int32, dev) for _ in range(3))
+        N.check(N.lib.svgir_column_median(N.ptr(x), n, Cn, x.stride(0), x.stride(1), scratch.data_ptr(), values.data_ptr(), idx.data_ptr(),
+                                          less.data_ptr(), greater.data_ptr(), N.stream_ptr(dev)), "column_median")
+    res = (values, idx.to(torch.int64))
+    return res + (less, greater) if with_counts else res
+
+
+def albedo_scale_median(render_albedo, gt_albedo, lo=1e-6, hi=10.0, render_srgb=True):
+    """eval_relighting_tensoIR.py:227-237, the albedo scale the relighting eval applies: over the pixels where
+    srgb_to_rgb(render_albedo).mean(dim=0) > 0, the per-channel MEDIAN of (gt_albedo / srgb_to_rgb(render_albedo)).clamp(lo, hi);
+    render_srgb=False takes render_albedo as it is.  Returns (scale [3] fp32, count [1] int32), both on the device: the scale goes into
+    `activations.activate(..., base_color_scale=)` as it is.  An empty selection gives NaN and 0.  (`albedo_scale` is the mean variant
+    of :285-294, which the reference computes and never uses.)"""
+    r, g = _gpu(render_albedo, "render_albedo"), _gpu(gt_albedo, "gt_albedo")
+    if r.dim() != 3 or r.shape[0] != 3 or tuple(g.shape) != tuple(r.shape):
+        raise ValueError(f"albedo_scale_median: both images must be [3,H,W] of one size, got {tuple(r.shape)} and {tuple(g.shape)}")
+    dev = r.device
+    r, g = N.f32c(r.detach(), dev), N.f32c(g.detach(), dev)
+    H, W = int(r.shape[1]), int(r.shape[2])
+    with torch.cuda.device(dev):
+        scratch = N.out_tensor((max(N.lib.svgir_albedo_scale_median_scratch_bytes(W, H) // 4, 1),), torch.int32, dev)
+        scale = N.out_tensor((3,), torch.float32, dev)
+        count = N.out_tensor((1,), torch.int32, dev)
+        N.check(N.lib.svgir_albedo_scale_median(W, H, r.data_ptr(), g.data_ptr(), int(bool(render_srgb)), float(lo), float(hi),
+                                                scratch.data_ptr(), scale.data_ptr(), count.data_ptr(), N.stream_ptr(dev)), "albedo_scale_median")
     return scale, count
 
 
