@@ -392,8 +392,7 @@ int svgir_shade_backward_view(const svgir_shade_params* p, const float* dL_dredu
  * work, a misaligned work, a non-NULL subset / subset_count (subset shading belongs to the rasterizer-fused path).
  * The bare light's gradient (svgir_sg_eval_backward), the eval backdrop (svgir_env_backdrop_sg) and the fused radiance-consistency loss
  * (svgir_radiance_loss_forward_sg / _backward_sg) follow below and next to their texture counterparts.
- * NOT provided (new work, not a switch): the shading fused into svgir_forward / svgir_backward (svgir_fused_shade carries no light
- * pointer: a struct change and an ABI bump). */
+ * The shading fused into the rasterizer calls has its twins too: svgir_forward_sg / svgir_backward_sg, behind svgir_fused_shade below. */
 #define SVGIR_SG_MAX_LOBES 128
 typedef struct svgir_sg_light {
     int32_t count;        /* M */
@@ -455,6 +454,33 @@ struct svgir_fused_shade {
     float* reduced;        /* [P,70] or NULL; rows of unshaded surfels are zero */
     int32_t all_surfels;
 };
+
+/* The fused shading under a spherical-Gaussian light (added within ABI 14: two entry points, no struct changes).  svgir_forward /
+ * svgir_backward with params->shade != NULL (required here: svgss, S / VS = 4 / 52 when sp.training, else 7 / 64) and `light` as the
+ * global light of the shading, as in svgir_shade_forward_sg / svgir_shade_backward_sg: the env* fields of params->shade->sp are ignored
+ * and may be NULL / 0, light->work is built by each call.  In svgir_grads, dL_denv receives dL_dlobes [M,7] and env_grad_work is scratch of
+ * svgir_sg_grad_work_bytes(M) bytes (both outside clear_base, as for the texture).  Everything else is what the texture calls do:
+ * all_surfels, reduced, dL_dreduced, dL_dradiance_ratio, dL_dviewdirs, out_weights, the clear_base carve-out, the working sets (the
+ * forward shades the surfels that touch a tile, or from sp.Ns >= 128 on those the contribution pre-pass finds; the backward
+ * differentiates the blended ones).
+ * Results are bit-identical to the unfused sequence svgir_shade_forward_sg -> svgir_forward and svgir_backward ->
+ * svgir_shade_backward_sg, except dL_dlobes: fp64 LDS sums per workgroup plus float atomics across workgroups, the same sum in the order
+ * of the day.  Every element of every requested output is written, dL_dlobes included; a view that blends nothing gives zero dL_dlobes
+ * and zero dL_dradiance_ratio.  Non-finite lobes give NaN in the light-dependent columns and never a fault.
+ * Rejected with SVGIR_ERR_INVALID and a message before any launch: a NULL light, count outside 1 ... SVGIR_SG_MAX_LOBES, NULL lobes / work,
+ * a misaligned work, params->shade == NULL, the rgss variant, widths that do not match sp.training, a missing dL_denv / env_grad_work /
+ * per-surfel gradient output, dL_dreduced without all_surfels.
+ * The lobe table, the lattice table and (backward) the cleared accumulator come from one small launch in front of the shading kernel; the
+ * texture path's kernels, which carry the texture's tables in passing, are untouched.
+ * Not provided: svgir_forward_batch with an SG light -- svgir_view_call has no room for one. */
+int svgir_forward_sg(const svgir_params* p, const svgir_sg_light* light, const svgir_outputs* o,
+                     svgir_alloc_fn geom, void* geom_ctx,
+                     svgir_alloc_fn binning, void* binning_ctx,
+                     svgir_alloc_fn image, void* image_ctx,
+                     void* stream);
+int svgir_backward_sg(const svgir_params* p, const svgir_sg_light* light, const svgir_grads* g, int32_t R, const int32_t* radii,
+                      char* geom_blob, char* binning_blob, size_t binning_bytes, char* image_blob,
+                      char* scratch, size_t scratch_bytes, void* stream);
 
 /* Materialises the incident-direction lattice: dirs [P,Ns,3] and / or areas [P,Ns,1] (either may be NULL), the return
  * values of the reference's fibonacci_sphere_sampling(normals, Ns, random_rotate) with `offsets` [P] standing for its

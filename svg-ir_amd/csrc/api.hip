@@ -21,6 +21,7 @@
 #include "geom_bwd.hpp"
 #include "workload_history.hpp"
 #include "depth_sort_plan.hpp"
+#include "sg_light.hpp"
 
 using namespace svgir;
 
@@ -403,6 +404,15 @@ int validate(const svgir_params* p, bool fwd) {
     return 0;
 }
 
+// svgir_forward_sg / svgir_backward_sg: the light, and that the call is a fused-shading call at all -- in front of validate(), which
+// checks the variant and the packed widths of any fused call
+int validate_sg(const svgir_params* p, const svgir_sg_light* light, const char* who) {
+    if (!p) return fail(SVGIR_ERR_INVALID, "params is NULL");
+    if (int rc = sg_light_valid(light, who)) return rc;
+    if (!p->shade) return fail(SVGIR_ERR_INVALID, "%s: params.shade is NULL (the spherical-Gaussian light belongs to the fused shading)", who);
+    return 0;
+}
+
 CapKey workload_key(const svgir_params* p) {
     int dev_id = 0;
     (void)hipGetDevice(&dev_id);
@@ -508,6 +518,7 @@ inline DepthRows geom_depth_rows(const GeomLayout& g, int P) {
 struct ForwardCall {
     const svgir_view_call c; const svgir_params* p = c.params; const svgir_outputs* o = c.outputs; hipStream_t s = (hipStream_t)c.stream;
     bool key_spec;
+    const svgir_sg_light* light = nullptr;   // svgir_forward_sg: the spherical-Gaussian light of the fused shading (else the texture of p->shade->sp)
     // set by begin()
     int P = 0, nstate = 0, fin = 0, spec_top = -1, cap = 0;
     ViewGrid v{};
@@ -519,7 +530,8 @@ struct ForwardCall {
     PinnedSlot R_pin;   // (the landing slot of the instance count, released when this call object dies)
     StageMarks tm;   // (stage_begin / stage_mark: one event per stage boundary, resolved lazily)
 
-    ForwardCall(const svgir_view_call& c_, bool key_spec_) : c(c_), key_spec(key_spec_), tm(stage_begin(s)) {}
+    ForwardCall(const svgir_view_call& c_, bool key_spec_, const svgir_sg_light* light_ = nullptr)
+        : c(c_), key_spec(key_spec_), light(light_), tm(stage_begin(s)) {}
 
     int check(const char* what) {
         hipError_t e = p->debug ? hipStreamSynchronize(s) : hipSuccess;  // reference CHECK_CUDA(debug), auxiliary.h:425-432
@@ -600,7 +612,11 @@ struct ForwardCall {
                                          // depth-sort plan, the others in no order that matters: the shading clears their rows)
                 sp.subset = depth_order; sp.subset_count = G.counters + 3;
             }
-            if (shade_forward_impl(&sp, p->shade->reduced, const_cast<float*>(p->features), const_cast<float*>(p->vfeatures), true, s) != 0)
+            if (light) {   // (the lobe and lattice tables: one small launch in front of the shading kernel; a message of its own on a bad call)
+                if (int rc = shade_forward_sg_impl(&sp, light, p->shade->reduced, const_cast<float*>(p->features), const_cast<float*>(p->vfeatures), false,
+                                                   "forward_sg", s))
+                    return rc;
+            } else if (shade_forward_impl(&sp, p->shade->reduced, const_cast<float*>(p->features), const_cast<float*>(p->vfeatures), true, s) != 0)
                 return fail(SVGIR_ERR_INVALID, "fused shading: svgir_shade_forward rejected its parameters");
             if (int rc = check("shade")) return rc;
             if (timed) stage_mark(tm, "shade");
@@ -662,7 +678,7 @@ struct ForwardCall {
         prepass = shade_subset && shade_prepass(p->shade->sp.Ns);
         pa.needed = prepass ? G.needed : nullptr;
         pa.span = G.counters + 3;
-        if (p->shade) pa.tabs = shade_tables(&p->shade->sp, nullptr, 0);   // (the preprocess launch carries the shading kernels' tables)
+        if (p->shade && !light) pa.tabs = shade_tables(&p->shade->sp, nullptr, 0);   // (the preprocess launch carries the shading kernels' tables)
         ckey = workload_key(p);
         static const bool key_spec_env = getenv("SVGIR_NO_KEY_SPEC") == nullptr;
         spec_top = (key_spec && key_spec_env) ? g_history.guess_top(ckey) : -1;
@@ -722,8 +738,8 @@ struct ForwardCall {
         return 0;
     }
 
-    static int run(const svgir_view_call& c, bool key_spec) {
-        ForwardCall f(c, key_spec);
+    static int run(const svgir_view_call& c, bool key_spec, const svgir_sg_light* light = nullptr) {
+        ForwardCall f(c, key_spec, light);
         const int rc = f.begin();
         return rc != 0 ? (rc < 0 ? rc : 0) : f.finish();
     }
@@ -764,7 +780,7 @@ struct ForwardCall {
                 // a visible key outside the speculated byte: the three-pass order is wrong -- run the whole view again, four passes
                 HIP_OK(hipStreamSynchronize(s));
                 g_history.count(WorkloadHistory::kRerunTop);
-                return run(c, false);
+                return run(c, false, light);
             }
         }
         g_history.record_R(ckey, R);
@@ -814,6 +830,7 @@ struct ForwardCall {
 struct BackwardCall {
     const svgir_params* p; const svgir_grads* g; int R; const int32_t* radii; char *geom_blob, *binning_blob; size_t binning_bytes;
     char *image_blob, *scratch; size_t scratch_bytes; hipStream_t s;
+    const svgir_sg_light* light;   // svgir_backward_sg: the spherical-Gaussian light of the fused shading (nullptr: the texture)
     ViewCounts caps;   // the binning blob's capacities (cap_R, cap_slots)
     ViewGrid v{};
     bool svgss = false;
@@ -856,7 +873,11 @@ struct BackwardCall {
     // validates the call, lays the blobs out and fills the composite's arguments: a negative status, 0, or 1 (nothing to do: P == 0)
     int locate() {
         if (int rc = validate(p, false)) return rc;
-        if (p->P == 0) return 1;
+        if (p->P == 0) {   // (nothing runs; the light's gradients are still written: zeros)
+            if (light && g && g->dL_denv) HIP_OK(hipMemsetAsync(g->dL_denv, 0, (size_t)7 * light->count * 4, s));
+            if (light && g && g->dL_dradiance_ratio) HIP_OK(hipMemsetAsync(g->dL_dradiance_ratio, 0, 4, s));
+            return 1;
+        }
         if (!g || !radii || !geom_blob || !binning_blob || !image_blob)
             return fail(SVGIR_ERR_INVALID, "grads / radii / blobs must be provided");
         if (p->shade) {   // fused shading: everything its backward needs, checked BEFORE anything is launched (no half-written gradients on a bad call)
@@ -1000,7 +1021,7 @@ struct BackwardCall {
         bool use_list = false;
         if (R > 0) {
             // (fused shading: the same launch builds the tables and zeroes the env-gradient accumulator of the shading backward below)
-            if (p->shade && g->env_grad_work) shade_tabs = shade_tables(&p->shade->sp, g->env_grad_work, p->shade->sp.env_h * p->shade->sp.env_w * 3);
+            if (p->shade && g->env_grad_work && !light) shade_tabs = shade_tables(&p->shade->sp, g->env_grad_work, p->shade->sp.env_h * p->shade->sp.env_w * 3);
             // (and counts, per chunk, the surfels that received a blend weight: the first half of the partition the per-Gaussian kernels walk)
             use_list = g->out_weights && !generic && (p->shade || p->P >= (rows ? kListMinPRows : kListMinP));
             launch_seg_build(ra, sc_clear, sc_bytes, shade_tabs, use_list ? g->out_weights : nullptr, p->P, G.shade_work, s);
@@ -1066,7 +1087,12 @@ struct BackwardCall {
                                 in_clear(g->dL_dshade_normals, 12 * Pz) &&
                                 (!g->dL_dradiance || in_clear(g->dL_dradiance, 3 * Pz * (size_t)sp.Ns)) &&
                                 (!g->dL_dviewdirs || in_clear(g->dL_dviewdirs, 3 * Pz));
-        if (shade_backward_impl(&sp, g->dL_dreduced, g->dL_dfeatures, g->dL_dvfeatures, g->dL_dbase_color, g->dL_droughness,
+        if (light) {   // (dL_denv = dL_dlobes [M,7]; the lobe / lattice tables and the accumulator's clear: one small launch in front)
+            if (int rc = shade_backward_sg_impl(&sp, light, g->dL_dreduced, g->dL_dfeatures, g->dL_dvfeatures, g->dL_dbase_color, g->dL_droughness,
+                                                g->dL_dshade_normals, g->dL_dradiance, g->dL_denv, g->env_grad_work, g->dL_dradiance_ratio,
+                                                g->dL_dviewdirs, precleared, false, "backward_sg", s))
+                return rc;
+        } else if (shade_backward_impl(&sp, g->dL_dreduced, g->dL_dfeatures, g->dL_dvfeatures, g->dL_dbase_color, g->dL_droughness,
                                 g->dL_dshade_normals, g->dL_dradiance, g->dL_denv, g->env_grad_work, g->dL_dradiance_ratio, g->dL_dviewdirs, precleared,
                                 shade_tabs.env != nullptr, s) != 0)
             return fail(SVGIR_ERR_INVALID, "fused shading: svgir_shade_backward rejected its parameters");
@@ -1100,6 +1126,13 @@ struct BackwardCall {
 int svgir_forward(const svgir_params* p, const svgir_outputs* o, svgir_alloc_fn geom, void* geom_ctx,
                   svgir_alloc_fn binning, void* binning_ctx, svgir_alloc_fn image, void* image_ctx, void* stream) {
     return ForwardCall::run({p, o, geom, geom_ctx, binning, binning_ctx, image, image_ctx, stream, 0}, true);
+}
+
+int svgir_forward_sg(const svgir_params* p, const svgir_sg_light* light, const svgir_outputs* o, svgir_alloc_fn geom, void* geom_ctx,
+                     svgir_alloc_fn binning, void* binning_ctx, svgir_alloc_fn image, void* image_ctx, void* stream) {
+    if (int rc = validate_sg(p, light, "forward_sg")) return rc;   // (a NULL light must not fall through to the texture path)
+    if (int rc = validate(p, true)) return rc;                      // (in front of the call object: a rejected call makes no HIP call at all)
+    return ForwardCall::run({p, o, geom, geom_ctx, binning, binning_ctx, image, image_ctx, stream, 0}, true, light);
 }
 
 // Several views in flight from ONE host thread: every view is begun (validated, allocated, all of its kernels launched on ITS stream)
@@ -1155,7 +1188,13 @@ size_t svgir_backward_scratch_bytes_for(int32_t variant, int32_t P, size_t binni
 int svgir_backward(const svgir_params* p, const svgir_grads* g, int32_t R, const int32_t* radii, char* geom_blob,
                    char* binning_blob, size_t binning_bytes, char* image_blob, char* scratch, size_t scratch_bytes,
                    void* stream) {
-    return BackwardCall{p, g, R, radii, geom_blob, binning_blob, binning_bytes, image_blob, scratch, scratch_bytes, (hipStream_t)stream}.run();
+    return BackwardCall{p, g, R, radii, geom_blob, binning_blob, binning_bytes, image_blob, scratch, scratch_bytes, (hipStream_t)stream, nullptr}.run();
+}
+
+int svgir_backward_sg(const svgir_params* p, const svgir_sg_light* light, const svgir_grads* g, int32_t R, const int32_t* radii, char* geom_blob,
+                      char* binning_blob, size_t binning_bytes, char* image_blob, char* scratch, size_t scratch_bytes, void* stream) {
+    if (int rc = validate_sg(p, light, "backward_sg")) return rc;   // (a NULL light must not fall through to the texture path)
+    return BackwardCall{p, g, R, radii, geom_blob, binning_blob, binning_bytes, image_blob, scratch, scratch_bytes, (hipStream_t)stream, light}.run();
 }
 
 int svgir_mark_visible(int32_t variant, int32_t P, const float* means3D, const float* viewmatrix,

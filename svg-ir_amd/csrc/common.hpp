@@ -578,6 +578,15 @@ int shade_backward_impl(const svgir_shade_params* p, const float* dL_dreduced, c
                         float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance, float* dL_denv,
                         float* env_grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, bool rows_precleared, bool tables_ready,
                         void* stream);
+// the same two under the spherical-Gaussian light (svgir_forward_sg / svgir_backward_sg): svgir_shade_forward_sg / _backward_sg without
+// their subset rejection.  tables_ready = the lobe table, the lattice table and (backward) the cleared 8 M-float accumulator are in place;
+// `who` names the entry point in the error messages
+int shade_forward_sg_impl(const svgir_shade_params* p, const svgir_sg_light* light, float* reduced, float* features, float* vfeatures,
+                          bool tables_ready, const char* who, void* stream);
+int shade_backward_sg_impl(const svgir_shade_params* p, const svgir_sg_light* light, const float* dL_dreduced, const float* dL_dfeatures,
+                           const float* dL_dvfeatures, float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance,
+                           float* dL_dlobes, float* grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, bool rows_precleared,
+                           bool tables_ready, const char* who, void* stream);
 
 #if defined(__HIPCC__)
 // ---- device helpers ----------------------------------------------------------------------------------------

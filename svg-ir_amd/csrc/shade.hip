@@ -1366,6 +1366,17 @@ __global__ void __launch_bounds__(BWAVES * 64) __attribute__((amdgpu_waves_per_e
     }
     if constexpr (LIGHT == LIGHT_SG) {   // (from the top down: the zeroing loop's address is not worth a register across the kernel)
         if (!VIEW) {
+            // The pull-back keeps the part of G = sum s d across the lobe's axis only, dxi = |lambda| (G - a (a.G)) / |xi|, and a sharp lobe
+            // (|lambda| in the hundreds) collects its G almost along a: flushed as it is, the fp32 rounding of the axial part -- per
+            // workgroup, and per float atomic behind it -- is |lambda| times larger in dxi than the part that counts.  So the axial part
+            // leaves here, in fp64, and the float accumulator holds G - a (a.G) (the pull-back's projection of it changes nothing).
+            for (int m = (int)threadIdx.x; m < sg_count(); m += BWAVES * 64) {
+                const float4 al = sg_tab()[2 * m];
+                double* G = sEnv + 8 * m;
+                const double ag = (double)al.x * G[0] + (double)al.y * G[1] + (double)al.z * G[2];
+                G[0] -= (double)al.x * ag; G[1] -= (double)al.y * ag; G[2] -= (double)al.z * ag;
+            }
+            __syncthreads();
             for (int i = 8 * sg_count() - 1 - (int)threadIdx.x; i >= 0; i -= BWAVES * 64) {
                 const float v = (float)sEnv[i];
                 if (v != 0.f) atomic_add_f32(&a.d_envtab[i], v);
@@ -1578,9 +1589,15 @@ namespace {
 // what the two shading entry points ask of svgir_shade_params (the env* fields are not read)
 int sg_params_check(const svgir_shade_params* p, const char* who) {
     if (!p || p->P < 0 || p->Ns <= 0) return report_error(SVGIR_ERR_INVALID, "%s: bad P / Ns", who);
-    if (p->subset || p->subset_count)
-        return report_error(SVGIR_ERR_INVALID, "%s: subset shading belongs to the rasterizer-fused path, which has no SG light", who);
+    if ((p->subset != nullptr) != (p->subset_count != nullptr)) return report_error(SVGIR_ERR_INVALID, "%s: subset and subset_count go together", who);
     if (const char* why = shade_inputs_check(p, true)) return report_error(SVGIR_ERR_INVALID, "%s: %s", who, why);
+    return 0;
+}
+
+// the public entry points shade all P surfels: a subset is the business of svgir_forward_sg / svgir_backward_sg, which bring their own list
+int sg_no_subset(const svgir_shade_params* p, const char* who) {
+    if (p && (p->subset || p->subset_count))
+        return report_error(SVGIR_ERR_INVALID, "%s: subset shading belongs to the rasterizer-fused path (svgir_forward_sg / svgir_backward_sg)", who);
     return 0;
 }
 
@@ -1620,13 +1637,31 @@ int svgir_sg_eval(const svgir_sg_light* light, int64_t n, const float* dirs, flo
 
 int svgir_shade_forward_sg(const svgir_shade_params* p, const svgir_sg_light* light, float* reduced, float* features, float* vfeatures,
                            void* stream) {
-    if (int rc = sg_params_check(p, "shade_forward_sg")) return rc;
-    if (int rc = sg_light_valid(light, "shade_forward_sg")) return rc;
-    if (vfeatures && !p->viewmatrix) return report_error(SVGIR_ERR_INVALID, "shade_forward_sg: vfeatures needs viewmatrix");
+    if (int rc = sg_no_subset(p, "shade_forward_sg")) return rc;
+    return svgir::shade_forward_sg_impl(p, light, reduced, features, vfeatures, false, "shade_forward_sg", stream);
+}
+
+int svgir_shade_backward_sg(const svgir_shade_params* p, const svgir_sg_light* light, const float* dL_dreduced, const float* dL_dfeatures,
+                            const float* dL_dvfeatures, float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance,
+                            float* dL_dlobes, float* grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream) {
+    if (int rc = sg_no_subset(p, "shade_backward_sg")) return rc;
+    return svgir::shade_backward_sg_impl(p, light, dL_dreduced, dL_dfeatures, dL_dvfeatures, dL_dbase_color, dL_droughness, dL_dnormals, dL_dradiance,
+                                         dL_dlobes, grad_work, dL_dradiance_ratio, dL_dviewdirs, false, false, "shade_backward_sg", stream);
+}
+
+}  // extern "C"
+
+// svgir_shade_forward_sg behind its subset rejection: p->subset (the rasterizer's list) is honoured -- the LIGHT_SG kernels zero-fill the
+// rows outside it like the texture's.  tables_ready: the lobe table and the lattice table were built by a kernel in front.
+int svgir::shade_forward_sg_impl(const svgir_shade_params* p, const svgir_sg_light* light, float* reduced, float* features, float* vfeatures,
+                                 bool tables_ready, const char* who, void* stream) {
+    if (int rc = sg_params_check(p, who)) return rc;
+    if (int rc = sg_light_valid(light, who)) return rc;
+    if (vfeatures && !p->viewmatrix) return report_error(SVGIR_ERR_INVALID, "%s: vfeatures needs viewmatrix", who);
     if (p->P == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     StageMarks tm = stage_begin(s);
-    launch_sg_prologue(light, p, nullptr, 0, s);
+    if (!tables_ready) launch_sg_prologue(light, p, nullptr, 0, s);
     stage_mark(tm, "shade_sg_table");
     ShadeArgs a;
     a.p = sg_kernel_params(p, light); a.reduced = reduced; a.features = features; a.vfeatures = vfeatures;
@@ -1635,25 +1670,31 @@ int svgir_shade_forward_sg(const svgir_shade_params* p, const svgir_sg_light* li
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
 
-int svgir_shade_backward_sg(const svgir_shade_params* p, const svgir_sg_light* light, const float* dL_dreduced, const float* dL_dfeatures,
-                            const float* dL_dvfeatures, float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance,
-                            float* dL_dlobes, float* grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, void* stream) {
-    if (int rc = sg_params_check(p, "shade_backward_sg")) return rc;
-    if (int rc = sg_light_valid(light, "shade_backward_sg")) return rc;
+// svgir_shade_backward_sg behind its subset rejection.  rows_precleared / tables_ready: as for shade_backward_impl (tables_ready: also the
+// cleared 8 M-float accumulator at the front of grad_work).
+int svgir::shade_backward_sg_impl(const svgir_shade_params* p, const svgir_sg_light* light, const float* dL_dreduced, const float* dL_dfeatures,
+                                  const float* dL_dvfeatures, float* dL_dbase_color, float* dL_droughness, float* dL_dnormals, float* dL_dradiance,
+                                  float* dL_dlobes, float* grad_work, float* dL_dradiance_ratio, float* dL_dviewdirs, bool rows_precleared,
+                                  bool tables_ready, const char* who, void* stream) {
+    if (int rc = sg_params_check(p, who)) return rc;
+    if (int rc = sg_light_valid(light, who)) return rc;
     if ((!dL_dreduced && !dL_dfeatures && !dL_dvfeatures) || (dL_dvfeatures && !p->viewmatrix) || !dL_dbase_color || !dL_droughness || !dL_dnormals ||
         !dL_dlobes || !grad_work)
-        return report_error(SVGIR_ERR_INVALID, "shade_backward_sg: an upstream gradient, an output or grad_work is missing");
+        return report_error(SVGIR_ERR_INVALID, "%s: an upstream gradient, an output or grad_work is missing", who);
     if ((!dL_dradiance && !p->radiance_ratio) || (dL_dradiance_ratio && !p->radiance_ratio))
-        return report_error(SVGIR_ERR_INVALID, "shade_backward_sg: dL_dradiance / dL_dradiance_ratio do not match radiance_ratio");
+        return report_error(SVGIR_ERR_INVALID, "%s: dL_dradiance / dL_dradiance_ratio do not match radiance_ratio", who);
     hipStream_t s = (hipStream_t)stream;
     const int M = light->count, ntab = 8 * M;
     StageMarks tm = stage_begin(s);
-    launch_sg_prologue(light, p, grad_work, ntab, s);   // (also when P == 0: dL_dlobes is then all zeros)
+    if (!tables_ready) launch_sg_prologue(light, p, grad_work, ntab, s);   // (also when P == 0: dL_dlobes is then all zeros)
+    // (zero_rest: every output is written completely -- rows outside the subset are zero)
     const ShadeBwdArgs a = shade_bwd_args(sg_kernel_params(p, light), dL_dreduced, dL_dfeatures, dL_dvfeatures, dL_dbase_color, dL_droughness, dL_dnormals,
-                                          dL_dradiance, grad_work, ntab, dL_dradiance_ratio, dL_dviewdirs, 0);
+                                          dL_dradiance, grad_work, ntab, dL_dradiance_ratio, dL_dviewdirs, (p->subset && !rows_precleared) ? 1 : 0);
     // the waves' records, the fp64 sums (8 M doubles) and the prepared table (8 M floats): 110 KB at M = 128, one workgroup per CU
     const size_t lds = (size_t)BW_GROUP_LDS * 4 + (size_t)ntab * 8 + (size_t)ntab * 4;
     if (int rc = shade_bwd_lds_opt_in<LIGHT_SG>()) return rc;
+    // (a subset launch keeps the grid of all P: the list's length is known on the device only; workgroups without work zero their share of
+    // the rest rows, store a zero partial sum and flush nothing)
     const int blocks = shade_bwd_blocks(p->P);
     stage_mark(tm, "shade_bwd_sg_prologue");
     if (p->P > 0) launch_shade_bwd<LIGHT_SG>(a, blocks, lds, false, 1, s);
@@ -1667,8 +1708,6 @@ int svgir_shade_backward_sg(const svgir_shade_params* p, const svgir_sg_light* l
     }
     return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
 }
-
-}  // extern "C"
 
 extern "C" {
 

@@ -129,12 +129,17 @@ def fill_grads(dev, upstream, grads, gblob, out_weights):
     return g, keep
 
 
-def run_backward(dev, p, g, R, radii, geomBuffer, binningBuffer, imageBuffer, scratch_bytes):
-    """Allocates the gradient-accumulation scratch (its size is the variant's business) and calls svgir_backward on the current stream."""
+def run_backward(dev, p, g, R, radii, geomBuffer, binningBuffer, imageBuffer, scratch_bytes, sg_light=None):
+    """Allocates the gradient-accumulation scratch (its size is the variant's business) and calls svgir_backward on the current stream
+    -- svgir_backward_sg when `sg_light` (a _native.SgLight: the light of the fused shading) is given."""
     rad = radii.contiguous()
     scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
-    N.guarded(dev, "backward", N.lib.svgir_backward, p, g, int(R), rad.data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-              binningBuffer.numel(), imageBuffer.data_ptr(), scratch.data_ptr(), scratch_bytes, N.stream_ptr(dev))
+    rest = (int(R), rad.data_ptr(), geomBuffer.data_ptr(), binningBuffer.data_ptr(), binningBuffer.numel(), imageBuffer.data_ptr(),
+            scratch.data_ptr(), scratch_bytes, N.stream_ptr(dev))
+    if sg_light is None:
+        N.guarded(dev, "backward", N.lib.svgir_backward, p, g, *rest)
+    else:
+        N.guarded(dev, "backward_sg", N.lib.svgir_backward_sg, p, sg_light, g, *rest)
 
 
 def mark_visible(variant, means3D, viewmatrix, projmatrix):

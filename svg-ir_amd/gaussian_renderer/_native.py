@@ -259,6 +259,13 @@ def _load():
     lib.svgir_radiance_loss_forward_sg.argtypes = [C.POINTER(RadianceLossParams), C.POINTER(SgLight)] + [C.c_void_p] * 5
     lib.svgir_radiance_loss_backward_sg.restype = C.c_int
     lib.svgir_radiance_loss_backward_sg.argtypes = [C.POINTER(RadianceLossParams), C.POINTER(SgLight)] + [C.c_void_p] * 8
+    # the fused shading under that light: svgir_forward / svgir_backward with the light block behind the params
+    lib.svgir_forward_sg.restype = C.c_int
+    lib.svgir_forward_sg.argtypes = [C.POINTER(Params), C.POINTER(SgLight), C.POINTER(Outputs), ALLOC_FN, C.c_void_p, ALLOC_FN, C.c_void_p,
+                                     ALLOC_FN, C.c_void_p, C.c_void_p]
+    lib.svgir_backward_sg.restype = C.c_int
+    lib.svgir_backward_sg.argtypes = [C.POINTER(Params), C.POINTER(SgLight), C.POINTER(Grads), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     if lib.svgir_abi_version() != ABI_VERSION:
         raise ImportError("libsvgir_raster.so ABI version mismatch")
     return lib
@@ -286,7 +293,8 @@ EXPORTS = ("svgir_abi_version", "svgir_geom_bytes", "svgir_image_bytes", "svgir_
            "svgir_sg_eval_backward", "svgir_env_backdrop_sg", "svgir_radiance_loss_sg_work_bytes", "svgir_radiance_loss_forward_sg",
            "svgir_radiance_loss_backward_sg", "svgir_lpips_packed_floats", "svgir_lpips_pack", "svgir_lpips_work_bytes", "svgir_lpips",
            "svgir_column_median_scratch_bytes", "svgir_column_median", "svgir_albedo_scale_median_scratch_bytes", "svgir_albedo_scale_median",
-           "svgir_surface_center_loss_partials", "svgir_surface_center_loss_forward", "svgir_surface_center_loss_backward")
+           "svgir_surface_center_loss_partials", "svgir_surface_center_loss_forward", "svgir_surface_center_loss_backward",
+           "svgir_forward_sg", "svgir_backward_sg")
 
 
 _scope = threading.local()
@@ -418,15 +426,19 @@ class BlobAllocator:
         return out
 
 
-def run_forward(steps):
+def run_forward(steps, sg_light=None):
     """Drives one `_forward_steps` generator of a binding (it yields (device, Params, Outputs, BlobAllocator) where the C call belongs
-    and returns the binding's tuple): ONE svgir_forward on the current stream."""
+    and returns the binding's tuple): ONE svgir_forward on the current stream -- svgir_forward_sg when `sg_light` (an SgLight: the
+    spherical-Gaussian light of the fused shading) is given."""
     try:
         dev, p, o, blobs = next(steps)
     except StopIteration as e:   # (P == 0: nothing to launch)
         return e.value
-    rendered = guarded(dev, "forward", lib.svgir_forward, p, o, blobs.fn("geom"), None, blobs.fn("binning"), None, blobs.fn("image"), None,
-                       stream_ptr(dev))
+    allocs = (blobs.fn("geom"), None, blobs.fn("binning"), None, blobs.fn("image"), None, stream_ptr(dev))
+    if sg_light is None:
+        rendered = guarded(dev, "forward", lib.svgir_forward, p, o, *allocs)
+    else:
+        rendered = guarded(dev, "forward_sg", lib.svgir_forward_sg, p, sg_light, o, *allocs)
     try:
         steps.send(rendered)
     except StopIteration as e:

@@ -246,8 +246,8 @@ def _is_sg(light):
 def _no_sg(light, what):
     if _is_sg(light):
         raise TypeError(f"{what} has no spherical-Gaussian (lgtSGs) light path: it needs the lat-long texture of DirectLightMap / EnvLight "
-                        f"(with an SG light use shade_and_pack + the rasterizer, sg_direct_light, render_view.sg_environment_backdrop, "
-                        f"losses.fused_radiance_loss_sg)")
+                        f"(with an SG light use render_shaded / fused_shade_sg, shade_and_pack, sg_direct_light, "
+                        f"render_view.sg_environment_backdrop, losses.fused_radiance_loss_sg)")
 
 
 def _sg_light(lobes, dev):
@@ -455,17 +455,20 @@ class _ShadedRasterize(torch.autograd.Function):
     """svgss.py:116-182 as ONE pair of library calls: svgir_forward runs its preprocess / sorts / per-tile cull, shades exactly the
     surfels that are a candidate of some 8x8 sub-tile of THIS view (packing included) and composites; svgir_backward differentiates
     the composite, then the shading of the surfels that received a blend weight.  Same results as shade_and_pack(...) followed by
-    GaussianRasterizer(...) -- bit for bit, except dL/d(env), whose float atomics are summed in another order."""
+    GaussianRasterizer(...) -- bit for bit, except dL/d(env), whose float atomics are summed in another order.
+    `sg`: the light is spherical-Gaussian -- the `env` slot holds the checked raw lobes [M,7] (SGLobes(...).lobes), its gradient is
+    [M,7], softplus / scale / env_transform are unused and the calls are svgir_forward_sg / svgir_backward_sg."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, opacities, scales, rotations, base_color, roughness, normals, viewdirs, radiance,
                 visibility, dirs, areas, env, raster_settings, softplus, scale, training, env_transform, all_surfels, want_reduced,
-                ratio=None, view_gradient=False):
+                ratio=None, view_gradient=False, sg=False):
         from .svgss_rasterization import _C, forward_args
         st = raster_settings
-        sp, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env,
-                                             softplus, scale, viewmatrix=st.viewmatrix, training=training,
+        sp, keep, dev, P, Ns, _, _ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas,
+                                             None if sg else env, softplus, scale, viewmatrix=st.viewmatrix, training=training,
                                              env_transform=env_transform, ratio=ratio)
+        lt, lkeep = _sg_light(env, dev) if sg else (None, None)
         if P != means3D.shape[0]:
             raise RuntimeError("render_shaded: the material tensors and means3D disagree on the number of surfels")
         S, VS = (4, 52) if training else (7, 64)
@@ -475,12 +478,12 @@ class _ShadedRasterize(torch.autograd.Function):
         empty = torch.empty(0, dtype=torch.float32, device=dev)
         out = _C.rasterize_gaussians(*forward_args(st, means3D, feats, vfeats, sh, empty, opacities, scales, rotations, empty,
                                                    st.viewmatrix, st.projmatrix, st.campos),
-                                     shade=fs, forward_only=not any(ctx.needs_input_grad))
+                                     shade=fs, forward_only=not any(ctx.needs_input_grad), **(dict(sg_light=lt) if sg else {}))
         (R, color, normal, depth, opacity, feature, vfeature, weights, radii, gb, bb, ib) = out
         lat = dirs if isinstance(dirs, FibonacciLattice) else None
         ctx.save_for_backward(means3D, sh, scales, rotations, base_color, roughness, normals, viewdirs, radiance, visibility,
                               None if lat else dirs, areas, env, feats, vfeats, weights, radii, gb, bb, ib, ratio)
-        ctx.cfg = (st, R, softplus, scale, training, env_transform, lat, all_surfels, bool(view_gradient))
+        ctx.cfg = (st, R, softplus, scale, training, env_transform, lat, all_surfels, bool(view_gradient), bool(sg))
         ctx.mark_non_differentiable(weights, radii)
         ctx.set_materialize_grads(False)
         if red is None:
@@ -492,11 +495,11 @@ class _ShadedRasterize(torch.autograd.Function):
         from .svgss_rasterization import _C, backward_args
         (means3D, sh, scales, rotations, base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, env, feats,
          vfeats, weights, radii, gb, bb, ib, ratio) = ctx.saved_tensors
-        st, R, softplus, scale, training, env_transform, lat, all_surfels, view = ctx.cfg
+        st, R, softplus, scale, training, env_transform, lat, all_surfels, view, sg = ctx.cfg
         view = view and ctx.needs_input_grad[9]
         dev = means3D.device
         sp, keep, _, P, Ns, env_h, env_w = _params(base_color, roughness, normals, viewdirs, radiance, visibility,
-                                                   lat if lat is not None else dirs, areas, env, softplus, scale,
+                                                   lat if lat is not None else dirs, areas, None if sg else env, softplus, scale,
                                                    viewmatrix=st.viewmatrix, training=training, env_transform=env_transform, ratio=ratio)
         if g_red is not None and not all_surfels:
             raise RuntimeError("render_shaded: a loss on `reduced` needs all_surfels=True (rows of unshaded surfels are zero)")
@@ -505,35 +508,38 @@ class _ShadedRasterize(torch.autograd.Function):
                              g_opacity, g_depth, g_feature, g_vfeature)
         if not view and not any(ctx.needs_input_grad[i] for i in (6, 7, 8, 10, 14, 22)):   # frozen materials (evaluation): the rasterizer's backward alone
             res = _C.rasterize_gaussians_backward(*args)
-            return (res[3], res[0], res[7], res[2], res[8], res[9]) + (None,) * 18
+            return (res[3], res[0], res[7], res[2], res[8], res[9]) + (None,) * 19
         fs = _fused_struct(sp, None, all_surfels)
-        d_env = N.out_tensor(keep[8].shape, torch.float32, dev)
+        lt, lkeep = _sg_light(env, dev) if sg else (None, None)
+        d_env = N.out_tensor(lkeep[0].shape if sg else keep[8].shape, torch.float32, dev)
         want_rad, d_ratio, gwork = _radiance_grads(ctx, 10, 22, ratio, env_h, env_w, dev)
+        if sg:   # (the lobes' table-space sums + the ratio's partial sums: svgir_sg_grad_work_bytes)
+            gwork = torch.empty(N.lib.svgir_sg_grad_work_bytes(lt.count) // 4, dtype=torch.float32, device=dev)
         # (the four per-surfel gradient tensors are carved out of the rasterizer's gradient allocation by the binding: the composite
         # backward clears that region in passing, the shading backward then writes the rows of the surfels that were blended.  Measured
         # at cfg3_train: +28 us in render_bwd / grad_reduce for the 160 MB; a zero-fill launch costs 37 us, zero-fill stores from the
         # shading backward's own waves 40 us -- its per-chunk vmcnt(0) waits for them)
-        sg = dict(dL_denv=d_env, env_grad_work=gwork, dL_dreduced=None if g_red is None else N.f32c(g_red, dev), out_weights=weights,
+        sgr = dict(dL_denv=d_env, env_grad_work=gwork, dL_dreduced=None if g_red is None else N.f32c(g_red, dev), out_weights=weights,
                   _shapes=dict(dL_dbase_color=keep[0].shape, dL_droughness=keep[1].shape, dL_dshade_normals=keep[2].shape))
         if want_rad:
-            sg["_shapes"]["dL_dradiance"] = keep[4].shape
+            sgr["_shapes"]["dL_dradiance"] = keep[4].shape
         if d_ratio is not None:
-            sg["dL_dradiance_ratio"] = d_ratio
+            sgr["dL_dradiance_ratio"] = d_ratio
         if view:   # (svgir_grads.dL_dviewdirs: carved out of the same allocation as the four per-surfel tensors, as the library asks)
-            sg["_shapes"]["dL_dviewdirs"] = keep[3].shape
+            sgr["_shapes"]["dL_dviewdirs"] = keep[3].shape
         if P == 0:
             d_env.zero_()
             if d_ratio is not None:
                 d_ratio.zero_()
-        res = _C.rasterize_gaussians_backward(*args, shade=fs, shade_grads=sg, scratch_feature_grads=not all_surfels)
-        d_base, d_rough, d_norm, d_rad = sg["dL_dbase_color"], sg["dL_droughness"], sg["dL_dshade_normals"], sg.get("dL_dradiance")
+        res = _C.rasterize_gaussians_backward(*args, shade=fs, shade_grads=sgr, scratch_feature_grads=not all_surfels, sg_light=lt)
+        d_base, d_rough, d_norm, d_rad = sgr["dL_dbase_color"], sgr["dL_droughness"], sgr["dL_dshade_normals"], sgr.get("dL_dradiance")
         (g_means2D, _gc, g_opac, g_means3D, _gf, _gvf, _gcov, g_sh, g_scales, g_rot, _gv, _gp, _gcp) = res
         return (g_means3D, g_means2D, g_sh, g_opac, g_scales, g_rot, d_base.reshape(base_color.shape),
                 d_rough.reshape(roughness.shape), d_norm.reshape(normals.shape),
-                sg["dL_dviewdirs"].reshape(viewdirs.shape) if view else None,
+                sgr["dL_dviewdirs"].reshape(viewdirs.shape) if view else None,
                 None if d_rad is None else d_rad.reshape(radiance.shape), None, None,
-                None, d_env.reshape(env.shape), None, None, None, None, None, None, None,
-                None if d_ratio is None else d_ratio.reshape(ratio.shape), None)
+                None, d_env.reshape(env.shape).to(env.dtype), None, None, None, None, None, None, None,
+                None if d_ratio is None else d_ratio.reshape(ratio.shape), None, None)
 
 
 def fused_shade(base_color, roughness, normals, viewdirs, radiance, direct_light_env_light, visibility, dirs, areas, viewmatrix,
@@ -547,6 +553,20 @@ def fused_shade(base_color, roughness, normals, viewdirs, radiance, direct_light
     return _fused_struct(sp, reduced, all_surfels), keep + [reduced]
 
 
+def fused_shade_sg(base_color, roughness, normals, viewdirs, radiance, direct_light_sg, visibility, dirs, areas, viewmatrix,
+                   is_training, reduced=None, all_surfels=False, radiance_ratio=None):
+    """fused_shade under a spherical-Gaussian light (`.lgtSGs`): (`_native.FusedShade`, `_native.SgLight`, keep-alive list) for the
+    `shade=` and `sg_light=` keywords of `_C.rasterize_gaussians{,_backward}` (svgir_forward_sg / svgir_backward_sg).  In the backward's
+    `shade_grads`, dL_denv is dL_dlobes [M,7] and env_grad_work holds svgir_sg_grad_work_bytes(M) bytes."""
+    if not _is_sg(direct_light_sg):
+        raise TypeError("fused_shade_sg needs a light exposing .lgtSGs (DirectLightSG); a lat-long texture goes through fused_shade")
+    lobes = SGLobes(direct_light_sg.lgtSGs).lobes
+    sp, keep, dev, *_ = _params(base_color, roughness, normals, viewdirs, radiance, visibility, dirs, areas, None, False, 1.0,
+                                viewmatrix=viewmatrix, training=bool(is_training), ratio=radiance_ratio)
+    lt, lkeep = _sg_light(lobes, dev)
+    return _fused_struct(sp, reduced, all_surfels), lt, keep + lkeep + [reduced]
+
+
 def render_shaded(raster_settings, means3D, means2D, opacities, shs, scales, rotations, base_color, roughness, normals, viewdirs,
                   radiance, direct_light_env_light, visibility, dirs, areas, is_training, all_surfels=False, want_reduced=False,
                   radiance_ratio=None, *, view_gradient=False):
@@ -555,15 +575,14 @@ def render_shaded(raster_settings, means3D, means2D, opacities, shs, scales, rot
     weights, radii) and `reduced` [P,70] (rows of unshaded surfels zero; an empty tensor unless want_reduced).
     all_surfels=True shades every surfel (needed when a loss reads `reduced` directly: the reference's lambda_light term,
     svgss.py:359-364).  `view_gradient`: see rendering_equation4 (svgir_grads.dL_dviewdirs).
-    With a spherical-Gaussian light (`.lgtSGs`) the unfused sequence runs -- shade_and_pack over all P surfels, then the rasterizer --
-    whose results the fused one reproduces bit for bit (include/svgir_raster.h): svgir_fused_shade carries no SG light."""
+    A spherical-Gaussian light (`.lgtSGs`) runs the same fused pair with the lobes as the light (svgir_forward_sg / svgir_backward_sg):
+    bit for bit the unfused sequence, the lobes' gradient up to the order of its float atomics."""
     if _is_sg(direct_light_env_light):
-        from .svgss_rasterization import GaussianRasterizer
-        feats, vfeats, red = shade_and_pack(base_color, roughness, normals, viewdirs, radiance, direct_light_env_light, visibility, dirs,
-                                            areas, raster_settings.viewmatrix, is_training, radiance_ratio, view_gradient=view_gradient)
-        out = GaussianRasterizer(raster_settings)(means3D=means3D, means2D=means2D, opacities=opacities, shs=shs, scales=scales,
-                                                  rotations=rotations, features=feats, vfeatures=vfeats)
-        return tuple(out), (red if want_reduced else torch.empty(0, dtype=torch.float32, device=means3D.device))
+        out = _ShadedRasterize.apply(means3D, means2D, shs, opacities, scales, rotations, base_color, roughness, normals, viewdirs,
+                                     radiance, visibility, dirs, areas, SGLobes(direct_light_env_light.lgtSGs).lobes, raster_settings,
+                                     False, 1.0, bool(is_training), None, bool(all_surfels), bool(want_reduced), radiance_ratio,
+                                     bool(view_gradient), True)
+        return out[:9], out[9]
     env, softplus, scale, transform = _env_of(direct_light_env_light)
     out = _ShadedRasterize.apply(means3D, means2D, shs, opacities, scales, rotations, base_color, roughness, normals, viewdirs,
                                  radiance, visibility, dirs, areas, env, raster_settings, softplus, scale, bool(is_training),

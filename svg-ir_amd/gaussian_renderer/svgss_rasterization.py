@@ -33,8 +33,13 @@ class _CBinding:
     @staticmethod
     def rasterize_gaussians(*args, **kw):
         """The reference's `_C.rasterize_gaussians` (24 positional arguments, rasterize_points.h:18-46); keyword-only extensions:
-        `features_ready`, `shade`, `forward_only` (see `_forward_steps`)."""
-        return N.run_forward(_CBinding._forward_steps(*args, **kw))
+        `features_ready`, `shade`, `forward_only` (see `_forward_steps`), and `sg_light`: a `_native.SgLight`, the spherical-Gaussian
+        light of the fused shading (needs `shade`) -- the call is then svgir_forward_sg.  (rasterize_gaussians_batch has no such
+        argument: svgir_view_call has no room for a light.)"""
+        sg_light = kw.pop("sg_light", None)
+        if sg_light is not None and kw.get("shade") is None:
+            raise ValueError("rasterize_gaussians: sg_light belongs to the fused shading (pass `shade`)")
+        return N.run_forward(_CBinding._forward_steps(*args, **kw), sg_light)
 
     @staticmethod
     def rasterize_gaussians_batch(calls, device, streams):
@@ -76,14 +81,18 @@ class _CBinding:
                                      tan_fovx, tan_fovy, dL_dout_color, dL_dout_normal, dL_dout_depth, dL_dout_opac,
                                      dL_dout_feature, dL_dout_vfeature, sh, degree, campos, geomBuffer, R,
                                      binningBuffer, imageBuffer, debug, config, *, shade=None, shade_grads=None, out_weights=None,
-                                     scratch_feature_grads=False):
+                                     scratch_feature_grads=False, sg_light=None):
         """`shade` / `shade_grads` (extension, keyword only): the `_native.FusedShade` of the forward and a dict of the shading's
         gradient outputs + `out_weights` (+ optional `dL_dreduced`), written by svgir_backward (gaussian_renderer/shading.py;
         its "_shapes" entry: _binding.carve_gradients).
         `out_weights` (extension, keyword only): the forward's weights [P,1] (_binding.fill_grads).
         `scratch_feature_grads` (with `shade`): dL_dfeatures / dL_dvfeatures are intermediates of the fused call -- written for the blended
         surfels, read back by the shading's backward for exactly those -- so they need no zero rows: they are taken out of the cleared
-        allocation (45 MB less to clear at P = 200 k); the rows of unblended surfels in the two returned tensors are then UNDEFINED."""
+        allocation (45 MB less to clear at P = 200 k); the rows of unblended surfels in the two returned tensors are then UNDEFINED.
+        `sg_light` (with `shade`): the `_native.SgLight` of the forward -- the call is svgir_backward_sg, shade_grads["dL_denv"] is
+        dL_dlobes [M,7] and shade_grads["env_grad_work"] holds svgir_sg_grad_work_bytes(M) bytes."""
+        if sg_light is not None and shade is None:
+            raise ValueError("rasterize_gaussians_backward: sg_light belongs to the fused shading (pass `shade`)")
         dev, P, S, VS, M = means3D.device, means3D.size(0), B.width(features), B.width(vfeatures), B.sh_count(sh)
         upstream = dict(dL_dout_color=dL_dout_color, dL_dout_normal=dL_dout_normal, dL_dout_depth=dL_dout_depth,
                         dL_dout_opacity=dL_dout_opac, dL_dout_feature=dL_dout_feature, dL_dout_vfeature=dL_dout_vfeature)
@@ -110,7 +119,7 @@ class _CBinding:
             # scratch for the gradient accumulation: one row per (instance, sub-tile) pair that survived this view's cull (the
             # forward read the count back behind its cull), summed per Gaussian
             nscr = N.lib.svgir_backward_scratch_bytes_for(N.SVGSS, P, binningBuffer.numel(), imageBuffer.data_ptr(), W, H, S, VS)
-            B.run_backward(dev, p, gs, R, radii, geomBuffer, binningBuffer, imageBuffer, nscr)
+            B.run_backward(dev, p, gs, R, radii, geomBuffer, binningBuffer, imageBuffer, nscr, **({} if sg_light is None else {"sg_light": sg_light}))
         return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dfeatures"], g["dL_dvfeatures"],
                 g["dL_dcov3D"], g["dL_dsh"], g["dL_dscales"], g["dL_drotations"], g["dL_dviewmat"], g["dL_dprojmat"], g["dL_dcampos"])
 

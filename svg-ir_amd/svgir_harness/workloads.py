@@ -53,9 +53,9 @@ class TrainStep:
         self.shading, self.render_view, self.losses, self.optim = shading, render_view, losses, optim
         self.GaussianRasterizer = GaussianRasterizer
         # sg_lobes > 0: the direct light is the reference's DirectLightSG with that many lobes (train.py:65-66) instead of the texture --
-        # the parameter of optimizer group 'env' is lgtSGs [sg_lobes, 7], and the step takes the unfused path (svgir_fused_shade has no SG light)
+        # the parameter of optimizer group 'env' is lgtSGs [sg_lobes, 7]; `fused` is honoured as for the texture (svgir_forward_sg / svgir_backward_sg)
         self.sg_lobes = int(sg_lobes)
-        self.dev, self.name, self.Ns, self.fused = dev, name, Ns, bool(fused) and not self.sg_lobes
+        self.dev, self.name, self.Ns, self.fused = dev, name, Ns, bool(fused)
         # The reference shades with pc.get_radiances = nan_to_num(_radiances.detach() * _radiance_ratio, nan=0) (gaussian_model.py:323-324):
         # the cache sits in the optimizer (group 'radiances', :527) but never receives a gradient; what learns is the scalar ratio
         # (lr 0.01, :526-528).  radiance_grad=True is the earlier rounds' form (the [P, Ns, 3] cache itself is a differentiated leaf).
