@@ -24,10 +24,22 @@
 // The second half of the file is the whole radiance-consistency loss around that sum as one forward and one backward kernel
 // (svgir_radiance_loss_forward / _backward; GaussianModel.get_radiance_loss, scene/gaussian_model.py:544-575): the selection of the
 // sample, the light of the hit surfel's escaped samples looked up in the kernel (env_lookup.hpp, the f(env) table of the shading
-// kernels) and the L1 against the cached radiance.  It shares irr_load_corners / irr_light / irr_spec with the kernels above; no
-// [N,S,3] light tensor and no [N,S,3] gradient exist on that path.  See the comment in front of radiance_loss_fwd_kernel.  Both kernels
-// are instantiated for the lat-long texture and for the spherical-Gaussian light (sg_light.hpp; svgir_radiance_loss_forward_sg /
-// _backward_sg): the light of a sample and the scatter of its adjoint are the only light-specific parts.
+// kernels) and the L1 against the cached radiance.  No [N,S,3] light tensor and no [N,S,3] gradient exist on that path.  See the comment
+// in front of radiance_loss_fwd_kernel.  Both kernels are instantiated for the lat-long texture and for the spherical-Gaussian light
+// (sg_light.hpp; svgir_radiance_loss_forward_sg / _backward_sg): the light of a sample and the scatter of its adjoint are the only
+// light-specific parts, on the device and behind the four entry points (rl_forward<LIGHT> / rl_backward<LIGHT>).
+//
+// Shared: irr_load_corners / irr_light / irr_spec (corners, a sample's light direction, a corner's specular term), irr_row_corners (the row
+// prologue of irradiance_kernel, irradiance_sample_bwd_kernel and radiance_loss_fwd_kernel) and wave.hpp's block_tree_sum (the fixed tree
+// of radiance_loss_final_kernel, 1024 doubles, and of the two d_ratio sums, BLOCK doubles).  Kept as copies ON PURPOSE, because one helper
+// changed the generated code of the kernel named (profiles/irradiance_refactor_isa.txt has the numbers):
+//   * the per-sample forward body (irradiance_kernel<FULL>, radiance_loss_fwd_kernel<LIGHT>): other address arithmetic in
+//     irradiance_kernel, svgir_pbgi_irradiance + 2.4 %, the fused texture forward + 1.2 %;
+//   * the per-sample backward body (irradiance_sample_bwd_kernel and both light branches of radiance_loss_bwd_kernel<LIGHT>), the row
+//     epilogue and the wave-ordered workgroup sum: radiance_loss_bwd_kernel<LIGHT> got 3 - 5 more SGPR spill lanes and another
+//     instruction stream behind every one of them, the row prologue included, so that kernel keeps all of its text.
+// A change of the per-sample body or of the skip rule (a channel without upstream is SKIPPED in the loss, multiplied in the sample form)
+// is made at each of these sites.
 #include <cmath>
 
 #include "common.hpp"
@@ -84,6 +96,15 @@ __device__ __forceinline__ void irr_load_corners(IrrCorners& c, const float* vdi
         c.k[k] = ((a + 2.0f * r) + 1.0f) / 8.0f;
         c.n1[k] = c.nov[k] * (1.0f - c.k[k]) + c.k[k];
     }
+}
+// the row prologue (every kernel but radiance_loss_bwd_kernel, which keeps its own text): the view direction is ray p of row i, the
+// corners are those of its hit h
+template <bool FULL>
+__device__ __forceinline__ void irr_row_corners(IrrCorners& c, const float* ray_d, size_t i, int S, int p, size_t h, const float* normals,
+                                                const float* albedos, const float* roughnesses) {
+    const float* vd = ray_d + (i * (size_t)S + p) * 3;
+    const float vdir[3] = {vd[0], vd[1], vd[2]};
+    irr_load_corners<FULL>(c, vdir, h, normals, albedos, roughnesses);
 }
 
 // per lane: the light direction of one secondary sample
@@ -159,10 +180,8 @@ __global__ void __launch_bounds__(BLOCK) irradiance_kernel(int N, int S, size_t 
     float acc[3] = {0.f, 0.f, 0.f};
     if (hh >= 0) {
         const size_t h = (size_t)hh;
-        const float* vd = ray_d + (i * (size_t)S + p) * 3;
-        const float vdir[3] = {vd[0], vd[1], vd[2]};
         IrrCorners c;
-        irr_load_corners<FULL>(c, vdir, h, normals, albedos, roughnesses);
+        irr_row_corners<FULL>(c, ray_d, i, S, p, h, normals, albedos, roughnesses);
         const float fs = (float)S;
         for (int s = lane; s < S; s += IRR_WAVE) {
             const size_t hs = h * (size_t)S + s;
@@ -170,6 +189,7 @@ __global__ void __launch_bounds__(BLOCK) irradiance_kernel(int N, int S, size_t 
             const float ld[3] = {ray_d[hs * 3], ray_d[hs * 3 + 1], ray_d[hs * 3 + 2]};
             IrrLight q;
             irr_light(q, c, ld, uvs[hs * 2], uvs[hs * 2 + 1]);
+            // (the per-sample forward body stands here and in radiance_loss_fwd_kernel: routed through one helper both measured slower)
             float b[4], cosn[4];
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -210,11 +230,9 @@ __global__ void __launch_bounds__(BLOCK) irradiance_sample_bwd_kernel(int N, int
     const int hh = __builtin_amdgcn_readfirstlane(irr_entry<false>(e, N, S, sample_indices, hit, i, p));
     if (hh < 0) return;   // (wave-uniform)
     const size_t h = (size_t)hh;
-    const float* vd = ray_d + (i * (size_t)S + p) * 3;
-    const float vdir[3] = {vd[0], vd[1], vd[2]};
     const float g[3] = {d_out[i * 3], d_out[i * 3 + 1], d_out[i * 3 + 2]};
     IrrCorners c;
-    irr_load_corners<false>(c, vdir, h, normals, albedos, roughnesses);
+    irr_row_corners<false>(c, ray_d, i, S, p, h, normals, albedos, roughnesses);
     const float fs = (float)S;
     float dalb[3][4] = {}, drough = 0.f;
     // passes of 64 samples; every lane takes part in the shuffles of a pass, also behind the tail
@@ -435,10 +453,8 @@ __global__ void __launch_bounds__(BLOCK) radiance_loss_fwd_kernel(const RadLossA
         float acc[3] = {0.f, 0.f, 0.f};
         if (hh >= 0) {
             const size_t h = (size_t)hh;
-            const float* vd = a.ray_d + (i * (size_t)S + p) * 3;
-            const float vdir[3] = {vd[0], vd[1], vd[2]};
             IrrCorners c;
-            irr_load_corners<false>(c, vdir, h, a.normals, a.albedos, a.roughnesses);
+            irr_row_corners<false>(c, a.ray_d, i, S, p, h, a.normals, a.albedos, a.roughnesses);
             const RlTransform T = rl_transform(a);
             const float fs = (float)S;
             for (int s = lane; s < S; s += IRR_WAVE) {
@@ -492,18 +508,10 @@ constexpr int RL_FINAL = 1024;
 // one workgroup: thread t adds partial[t], partial[t + 1024], ... in order, then a fixed tree.  sum_out = the sum, loss = fp32(sum / count)
 __global__ void __launch_bounds__(RL_FINAL) radiance_loss_final_kernel(const double* __restrict__ partial, size_t n, double count,
                                                                        double* __restrict__ sum_out, float* __restrict__ loss) {
-    __shared__ double part[RL_FINAL];
-    double t = 0.0;
-    for (size_t k = threadIdx.x; k < n; k += RL_FINAL) t += partial[k];
-    part[threadIdx.x] = t;
-    __syncthreads();
-    for (int h = RL_FINAL / 2; h >= 1; h >>= 1) {
-        if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-        __syncthreads();
-    }
+    const double t = block_tree_sum<double, RL_FINAL>(partial, n);
     if (threadIdx.x == 0) {
-        *sum_out = part[0];
-        *loss = (float)(part[0] / count);
+        *sum_out = t;
+        *loss = (float)(t / count);
     }
 }
 
@@ -669,38 +677,33 @@ __global__ void __launch_bounds__(RLB_WAVES * 64) radiance_loss_bwd_kernel(const
     }
 }
 
+// d_ratio = the backward workgroups' partial sums in a fixed tree (one workgroup of BLOCK threads)
+__device__ __forceinline__ void rl_ratio_tree(const double* __restrict__ ratio_part, int nparts, float* __restrict__ d_ratio) {
+    const double t = block_tree_sum<double, BLOCK>(ratio_part, nparts);
+    if (threadIdx.x == 0) *d_ratio = (float)t;
+}
+
 // d_env = d f(env) * f'(env) (softplus' = sigmoid; an element nothing was added to is exactly 0, whatever env holds there) and, in
 // workgroup 0, d_ratio = the workgroups' partial sums in a fixed tree
 __global__ void __launch_bounds__(BLOCK) radiance_loss_env_grad_kernel(const float* __restrict__ env, const float* __restrict__ dtab,
                                                                        float* __restrict__ denv, int n, int softplus,
                                                                        const double* __restrict__ ratio_part, int nparts,
                                                                        float* __restrict__ d_ratio) {
-    if (d_ratio && blockIdx.x == 0) {
-        __shared__ double part[BLOCK];
-        double t = 0.0;
-        for (int k = threadIdx.x; k < nparts; k += BLOCK) t += ratio_part[k];
-        part[threadIdx.x] = t;
-        __syncthreads();
-        for (int h = BLOCK / 2; h >= 1; h >>= 1) {
-            if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) *d_ratio = (float)part[0];
-    }
+    if (d_ratio && blockIdx.x == 0) rl_ratio_tree(ratio_part, nparts, d_ratio);
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (!denv || i >= n) return;
     const float d = dtab[i], x = env[i];
     denv[i] = d == 0.f ? 0.f : softplus ? d * (x > 20.f ? 1.f : 1.f / (1.f + expf(-x))) : d;
 }
 
-// the work buffer: [f(env) float4 table | env-gradient table, floats | partial sums, doubles]
+// the work buffer of both lights: [the light's table | the light's gradient table, floats | partial sums, doubles].  Texture: the f(env)
+// float4 table and the env-gradient table [He*We*3]; SG: no table (the prepared one is light->work) and the 8 M table-space sums.
 struct RlWork { size_t tab, dtab, part, bytes, nparts; };
-RlWork rl_work(int32_t N, int32_t env_h, int32_t env_w) {
+RlWork rl_work(int32_t N, size_t tab_bytes, size_t dtab_floats) {
     RlWork w;
-    const size_t ntexel = (size_t)env_h * env_w;
     w.tab = 0;
-    w.dtab = ntexel * 16;
-    w.part = w.dtab + ((ntexel * 3 * 4 + 15) & ~(size_t)15);
+    w.dtab = tab_bytes;
+    w.part = w.dtab + ((dtab_floats * 4 + 15) & ~(size_t)15);
     w.nparts = std::max(((size_t)N + IRR_WAVES - 1) / IRR_WAVES, (size_t)RLB_MAX_BLOCKS);
     w.bytes = w.part + w.nparts * 8;
     return w;
@@ -742,27 +745,6 @@ size_t rl_resident(size_t lds) {
     return resident;
 }
 
-// ---- the SG light's host side: p->work = [table-space sums, 8 M floats | partial sums, doubles]; the prepared table is light->work
-struct RlSgWork { size_t dtab, part, bytes, nparts; };
-RlSgWork rl_sg_work(int32_t N, int32_t count) {
-    RlSgWork w;
-    w.dtab = 0;
-    w.part = (size_t)8 * count * sizeof(float);
-    w.nparts = std::max(((size_t)N + IRR_WAVES - 1) / IRR_WAVES, (size_t)RLB_MAX_BLOCKS);
-    w.bytes = w.part + w.nparts * 8;
-    return w;
-}
-
-RadLossArgs rl_args_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* l) {
-    RadLossArgs a{};
-    a.N = p->N; a.S = p->S;
-    a.xyz = p->xyz; a.cam = p->camera_center; a.geo = p->geo_normal; a.ray_d = p->ray_d; a.area = p->areas; a.vis = p->visibility;
-    a.normals = p->normals; a.albedos = p->albedos; a.roughnesses = p->roughnesses; a.uvs = p->uvs; a.radiances = p->radiances;
-    a.ratio = p->radiance_ratio; a.hit = p->hit_indices;
-    a.env_tab = (const float4*)l->work; a.env_h = 1; a.env_w = l->count; a.env_scale = 1.f;
-    return a;
-}
-
 // prologue of both SG calls: the prepared table; backward: the clear of the table-space sums and of the two per-surfel gradients
 __global__ void __launch_bounds__(BLOCK) radiance_loss_sg_table_kernel(const float* __restrict__ lobes, int M, float4* __restrict__ tab,
                                                                        float* __restrict__ zero, int nzero, float* z0, size_t n0, float* z1, size_t n1) {
@@ -777,39 +759,99 @@ __global__ void __launch_bounds__(BLOCK) radiance_loss_sg_table_kernel(const flo
 __global__ void __launch_bounds__(BLOCK) radiance_loss_sg_grad_kernel(const float* __restrict__ lobes, const float4* __restrict__ tab,
                                                                       const float* __restrict__ dtab, float* __restrict__ dlobes, int M,
                                                                       const double* __restrict__ ratio_part, int nparts, float* __restrict__ d_ratio) {
-    if (d_ratio) {
-        __shared__ double part[BLOCK];
-        double t = 0.0;
-        for (int k = threadIdx.x; k < nparts; k += BLOCK) t += ratio_part[k];
-        part[threadIdx.x] = t;
-        __syncthreads();
-        for (int h = BLOCK / 2; h >= 1; h >>= 1) {
-            if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) *d_ratio = (float)part[0];
-    }
+    if (d_ratio) rl_ratio_tree(ratio_part, nparts, d_ratio);
     if (dlobes && (int)threadIdx.x < M) sg_pullback(lobes, tab, dtab, threadIdx.x, dlobes);
 }
 
 static_assert(SVGIR_SG_MAX_LOBES <= BLOCK, "radiance_loss_sg_grad_kernel: one thread per lobe, one block");
 
-RadLossArgs rl_args(const svgir_radiance_loss_params* p, const RlWork& w) {
+// ---- the host side of the four loss calls, per light kind (l: the SG light, null for the texture, whose light is in p) --------------------
+template <int LIGHT>
+RlWork rl_work_of(const svgir_radiance_loss_params* p, const svgir_sg_light* l) {
+    if (LIGHT == LIGHT_SG) return rl_work(p->N, 0, (size_t)8 * l->count);
+    return rl_work(p->N, (size_t)p->env_h * p->env_w * 16, (size_t)p->env_h * p->env_w * 3);
+}
+
+template <int LIGHT>
+RadLossArgs rl_args(const svgir_radiance_loss_params* p, const svgir_sg_light* l, const RlWork& w) {
     RadLossArgs a{};
     a.N = p->N; a.S = p->S;
     a.xyz = p->xyz; a.cam = p->camera_center; a.geo = p->geo_normal; a.ray_d = p->ray_d; a.area = p->areas; a.vis = p->visibility;
     a.normals = p->normals; a.albedos = p->albedos; a.roughnesses = p->roughnesses; a.uvs = p->uvs; a.radiances = p->radiances;
     a.ratio = p->radiance_ratio; a.hit = p->hit_indices;
-    a.env_tab = (const float4*)((char*)p->work + w.tab);
-    a.env_h = p->env_h; a.env_w = p->env_w; a.env_scale = p->env_scale; a.transform = p->env_transform;
-    a.ntex3 = p->env_h * p->env_w * 3;
+    if constexpr (LIGHT == LIGHT_SG) {
+        a.env_tab = (const float4*)l->work; a.env_h = 1; a.env_w = l->count; a.env_scale = 1.f;
+    } else {
+        a.env_tab = (const float4*)((char*)p->work + w.tab);
+        a.env_h = p->env_h; a.env_w = p->env_w; a.env_scale = p->env_scale; a.transform = p->env_transform;
+        a.ntex3 = p->env_h * p->env_w * 3;
+    }
     return a;
 }
 
-ShadeTables rl_tables(const svgir_radiance_loss_params* p, const RlWork& w) {
-    ShadeTables t;
-    t.env = p->env; t.env_tab = (float4*)((char*)p->work + w.tab); t.ntexel = p->env_h * p->env_w; t.softplus = p->env_softplus;
-    return t;
+// prologue of every call: the light's table; backward: the clear of a.d_envtab and of the two per-surfel gradients z0 [n0], z1 [n1]
+template <int LIGHT>
+void rl_prologue(const svgir_radiance_loss_params* p, const svgir_sg_light* l, const RlWork& w, const RadLossArgs& a, float* z0, size_t n0,
+                 float* z1, size_t n1, hipStream_t s) {
+    if constexpr (LIGHT == LIGHT_SG) {
+        hipLaunchKernelGGL(radiance_loss_sg_table_kernel, dim3((unsigned)std::max<size_t>((n0 + BLOCK - 1) / BLOCK, 1)), dim3(BLOCK), 0, s, l->lobes,
+                           l->count, (float4*)l->work, a.d_envtab, a.ntex3, z0, n0, z1, n1);
+    } else {
+        ShadeTables t;
+        t.env = p->env; t.env_tab = (float4*)((char*)p->work + w.tab); t.ntexel = p->env_h * p->env_w; t.softplus = p->env_softplus;
+        t.zero = a.d_envtab; t.nzero = a.d_envtab ? a.ntex3 : 0;
+        const size_t items = std::max(std::max((size_t)t.ntexel, (size_t)t.nzero), n0);
+        hipLaunchKernelGGL(radiance_loss_table_kernel, dim3((unsigned)((items + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, t, z0, n0, z1, n1);
+    }
+}
+
+// table prologue -> radiance_loss_fwd_kernel<LIGHT> -> radiance_loss_final_kernel; false: a launch failed
+template <int LIGHT>
+bool rl_forward(const svgir_radiance_loss_params* p, const svgir_sg_light* l, int32_t* sample_indices, float* radiance, double* loss_sum,
+                float* loss, hipStream_t s) {
+    const RlWork w = rl_work_of<LIGHT>(p, l);
+    RadLossArgs a = rl_args<LIGHT>(p, l, w);
+    a.sample_out = sample_indices; a.R_out = radiance; a.partial = (double*)((char*)p->work + w.part);
+    const size_t blocks = ((size_t)p->N + IRR_WAVES - 1) / IRR_WAVES;
+    rl_prologue<LIGHT>(p, l, w, a, nullptr, 0, nullptr, 0, s);
+    hipLaunchKernelGGL(radiance_loss_fwd_kernel<LIGHT>, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(radiance_loss_final_kernel, dim3(1), dim3(RL_FINAL), 0, s, (const double*)a.partial, blocks, 3.0 * (double)p->N, loss_sum,
+                       loss);
+    return hipGetLastError() == hipSuccess;
+}
+
+// table prologue and clears -> radiance_loss_bwd_kernel<LIGHT> in persistent workgroups -> the light's gradient epilogue, which also sums
+// d_ratio.  d_light: d_env [He,We,3] or d_lobes [M,7] (null: the light gets no gradient).  Returns what failed, null when nothing did.
+template <int LIGHT>
+const char* rl_backward(const svgir_radiance_loss_params* p, const svgir_sg_light* l, const int32_t* sample_indices, const float* radiance,
+                        const float* d_loss, float* d_light, float* d_albedos, float* d_roughnesses, float* d_radiance_ratio, hipStream_t s) {
+    const RlWork w = rl_work_of<LIGHT>(p, l);
+    RadLossArgs a = rl_args<LIGHT>(p, l, w);
+    a.sample_in = sample_indices; a.R_in = radiance; a.g = d_loss; a.d_albedos = d_albedos; a.d_roughnesses = d_roughnesses;
+    a.d_envtab = d_light ? (float*)((char*)p->work + w.dtab) : nullptr;
+    a.ratio_part = (double*)((char*)p->work + w.part);
+    size_t lds = (size_t)RLB_WAVES * 8;   // the waves' d_ratio sums, then the light's fp64 sums
+    if constexpr (LIGHT == LIGHT_SG) {
+        // ... the prepared table, the waves' parked samples (two float4 per lane): 29 KB at M = 128
+        a.env_in_lds = 1; a.ntex3 = d_light ? 8 * l->count : 0;
+        lds += (size_t)a.ntex3 * 8 + (size_t)8 * l->count * 4 + (size_t)RLB_WAVES * 128 * 16;
+    } else if (d_light && lds + (size_t)a.ntex3 * 8 <= RL_LDS_BYTES) {
+        a.env_in_lds = 1; lds += (size_t)a.ntex3 * 8;
+    }
+    const size_t resident = rl_resident<LIGHT>(lds);   // (persistent workgroups)
+    if (!resident) return "querying the device failed";
+    const int blocks = (int)std::min<size_t>(((size_t)p->N + RLB_WAVES - 1) / RLB_WAVES, std::min<size_t>(resident, RLB_MAX_BLOCKS));
+    rl_prologue<LIGHT>(p, l, w, a, d_albedos, (size_t)p->N * 12, d_roughnesses, (size_t)p->N * 4, s);
+    hipLaunchKernelGGL(radiance_loss_bwd_kernel<LIGHT>, dim3(blocks), dim3(RLB_WAVES * 64), lds, s, a);
+    if (d_light || d_radiance_ratio) {
+        if constexpr (LIGHT == LIGHT_SG)
+            hipLaunchKernelGGL(radiance_loss_sg_grad_kernel, dim3(1), dim3(BLOCK), 0, s, l->lobes, (const float4*)l->work, (const float*)a.d_envtab,
+                               d_light, l->count, (const double*)a.ratio_part, blocks, d_radiance_ratio);
+        else
+            hipLaunchKernelGGL(radiance_loss_env_grad_kernel, dim3(d_light ? (a.ntex3 + BLOCK - 1) / BLOCK : 1), dim3(BLOCK), 0, s, p->env,
+                               (const float*)a.d_envtab, d_light, a.ntex3, p->env_softplus, (const double*)a.ratio_part, blocks, d_radiance_ratio);
+    }
+    return hipGetLastError() == hipSuccess ? nullptr : "launch failed";
 }
 
 }  // namespace
@@ -820,7 +862,7 @@ extern "C" {
 
 size_t svgir_radiance_loss_work_bytes(int32_t N, int32_t env_h, int32_t env_w) {
     if (N < 0 || env_h < 1 || env_w < 1 || (int64_t)env_h * env_w > (int64_t)1 << 26) return 0;
-    return svgir::rl_work(N, env_h, env_w).bytes;
+    return svgir::rl_work(N, (size_t)env_h * env_w * 16, (size_t)env_h * env_w * 3).bytes;
 }
 
 int svgir_radiance_loss_forward(const svgir_radiance_loss_params* p, int32_t* sample_indices, float* radiance, double* loss_sum, float* loss,
@@ -828,18 +870,7 @@ int svgir_radiance_loss_forward(const svgir_radiance_loss_params* p, int32_t* sa
     using namespace svgir;
     if (!rl_args_ok(p) || (p->N > 0 && (!sample_indices || !radiance || !loss_sum || !loss))) return SVGIR_ERR_INVALID;
     if (p->N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const RlWork w = rl_work(p->N, p->env_h, p->env_w);
-    RadLossArgs a = rl_args(p, w);
-    a.sample_out = sample_indices; a.R_out = radiance; a.partial = (double*)((char*)p->work + w.part);
-    const ShadeTables t = rl_tables(p, w);
-    const size_t blocks = ((size_t)p->N + IRR_WAVES - 1) / IRR_WAVES;
-    hipLaunchKernelGGL(radiance_loss_table_kernel, dim3((t.ntexel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, t, (float*)nullptr, (size_t)0,
-                       (float*)nullptr, (size_t)0);
-    hipLaunchKernelGGL(radiance_loss_fwd_kernel<LIGHT_TEX>, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
-    hipLaunchKernelGGL(radiance_loss_final_kernel, dim3(1), dim3(RL_FINAL), 0, s, (const double*)a.partial, blocks, 3.0 * (double)p->N, loss_sum,
-                       loss);
-    return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+    return rl_forward<LIGHT_TEX>(p, nullptr, sample_indices, radiance, loss_sum, loss, (hipStream_t)stream) ? 0 : SVGIR_ERR_HIP;
 }
 
 int svgir_radiance_loss_backward(const svgir_radiance_loss_params* p, const int32_t* sample_indices, const float* radiance, const float* d_loss,
@@ -847,33 +878,13 @@ int svgir_radiance_loss_backward(const svgir_radiance_loss_params* p, const int3
     using namespace svgir;
     if (!rl_args_ok(p) || (p->N > 0 && (!sample_indices || !radiance || !d_loss || !d_albedos || !d_roughnesses))) return SVGIR_ERR_INVALID;
     if (p->N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const RlWork w = rl_work(p->N, p->env_h, p->env_w);
-    RadLossArgs a = rl_args(p, w);
-    a.sample_in = sample_indices; a.R_in = radiance; a.g = d_loss; a.d_albedos = d_albedos; a.d_roughnesses = d_roughnesses;
-    a.d_envtab = d_env ? (float*)((char*)p->work + w.dtab) : nullptr;
-    a.ratio_part = (double*)((char*)p->work + w.part);
-    size_t lds = (size_t)RLB_WAVES * 8;
-    if (d_env && lds + (size_t)a.ntex3 * 8 <= RL_LDS_BYTES) { a.env_in_lds = 1; lds += (size_t)a.ntex3 * 8; }
-    const size_t resident = rl_resident<LIGHT_TEX>(lds);   // (persistent workgroups)
-    if (!resident) return SVGIR_ERR_HIP;
-    const int blocks = (int)std::min<size_t>(((size_t)p->N + RLB_WAVES - 1) / RLB_WAVES, std::min<size_t>(resident, RLB_MAX_BLOCKS));
-    ShadeTables t = rl_tables(p, w);
-    t.zero = a.d_envtab; t.nzero = a.d_envtab ? a.ntex3 : 0;
-    const size_t n_alb = (size_t)p->N * 12, n_rough = (size_t)p->N * 4;
-    const size_t items = std::max(std::max((size_t)t.ntexel, (size_t)t.nzero), n_alb);
-    hipLaunchKernelGGL(radiance_loss_table_kernel, dim3((unsigned)((items + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, t, d_albedos, n_alb,
-                       d_roughnesses, n_rough);
-    hipLaunchKernelGGL(radiance_loss_bwd_kernel<LIGHT_TEX>, dim3(blocks), dim3(RLB_WAVES * 64), lds, s, a);
-    if (d_env || d_radiance_ratio)
-        hipLaunchKernelGGL(radiance_loss_env_grad_kernel, dim3(d_env ? (a.ntex3 + BLOCK - 1) / BLOCK : 1), dim3(BLOCK), 0, s, p->env,
-                           (const float*)a.d_envtab, d_env, a.ntex3, p->env_softplus, (const double*)a.ratio_part, blocks, d_radiance_ratio);
-    return hipGetLastError() == hipSuccess ? 0 : SVGIR_ERR_HIP;
+    return rl_backward<LIGHT_TEX>(p, nullptr, sample_indices, radiance, d_loss, d_env, d_albedos, d_roughnesses, d_radiance_ratio,
+                                  (hipStream_t)stream) ? SVGIR_ERR_HIP : 0;
 }
 
 size_t svgir_radiance_loss_sg_work_bytes(int32_t N, int32_t count) {
     if (N < 0 || count < 1 || count > SVGIR_SG_MAX_LOBES) return 0;
-    return svgir::rl_sg_work(N, count).bytes;
+    return svgir::rl_work(N, 0, (size_t)8 * count).bytes;
 }
 
 int svgir_radiance_loss_forward_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* light, int32_t* sample_indices, float* radiance,
@@ -883,17 +894,8 @@ int svgir_radiance_loss_forward_sg(const svgir_radiance_loss_params* p, const sv
     if (!rl_args_ok(p, true) || (p->N > 0 && (!sample_indices || !radiance || !loss_sum || !loss)))
         return report_error(SVGIR_ERR_INVALID, "radiance_loss_forward_sg: bad N / S, a NULL input or output, or a NULL / misaligned work");
     if (p->N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const RlSgWork w = rl_sg_work(p->N, light->count);
-    RadLossArgs a = rl_args_sg(p, light);
-    a.sample_out = sample_indices; a.R_out = radiance; a.partial = (double*)((char*)p->work + w.part);
-    const size_t blocks = ((size_t)p->N + IRR_WAVES - 1) / IRR_WAVES;
-    hipLaunchKernelGGL(radiance_loss_sg_table_kernel, dim3(1), dim3(BLOCK), 0, s, light->lobes, light->count, (float4*)light->work, (float*)nullptr, 0,
-                       (float*)nullptr, (size_t)0, (float*)nullptr, (size_t)0);
-    hipLaunchKernelGGL(radiance_loss_fwd_kernel<LIGHT_SG>, dim3((unsigned)blocks), dim3(BLOCK), 0, s, a);
-    hipLaunchKernelGGL(radiance_loss_final_kernel, dim3(1), dim3(RL_FINAL), 0, s, (const double*)a.partial, blocks, 3.0 * (double)p->N, loss_sum,
-                       loss);
-    return hipGetLastError() == hipSuccess ? 0 : report_error(SVGIR_ERR_HIP, "radiance_loss_forward_sg: launch failed");
+    return rl_forward<LIGHT_SG>(p, light, sample_indices, radiance, loss_sum, loss, (hipStream_t)stream)
+               ? 0 : report_error(SVGIR_ERR_HIP, "radiance_loss_forward_sg: launch failed");
 }
 
 int svgir_radiance_loss_backward_sg(const svgir_radiance_loss_params* p, const svgir_sg_light* light, const int32_t* sample_indices,
@@ -904,27 +906,9 @@ int svgir_radiance_loss_backward_sg(const svgir_radiance_loss_params* p, const s
     if (!rl_args_ok(p, true) || (p->N > 0 && (!sample_indices || !radiance || !d_loss || !d_albedos || !d_roughnesses)))
         return report_error(SVGIR_ERR_INVALID, "radiance_loss_backward_sg: bad N / S, a NULL input or output, or a NULL / misaligned work");
     if (p->N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int M = light->count;
-    const RlSgWork w = rl_sg_work(p->N, M);
-    RadLossArgs a = rl_args_sg(p, light);
-    a.sample_in = sample_indices; a.R_in = radiance; a.g = d_loss; a.d_albedos = d_albedos; a.d_roughnesses = d_roughnesses;
-    a.d_envtab = d_lobes ? (float*)((char*)p->work + w.dtab) : nullptr;
-    a.ratio_part = (double*)((char*)p->work + w.part);
-    a.env_in_lds = 1; a.ntex3 = d_lobes ? 8 * M : 0;
-    // the waves' d_ratio sums, the fp64 sums, the prepared table, the waves' parked samples (two float4 per lane): 29 KB at M = 128
-    const size_t lds = (size_t)RLB_WAVES * 8 + (size_t)a.ntex3 * 8 + (size_t)8 * M * 4 + (size_t)RLB_WAVES * 128 * 16;
-    const size_t resident = rl_resident<LIGHT_SG>(lds);
-    if (!resident) return report_error(SVGIR_ERR_HIP, "radiance_loss_backward_sg: querying the device failed");
-    const int blocks = (int)std::min<size_t>(((size_t)p->N + RLB_WAVES - 1) / RLB_WAVES, std::min<size_t>(resident, RLB_MAX_BLOCKS));
-    const size_t n_alb = (size_t)p->N * 12, n_rough = (size_t)p->N * 4;
-    hipLaunchKernelGGL(radiance_loss_sg_table_kernel, dim3((unsigned)((n_alb + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, light->lobes, M,
-                       (float4*)light->work, a.d_envtab, a.ntex3, d_albedos, n_alb, d_roughnesses, n_rough);
-    hipLaunchKernelGGL(radiance_loss_bwd_kernel<LIGHT_SG>, dim3(blocks), dim3(RLB_WAVES * 64), lds, s, a);
-    if (d_lobes || d_radiance_ratio)
-        hipLaunchKernelGGL(radiance_loss_sg_grad_kernel, dim3(1), dim3(BLOCK), 0, s, light->lobes, (const float4*)light->work, (const float*)a.d_envtab,
-                           d_lobes, M, (const double*)a.ratio_part, blocks, d_radiance_ratio);
-    return hipGetLastError() == hipSuccess ? 0 : report_error(SVGIR_ERR_HIP, "radiance_loss_backward_sg: launch failed");
+    const char* failed = rl_backward<LIGHT_SG>(p, light, sample_indices, radiance, d_loss, d_lobes, d_albedos, d_roughnesses, d_radiance_ratio,
+                                               (hipStream_t)stream);
+    return failed ? report_error(SVGIR_ERR_HIP, "radiance_loss_backward_sg: %s", failed) : 0;
 }
 
 int svgir_pbgi_irradiance_sample(int32_t N, int32_t S, const int32_t* sample_indices, const float* ray_d, const float* envmap,

@@ -96,7 +96,7 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {
 // THE fixed-order floating-point sum over the four waves of a 256-thread workgroup, N quantities at once, in every thread: w[q] comes in as
 // the caller's own per-wave total (wave_sum or wave_reduce_add: the two give different float bits, so the wave step stays the caller's) and
 // goes out as (wave 0 + wave 1) + (wave 2 + wave 3).  lds[N][4]: see BARRIERS.  The losses' bit-reproducibility rests on this one tree.
-// (csrc/irradiance.hip's radiance loss keeps its own orders -- a 1024-thread halving tree and a serial wave loop: moving it here changes its bits.)
+// (csrc/irradiance.hip's radiance loss keeps its own orders -- block_tree_sum's halving tree below and a serial wave loop: another order changes its bits.)
 template <int N, class T>
 __device__ __forceinline__ void block_sum_put(const T (&w)[N], T (*lds)[4]) {
     if ((threadIdx.x & 63) == 0) {
@@ -135,6 +135,28 @@ __device__ __forceinline__ void block_reduce_records(const T* __restrict__ rec, 
 #pragma unroll
     for (int q = 0; q < N; q++) s[q] = wave_reduce_add(s[q]);
     block_sum_ordered(s, lds);
+}
+// THE halving tree over the THREADS threads of ONE workgroup: part[t] += part[t + h] for h = THREADS / 2 ... 1, every thread bringing `mine`;
+// the sum comes back in every thread.  The tree's shape decides the bits: a call site keeps its THREADS and its T.  The array is the
+// helper's own and there is no barrier in front of its first write: ONE call per kernel (a second one would overwrite part[] while
+// slower threads still read the first result).
+template <typename T, int THREADS>
+__device__ __forceinline__ T block_tree_sum(T mine) {
+    __shared__ T part[THREADS];
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (int h = THREADS / 2; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+        __syncthreads();
+    }
+    return part[0];
+}
+// ... of n values in memory: thread t adds src[t], src[t + THREADS], ... in that order first
+template <typename T, int THREADS, typename Count>
+__device__ __forceinline__ T block_tree_sum(const T* __restrict__ src, Count n) {
+    T t = 0;
+    for (Count k = threadIdx.x; k < n; k += THREADS) t += src[k];
+    return block_tree_sum<T, THREADS>(t);
 }
 // sum of block_sums[0 .. nbefore) -- the totals of the workgroups in front of this one -- in every thread
 template <int WAVES>

@@ -8,6 +8,8 @@ The consumers of those caches are here as well: `render_irradiance_sample` (:181
 `GaussianModel.get_radiance_loss`, scene/gaussian_model.py:544-575) and `render_irradiance` (:100-178, 743-746;
 `GaussianModel.calculate_radiance`, :530-542), with the reference's names and positional arguments -> svg-ir_amd/csrc/irradiance.hip.
 The contract, and what it decides where the reference is undefined, is in include/svgir_raster.h."""
+import types
+
 import torch
 
 from gaussian_renderer import _native
@@ -73,107 +75,34 @@ class _IrradianceSample(torch.autograd.Function):
         return (None, None, None, d_env.reshape(env_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape), None, None, None, None)
 
 
-class _RadianceConsistency(torch.autograd.Function):
-    """svgir_radiance_loss_forward / _backward: the whole radiance-consistency loss as one node.  Differentiable in env, albedos,
-    roughnesses and radiance_ratio; everything else gets None.  Returns (loss, sample_indices [N] int32, radiance [N,3], loss_sum
-    (float64 scalar)); only the loss carries a graph."""
+class _ConsistencyNode(torch.autograd.Function):
+    """The whole radiance-consistency loss as one autograd node; what both light kinds share.  A subclass names its two C entry points
+    (`FORWARD`, `BACKWARD`) and supplies `light(what, leaf, spec, dev)`: a namespace with `args` (the C arguments behind the parameter
+    block), `fields` (plain fields of the block), `tensors(f)` (its tensor fields; f: the shape-checked fp32 view), `held` (what else must
+    stay alive), `work_bytes(N)` and `grad_shape`.  Differentiable in leaf (the light's parameter), albedos, roughnesses and
+    radiance_ratio; everything else gets None.  Returns (loss, sample_indices [N] int32, radiance [N,3], loss_sum (float64 scalar));
+    only the loss carries a graph."""
 
-    @staticmethod
-    def forward(ctx, env, albedos, roughnesses, radiance_ratio, light, xyz, camera_center, geo_normal, ray_directions, areas, visibility,
-                normals, radiances, hit, uvs):
-        what = "radiance_consistency"
-        softplus, scale, transform = light
+    @classmethod
+    def _forward(cls, ctx, what, leaf, spec, on_device, albedos, roughnesses, radiance_ratio, xyz, camera_center, geo_normal, ray_directions, areas,
+                 visibility, normals, radiances, hit, uvs):
         N, S = int(ray_directions.shape[0]), int(ray_directions.shape[1])
-        for t in (env, xyz, camera_center, geo_normal, areas, visibility, radiances, radiance_ratio) + (() if transform is None else (transform,)):
+        for t in (leaf, xyz, camera_center, geo_normal, areas, visibility, radiances, radiance_ratio) + on_device:
             if not t.is_cuda:
                 raise RuntimeError(f"{what} needs CUDA/HIP tensors (there is no CPU path)")
         dev, t = _irradiance_inputs(what, N, S, hit, uvs, None, ray_directions, normals, albedos, roughnesses)
         f = lambda x, shape, name: _rows(what, _native.f32c(x.detach(), dev), shape, name)
-        e = _native.f32c(env.detach(), dev)
-        if e.dim() < 3 or e.shape[-1] != 3 or e.shape[-3] < 1 or e.shape[-2] < 1 or e.numel() != e.shape[-3] * e.shape[-2] * 3:
-            raise ValueError(f"{what}: the light's map must be ONE [He,We,3] map (leading dimensions of 1 are fine), got {tuple(env.shape)}")
-        e = e.reshape(e.shape[-3:])
-        e = e.contiguous()
+        lt = cls.light(what, leaf, spec, dev)
         p = _native.RadianceLossParams()
         keep = dict(xyz=f(xyz, (N, 3), "xyz"), camera_center=f(camera_center, (3,), "camera_center"), geo_normal=f(geo_normal, (N, 3), "geo_normal"),
                     ray_d=t[0], areas=f(areas, (N, S), "incident_areas"), visibility=f(visibility, (N, S), "visibility"), normals=t[2],
                     albedos=t[3], roughnesses=t[4], hit_indices=t[5], uvs=t[6], radiances=f(radiances, (N, S, 3), "radiances"),
-                    radiance_ratio=f(radiance_ratio, (1,), "radiance_ratio"), env=e,
-                    env_transform=None if transform is None else f(transform, (3, 3), "the light's transform"))
+                    radiance_ratio=f(radiance_ratio, (1,), "radiance_ratio"), **lt.tensors(f))
         with torch.cuda.device(dev):
-            work = torch.empty(max(_lib.svgir_radiance_loss_work_bytes(N, e.shape[0], e.shape[1]), 16), dtype=torch.uint8, device=dev)
-            keep["work"] = work
-            p.N, p.S, p.env_h, p.env_w, p.env_softplus, p.env_scale = N, S, int(e.shape[0]), int(e.shape[1]), int(bool(softplus)), float(scale)
-            for k, v in keep.items():
-                setattr(p, k, _native.ptr(v))
-            idx = _native.out_tensor((N,), torch.int32, dev)
-            R = _native.out_tensor((N, 3), torch.float32, dev)
-            total = _native.out_tensor((), torch.float64, dev)
-            loss = _native.out_tensor((), torch.float32, dev)
-            if N == 0:   # nothing is launched: the mean of no rows is NaN, as torch's
-                total.zero_()
-                loss.fill_(float("nan"))
-            _native.check(_lib.svgir_radiance_loss_forward(p, _native.ptr(idx), _native.ptr(R), total.data_ptr(), loss.data_ptr(),
-                                                           _native.stream_ptr(dev)), "radiance_loss_forward")
-        # The backward reads the inputs through the parameter block's raw pointers; `keep` holds the tensors behind them (the fp32 /
-        # contiguous copies where one was made, and the work buffer).  Unlike save_for_backward this does not notice an in-place change
-        # of an input between forward and backward: the backward then differentiates the changed values.
-        ctx.p, ctx.keep = p, keep
-        ctx.save_for_backward(idx, R)
-        ctx.shapes = (env.shape, albedos.shape, roughnesses.shape, radiance_ratio.shape)
-        ctx.mark_non_differentiable(idx, R, total)
-        return loss, idx, R, total
-
-    @staticmethod
-    def backward(ctx, g, _gi, _gr, _gt):
-        idx, R = ctx.saved_tensors
-        p, keep = ctx.p, ctx.keep
-        N = p.N
-        dev = idx.device
-        need_env, _, _, need_ratio = ctx.needs_input_grad[:4]
-        he, we = p.env_h, p.env_w
-        with torch.cuda.device(dev):
-            d_env = _native.out_tensor((he, we, 3), torch.float32, dev) if need_env else None
-            d_alb = _native.out_tensor((N, 12), torch.float32, dev)
-            d_rough = _native.out_tensor((N, 4), torch.float32, dev)
-            d_ratio = _native.out_tensor((1,), torch.float32, dev) if need_ratio else None
-            if N == 0:
-                for t in (d_env, d_ratio):
-                    if t is not None:
-                        t.zero_()
-            gdev = _native.f32c(g.detach(), dev).reshape(1).contiguous()   # the upstream scalar stays on the device
-            _native.check(_lib.svgir_radiance_loss_backward(p, _native.ptr(idx), _native.ptr(R), gdev.data_ptr(), _native.ptr(d_env),
-                                                            _native.ptr(d_alb), _native.ptr(d_rough), _native.ptr(d_ratio),
-                                                            _native.stream_ptr(dev)), "radiance_loss_backward")
-        env_shape, alb_shape, rough_shape, ratio_shape = ctx.shapes
-        return (None if d_env is None else d_env.reshape(env_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape),
-                None if d_ratio is None else d_ratio.reshape(ratio_shape)) + (None,) * 11
-
-
-class _RadianceConsistencySG(torch.autograd.Function):
-    """svgir_radiance_loss_forward_sg / _backward_sg: _RadianceConsistency under a spherical-Gaussian light, the raw lobes [M,7] in the
-    texture's place.  Differentiable in the lobes, albedos, roughnesses and radiance_ratio."""
-
-    @staticmethod
-    def forward(ctx, lobes, albedos, roughnesses, radiance_ratio, xyz, camera_center, geo_normal, ray_directions, areas, visibility, normals,
-                radiances, hit, uvs):
-        from gaussian_renderer import shading
-        what = "radiance_consistency_sg"
-        N, S = int(ray_directions.shape[0]), int(ray_directions.shape[1])
-        for t in (lobes, xyz, camera_center, geo_normal, areas, visibility, radiances, radiance_ratio):
-            if not t.is_cuda:
-                raise RuntimeError(f"{what} needs CUDA/HIP tensors (there is no CPU path)")
-        dev, t = _irradiance_inputs(what, N, S, hit, uvs, None, ray_directions, normals, albedos, roughnesses)
-        f = lambda x, shape, name: _rows(what, _native.f32c(x.detach(), dev), shape, name)
-        lt, lkeep = shading._sg_light(shading.SGLobes(lobes).lobes, dev)
-        p = _native.RadianceLossParams()
-        keep = dict(xyz=f(xyz, (N, 3), "xyz"), camera_center=f(camera_center, (3,), "camera_center"), geo_normal=f(geo_normal, (N, 3), "geo_normal"),
-                    ray_d=t[0], areas=f(areas, (N, S), "incident_areas"), visibility=f(visibility, (N, S), "visibility"), normals=t[2],
-                    albedos=t[3], roughnesses=t[4], hit_indices=t[5], uvs=t[6], radiances=f(radiances, (N, S, 3), "radiances"),
-                    radiance_ratio=f(radiance_ratio, (1,), "radiance_ratio"))
-        with torch.cuda.device(dev):
-            keep["work"] = torch.empty(max(_lib.svgir_radiance_loss_sg_work_bytes(N, lt.count), 16), dtype=torch.uint8, device=dev)
+            keep["work"] = torch.empty(max(lt.work_bytes(N), 16), dtype=torch.uint8, device=dev)
             p.N, p.S = N, S
+            for k, v in lt.fields.items():
+                setattr(p, k, v)
             for k, v in keep.items():
                 setattr(p, k, _native.ptr(v))
             idx = _native.out_tensor((N,), torch.int32, dev)
@@ -183,38 +112,87 @@ class _RadianceConsistencySG(torch.autograd.Function):
             if N == 0:   # nothing is launched: the mean of no rows is NaN, as torch's
                 total.zero_()
                 loss.fill_(float("nan"))
-            _native.check(_lib.svgir_radiance_loss_forward_sg(p, lt, _native.ptr(idx), _native.ptr(R), total.data_ptr(), loss.data_ptr(),
-                                                              _native.stream_ptr(dev)), "radiance_loss_forward_sg")
-        # (as _RadianceConsistency: the backward reads the inputs through the raw pointers of `p` and `lt`; `keep` holds the tensors)
-        ctx.p, ctx.lt, ctx.keep = p, lt, (keep, lkeep)
+            _native.check(getattr(_lib, cls.FORWARD)(p, *lt.args, _native.ptr(idx), _native.ptr(R), total.data_ptr(), loss.data_ptr(),
+                                                     _native.stream_ptr(dev)), cls.FORWARD[len("svgir_"):])
+        # The backward reads the inputs through the raw pointers of the parameter block (and of the SG light); `keep` holds the tensors
+        # behind them (the fp32 / contiguous copies where one was made, and the work buffer).  Unlike save_for_backward this does not notice
+        # an in-place change of an input between forward and backward: the backward then differentiates the changed values.
+        ctx.p, ctx.lt, ctx.keep = p, lt, keep
         ctx.save_for_backward(idx, R)
-        ctx.shapes = (lobes.shape, albedos.shape, roughnesses.shape, radiance_ratio.shape)
+        ctx.shapes = (leaf.shape, albedos.shape, roughnesses.shape, radiance_ratio.shape)
         ctx.mark_non_differentiable(idx, R, total)
         return loss, idx, R, total
 
-    @staticmethod
-    def backward(ctx, g, _gi, _gr, _gt):
+    @classmethod
+    def _backward(cls, ctx, g):
         idx, R = ctx.saved_tensors
         p, lt = ctx.p, ctx.lt
         N = p.N
         dev = idx.device
-        need_lobes, _, _, need_ratio = ctx.needs_input_grad[:4]
+        need_light, _, _, need_ratio = ctx.needs_input_grad[:4]
         with torch.cuda.device(dev):
-            d_lobes = _native.out_tensor((lt.count, 7), torch.float32, dev) if need_lobes else None
+            d_light = _native.out_tensor(lt.grad_shape, torch.float32, dev) if need_light else None
             d_alb = _native.out_tensor((N, 12), torch.float32, dev)
             d_rough = _native.out_tensor((N, 4), torch.float32, dev)
             d_ratio = _native.out_tensor((1,), torch.float32, dev) if need_ratio else None
             if N == 0:
-                for t in (d_lobes, d_ratio):
+                for t in (d_light, d_ratio):
                     if t is not None:
                         t.zero_()
             gdev = _native.f32c(g.detach(), dev).reshape(1).contiguous()   # the upstream scalar stays on the device
-            _native.check(_lib.svgir_radiance_loss_backward_sg(p, lt, _native.ptr(idx), _native.ptr(R), gdev.data_ptr(), _native.ptr(d_lobes),
-                                                               _native.ptr(d_alb), _native.ptr(d_rough), _native.ptr(d_ratio),
-                                                               _native.stream_ptr(dev)), "radiance_loss_backward_sg")
-        lobes_shape, alb_shape, rough_shape, ratio_shape = ctx.shapes
-        return (None if d_lobes is None else d_lobes.reshape(lobes_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape),
-                None if d_ratio is None else d_ratio.reshape(ratio_shape)) + (None,) * 10
+            _native.check(getattr(_lib, cls.BACKWARD)(p, *lt.args, _native.ptr(idx), _native.ptr(R), gdev.data_ptr(), _native.ptr(d_light),
+                                                      _native.ptr(d_alb), _native.ptr(d_rough), _native.ptr(d_ratio), _native.stream_ptr(dev)),
+                          cls.BACKWARD[len("svgir_"):])
+        light_shape, alb_shape, rough_shape, ratio_shape = ctx.shapes
+        return (None if d_light is None else d_light.reshape(light_shape), d_alb.reshape(alb_shape), d_rough.reshape(rough_shape),
+                None if d_ratio is None else d_ratio.reshape(ratio_shape)) + (None,) * (len(ctx.needs_input_grad) - 4)
+
+
+class _RadianceConsistency(_ConsistencyNode):
+    """The lat-long texture: env is the map, light = (softplus, scale, transform)."""
+    FORWARD, BACKWARD = "svgir_radiance_loss_forward", "svgir_radiance_loss_backward"
+
+    @staticmethod
+    def light(what, env, spec, dev):
+        softplus, scale, transform = spec
+        e = _native.f32c(env.detach(), dev)
+        if e.dim() < 3 or e.shape[-1] != 3 or e.shape[-3] < 1 or e.shape[-2] < 1 or e.numel() != e.shape[-3] * e.shape[-2] * 3:
+            raise ValueError(f"{what}: the light's map must be ONE [He,We,3] map (leading dimensions of 1 are fine), got {tuple(env.shape)}")
+        e = e.reshape(e.shape[-3:]).contiguous()
+        he, we = int(e.shape[0]), int(e.shape[1])
+        return types.SimpleNamespace(
+            args=(), fields=dict(env_h=he, env_w=we, env_softplus=int(bool(softplus)), env_scale=float(scale)), held=None,
+            tensors=lambda f: dict(env=e, env_transform=None if transform is None else f(transform, (3, 3), "the light's transform")),
+            work_bytes=lambda N: _lib.svgir_radiance_loss_work_bytes(N, he, we), grad_shape=(he, we, 3))
+
+    @staticmethod
+    def forward(ctx, env, albedos, roughnesses, radiance_ratio, light, *rest):
+        return _RadianceConsistency._forward(ctx, "radiance_consistency", env, light, () if light[2] is None else (light[2],), albedos,
+                                             roughnesses, radiance_ratio, *rest)
+
+    @staticmethod
+    def backward(ctx, g, _gi, _gr, _gt):
+        return _RadianceConsistency._backward(ctx, g)
+
+
+class _RadianceConsistencySG(_ConsistencyNode):
+    """A spherical-Gaussian light: the raw lobes [M,7] in the texture's place."""
+    FORWARD, BACKWARD = "svgir_radiance_loss_forward_sg", "svgir_radiance_loss_backward_sg"
+
+    @staticmethod
+    def light(what, lobes, spec, dev):
+        from gaussian_renderer import shading
+        lt, held = shading._sg_light(shading.SGLobes(lobes).lobes, dev)
+        return types.SimpleNamespace(args=(lt,), fields={}, held=held, tensors=lambda f: {},
+                                     work_bytes=lambda N: _lib.svgir_radiance_loss_sg_work_bytes(N, lt.count), grad_shape=(lt.count, 7))
+
+    @staticmethod
+    def forward(ctx, lobes, albedos, roughnesses, radiance_ratio, *rest):
+        return _RadianceConsistencySG._forward(ctx, "radiance_consistency_sg", lobes, None, (), albedos, roughnesses, radiance_ratio, *rest)
+
+    @staticmethod
+    def backward(ctx, g, _gi, _gr, _gt):
+        return _RadianceConsistencySG._backward(ctx, g)
 
 
 def _rows(what, t, shape, name):

@@ -220,6 +220,8 @@ for _S in (63, 64, 65, 129, 300):
     CASES["random_5x%d" % _S] = functools.partial(_base, 5, _S, 500 + _S)      # N = 5: one row past a forward workgroup's 4
 CASES["random_9x65"] = functools.partial(_base, 9, 65, 965)                    # one row past a backward pass of 8
 CASES["random_70x64"] = functools.partial(_base, 70, 64, 7064)
+# a backward that is not asked for d_radiance_ratio (the tests make the ratio no leaf)
+CASES["random_5x65_fixed_ratio"] = lambda: dict(_base(5, 65, 1565), ratio_grad=False)
 
 
 @_register

@@ -205,6 +205,10 @@ RL_CASES = {
     "hits_out_of_range-M128": _rl("hits_out_of_range", 128, 5), "ratio_zero-M32": _rl("ratio_zero", 32, 6),
     "at_camera-M33": _rl("at_camera", 33, 7), "non_finite-M32": _rl("random_70x64", 32, 8, non_finite=True),
     "random_9x65-M128": _rl("random_9x65", 128, 9), "physical-M32": _rl("physical", 32, 10),
+    # the SG backward's whole passes of 64 at the sample counts around them (one sample, one short of a pass, one past two passes), and a
+    # backward that is not asked for d_radiance_ratio (ratio_grad=False: the ratio is no leaf)
+    "self_hit_1x1-M1": _rl("self_hit_1x1", 1, 11), "random_5x63-M1": _rl("random_5x63", 1, 12), "random_5x129-M1": _rl("random_5x129", 1, 13),
+    "random_5x65-M1-fixed_ratio": _rl("random_5x65", 1, 14, ratio_grad=False),
 }
 RL_NAMES = sorted(RL_CASES)
 MAX_EXCLUDED = 0.05     # of the rows and of the lobes of a case
@@ -239,7 +243,7 @@ def rl_case(name):
         # directions are (radiance_loss_cases._base does the same for its own cases)
         d = c["ray_d"].astype(F64)
         c["ray_d"] = (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(F32)
-    c.update(radiances=rad.astype(F32), lobes=np.ascontiguousarray(lobes, dtype=F32))
+    c.update(radiances=rad.astype(F32), lobes=np.ascontiguousarray(lobes, dtype=F32), ratio_grad=spec.get("ratio_grad", True))
     for v in c.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)

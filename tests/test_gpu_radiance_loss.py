@@ -48,7 +48,7 @@ def _light(c, env):
 def _leaves(c, env_grad=True):
     env = _t(c["env"])[None] if c["softplus"] else _t(c["env"])          # DirectLightMap.env is [1,He,We,3]
     return [env.requires_grad_(env_grad), _t(c["albedos"]).requires_grad_(True), _t(c["roughnesses"]).requires_grad_(True),
-            _t(c["radiance_ratio"]).requires_grad_(True)]
+            _t(c["radiance_ratio"]).requires_grad_(c.get("ratio_grad", True))]   # (ratio_grad False: the backward gets no d_radiance_ratio)
 
 
 def _run(r, c, leaves, with_sum=True, conv=_t):
@@ -127,6 +127,9 @@ def _check_gradients(name, c, o, leaves, env_grad=True):
         assert env.grad is None
     N = c["N"]
     tol = (3 * N + 4) * 2.0 ** -24 * o["d_ratio_abs"] + 2 * o["unsafe_ratio_abs"]
+    if not c.get("ratio_grad", True):
+        assert ratio.grad is None
+        return
     assert ratio.grad is not None and ratio.grad.shape == ratio.shape
     assert abs(float(ratio.grad) - o["d_ratio"]) <= tol, (float(ratio.grad), o["d_ratio"], tol)
 

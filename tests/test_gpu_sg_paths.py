@@ -212,7 +212,7 @@ def _renderer(c):
 
 def _leaves(c, lobes_grad=True):
     return [_t(c["lobes"]).requires_grad_(lobes_grad), _t(c["albedos"]).requires_grad_(True), _t(c["roughnesses"]).requires_grad_(True),
-            _t(c["radiance_ratio"]).requires_grad_(True)]
+            _t(c["radiance_ratio"]).requires_grad_(c.get("ratio_grad", True))]   # (ratio_grad False: the backward gets no d_radiance_ratio)
 
 
 def _run(r, c, leaves, with_sum=True):
@@ -289,7 +289,10 @@ def test_fused_sg_loss_forward_and_backward(built, name):
             only[:, 0] |= k["thr"]
         _close(kind, leaf.grad, k[kind], k[kind + "_cnt"], k[kind + "_abs"], f"{name} {kind}", only)
     tol = (3 * N + 4) * 2.0 ** -24 * o["d_ratio_abs"] + 2 * o["unsafe_ratio_abs"]
-    assert ratio.grad is not None and abs(float(ratio.grad) - o["d_ratio"]) <= tol, (float(ratio.grad), o["d_ratio"], tol)
+    if c["ratio_grad"]:
+        assert ratio.grad is not None and abs(float(ratio.grad) - o["d_ratio"]) <= tol, (float(ratio.grad), o["d_ratio"], tol)
+    else:
+        assert ratio.grad is None
     assert lobes.grad is not None and lobes.grad.shape == lobes.shape and bool(torch.isfinite(lobes.grad).all())
     e = sc.row_err(lobes.grad, torch.from_numpy(o["d_lobes"]))
     e = torch.where(torch.from_numpy(o["unsafe_lobes"]), torch.zeros_like(e), e)
